@@ -14,11 +14,14 @@ warped (fused image + mask), fed to the blender and the panorama is produced in 
           8 frames per GPU (N = 8: configs[3], 64 frames).  --config 2 --gpus N: the tele-ring family of round 1.
   --config 3 / 4 at N = 1: one GPU's share of that configuration, unsharded (the same-family single-GPU rate).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel, HIP events on the
-stream the kernel runs on), `parity` (N = 1: the panorama of the timed path against the oracle's; N > 1: every rank's band
-against the oracle's columns of that band — rank 0 runs the oracle once on all frames, after the timed region;
---no-parity skips it) and `cpu_baseline` (the oracle, timed on the host cores, N = 1 only).  torch is imported only for N > 1 (rendezvous / barrier); the
-product path is ctypes -> libstitching_amd.so.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times exactly --steps steps and prints the headline (`value`,
+`ms_per_step` = milliseconds of one timed step).  --full adds everything else, each measured after the timed steps: `timed_rounds`
+(more rounds of --steps steps until --min-seconds are timed: the spread), `roofline` (dominant kernel, HIP events on the stream the
+kernel runs on), `kernels[]`, `parity` (N = 1: the panorama of the timed path against the oracle's; N > 1: every rank's band against
+the oracle's columns of that band — rank 0 runs the oracle once on all frames; --no-parity skips it), `cpu_baseline` (the oracle, timed
+on the host cores, N = 1 only), the latency of one panorama, the PCIe-inclusive rates and the extra legs.
+--dump-outputs DIR writes what the last timed step computed (see dump_outputs).  torch is imported only for N > 1 (rendezvous /
+barrier); the product path is ctypes -> libstitching_amd.so.
 """
 import argparse
 import glob
@@ -34,7 +37,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
-MIN_TIMED_S = 3.0      # the timed region is repeated in rounds of --steps until it holds at least this much work
+MIN_TIMED_S = 3.0      # --full: `timed_rounds` repeats rounds of --steps steps until they hold at least this much work
+DUMP_BYTES = 64 * 10**6  # --dump-outputs: all files of one run together stay below this
 
 
 def parse():
@@ -42,6 +46,11 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true", help="after the timed steps, also measure and check everything besides the headline: "
+                   "timed_rounds, roofline / kernels, parity, cpu_baseline, latency, PCIe-inclusive rates, extra legs (N > 1: the "
+                   "same-family single-GPU rate and the per-rank parity)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR", help="write the panorama and mask of the last timed step as float32 / "
+                   "float64 .npy files under DIR (a seeded sample of the pixels where the whole would exceed 64 MB)")
     p.add_argument("--config", type=int, default=0, help="BASELINE configuration 2..5 (1-based as in DESIGN.md); default: 2 at "
                    "N = 1, 3 at N > 1")
     p.add_argument("--frames-per-gpu", type=int, default=0, help="config 2 only (default 8)")
@@ -50,19 +59,22 @@ def parse():
     p.add_argument("--bands", type=int, default=0)
     p.add_argument("--warper", default="")
     p.add_argument("--blender", default="")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-parity", action="store_true", help="N > 1: skip the comparison of every rank's band with the oracle's "
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline (and with it the N = 1 parity)")
+    p.add_argument("--no-parity", action="store_true", help="--full, N > 1: skip the comparison of every rank's band with the oracle's "
                    "panorama (rank 0 runs the oracle once on all frames, outside the timed region)")
-    p.add_argument("--no-extra", action="store_true", help="skip the extra legs (seam masks, configs 4 / 5, latency)")
+    p.add_argument("--no-extra", action="store_true", help="--full: skip the extra legs (seam masks, configs 4 / 5, modes)")
     p.add_argument("--cpu-frames", type=int, default=0, help="frames in the CPU-baseline sample (0: all frames of the step, which also gives `parity`)")
-    p.add_argument("--profile-steps", type=int, default=10)
-    p.add_argument("--min-seconds", type=float, default=MIN_TIMED_S)
+    p.add_argument("--profile-steps", type=int, default=10, help="--full: steps of the per-kernel HIP-event pass")
+    p.add_argument("--min-seconds", type=float, default=MIN_TIMED_S, help="--full: seconds of work the `timed_rounds` record holds at least")
     p.add_argument("--streams", type=int, default=2, help="panoramas in flight per GPU (contexts = HIP streams); N = 1 "
                    "measured: 1 -> 93.0, 2 -> 105.9, 3 -> 99.6 Gpix/s")
-    p.add_argument("--e2e-steps", type=int, default=2, help="PCIe-inclusive passes (host frames in, host panorama out)")
+    p.add_argument("--e2e-steps", type=int, default=2, help="--full: PCIe-inclusive passes (host frames in, host panorama out)")
     p.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "r06_traffic.json"),
                    help="JSON with PMC-derived HBM bytes per launch and rocprofv3's average launch durations (tools/make_traffic_json.py)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def kernel_source_hash():
@@ -341,6 +353,46 @@ def sharded_parity(job, dist, rank, world, wl, all_cams):
     return rec
 
 
+def timed_steps(run_step, barrier, steps, warmup, n_inflight, reduce_max):
+    """W warm-up steps per panorama in flight, then exactly `steps` timed steps between barriers + stream syncs (max over ranks).
+    Returns (seconds, what the last timed step returned); the earlier steps' outputs are dropped as they come back."""
+    for i in range(warmup * n_inflight):
+        run_step(i)
+    barrier()
+    t0 = time.perf_counter()
+    for i in range(steps - 1):
+        run_step(i)
+    last = run_step(steps - 1)
+    barrier()
+    return reduce_max(time.perf_counter() - t0), last
+
+
+def dump_outputs(out_dir, outputs, rank, world):
+    """--dump-outputs: what the last timed step handed its caller — the panorama (u8 x3) and its mask (u8); at N > 1 this rank's
+    band, files suffixed _rank<r> — as .npy files: `panorama` / `mask` in float32, whole where they fit this rank's share of
+    DUMP_BYTES, else the same seeded sample of pixel positions of both (flattened; the sample depends on the shape alone), and always
+    `panorama_row_sums` / `panorama_col_sums` / `mask_row_sums` / `mask_col_sums` over every pixel in float64."""
+    import numpy as np
+
+    pano, mask = (np.asarray(a) for a in outputs)
+    h, w = mask.shape
+    c = pano.shape[2]
+    sfx = f"_rank{rank}" if world > 1 else ""
+    sums = {"panorama_row_sums": pano.sum(axis=1, dtype=np.float64), "panorama_col_sums": pano.sum(axis=0, dtype=np.float64),
+            "mask_row_sums": mask.sum(axis=1, dtype=np.float64), "mask_col_sums": mask.sum(axis=0, dtype=np.float64)}
+    room = DUMP_BYTES // world - sum(a.nbytes for a in sums.values()) - 6 * 4096  # .npy headers
+    n_px = max(0, room // (4 * (c + 1)))
+    if n_px >= h * w:
+        arrays = {"panorama": pano.astype(np.float32), "mask": mask.astype(np.float32)}
+    else:
+        idx = np.unique(np.random.default_rng(20251016).integers(0, h * w, n_px))
+        arrays = {"panorama": pano.reshape(-1, c)[idx].astype(np.float32), "mask": mask.reshape(-1)[idx].astype(np.float32)}
+    arrays.update(sums)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a)
+
+
 def timed_rounds(run_step, barrier, steps, warmup, n_inflight, min_seconds, reduce_max):
     """W warm-up steps, then rounds of exactly K timed steps (barrier + stream sync on both sides, max over ranks) until
     the rounds hold >= min_seconds of work.  Returns (seconds per round list)."""
@@ -478,37 +530,43 @@ def main():
         return dt if dist is None else dist.all_reduce_max(dt)
 
     def run_step(i):
-        out = jobs[i % len(jobs)].run()
-        del out
+        return jobs[i % len(jobs)].run()
 
-    rounds = timed_rounds(run_step, barrier, args.steps, args.warmup, len(jobs), args.min_seconds, reduce_max)
-    steps_executed = args.steps * len(rounds)
-    dt_total = sum(rounds)
+    dt_total, last = timed_steps(run_step, barrier, args.steps, args.warmup, len(jobs), reduce_max)
+    ms_per_step = dt_total / args.steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, rank, world)
+    del last
 
-    # per-kernel durations: HIP events on the ctx stream, separate pass over the same steps
-    ctx.prof_reset()
-    ctx.prof_enable(True)
-    for _ in range(max(1, args.profile_steps)):
-        out = job.run()
-        del out
-    ctx.prof_enable(False)
-    kernels = ctx.prof_results()
-    ctx.prof_reset()
+    share = parity_n = None
+    if args.full:
+        # the spread of the headline: more rounds of exactly --steps steps (the headline's round first) until >= --min-seconds are timed
+        rounds = [dt_total]
+        if dt_total < args.min_seconds:
+            rounds += timed_rounds(run_step, barrier, args.steps, 0, len(jobs), args.min_seconds - dt_total, reduce_max)
 
-    # the same-family single-GPU rate (N > 1): this rank's share as an unsharded panorama of its own — no strips, no
-    # exchange, the whole band; what `value / n_gpus` is to be compared with, since the N = 1 line is another geometry
-    share = None
-    if world > 1:
-        sj = [StitchJob(jobs[0].frames, cams, warper_type=wl["warper"], blender_type=wl["blender"], num_bands=nb, ctx=c) for c in ctxs]
-        for j in sj:
-            j.warper.set_scale(all_cams)
-        sr = timed_rounds(lambda i: sj[i % len(sj)].run(), barrier, max(4, args.steps // 2), 1, len(sj), args.min_seconds / 2, reduce_max)
-        share = fpg * W * H / 1e6 / (sum(sr) / (max(4, args.steps // 2) * len(sr)))
-        del sj
+        # per-kernel durations: HIP events on the ctx stream, separate pass over the same steps
+        ctx.prof_reset()
+        ctx.prof_enable(True)
+        for _ in range(max(1, args.profile_steps)):
+            out = job.run()
+            del out
+        ctx.prof_enable(False)
+        kernels = ctx.prof_results()
+        ctx.prof_reset()
 
-    parity_n = None
-    if world > 1 and not args.no_parity:  # every blender type shards (feather and "no": distributed.py, round 3)
-        parity_n = sharded_parity(jobs[0], dist, rank, world, wl, all_cams)
+        # the same-family single-GPU rate (N > 1): this rank's share as an unsharded panorama of its own — no strips, no
+        # exchange, the whole band; what `value / n_gpus` is to be compared with, since the N = 1 line is another geometry
+        if world > 1:
+            sj = [StitchJob(jobs[0].frames, cams, warper_type=wl["warper"], blender_type=wl["blender"], num_bands=nb, ctx=c) for c in ctxs]
+            for j in sj:
+                j.warper.set_scale(all_cams)
+            sr = timed_rounds(lambda i: sj[i % len(sj)].run(), barrier, max(4, args.steps // 2), 1, len(sj), args.min_seconds / 2, reduce_max)
+            share = fpg * W * H / 1e6 / (sum(sr) / (max(4, args.steps // 2) * len(sr)))
+            del sj
+
+        if world > 1 and not args.no_parity:  # every blender type shards (feather and "no": distributed.py, round 3)
+            parity_n = sharded_parity(jobs[0], dist, rank, world, wl, all_cams)
 
     if rank != 0:
         if dist is not None:
@@ -519,8 +577,39 @@ def main():
     src_mpix = n_total * W * H / 1e6
     wsz = job.plan_.sizes if world > 1 else job.warped_sizes
     warped_mpix = sum(w * h for w, h in wsz) / 1e6
-    ms_per_step = dt_total / steps_executed * 1e3
     value = src_mpix / (ms_per_step / 1e3)
+    bands_txt = f"{getattr(job, 'last_num_bands', wl['bands'])}-band " if wl["blender"] == "multiband" else ""
+    result = {
+        "metric": "warped+blended Mpix/s", "value": round(value, 1), "unit": "Mpix/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "u8/int16 (fixed-point remap, int32 pyramid sums, fp32 weights)",
+        "data": "synthetic",
+        "steps_executed": args.steps,
+        "config": {"workload": f"{wl['name']}; {wl['warper']} warp + {bands_txt}{wl['blender']} blend, inputs resident in HBM",
+                   "baseline_config": wl["cfg"], "frames_per_gpu": fpg,
+                   "sharding": ("contiguous yaw columns -> panorama column bands, "
+                                + ("warped-image strips" if getattr(jobs[0], "exchange", "strips") == "strips" else "per-level contribution strips")
+                                + f" over {jobs[0].transport.name} send/recv") if world > 1 else "single GPU",
+                   "ranks_share_a_gpu": bool(shared and world > 1),
+                   "panoramas_in_flight": len(jobs),
+                   "warped_mpix_per_step": round(warped_mpix, 2),
+                   "source_mpix_per_step": round(src_mpix, 2)},
+    }
+    if world > 1:
+        p = job.plan_
+        tr = jobs[0].transport
+        result["config"]["transport"] = dict(name=tr.name, **(tr.info() if hasattr(tr, "info") else {}))  # rccl: ncclCommCount, ncclGetVersion
+        result["config"]["exchange"] = {"messages": len(p.messages), "bytes_per_step": p.exchanged_bytes(),
+                                        "rank0_sends_MB": round(sum(m[4] for m in p.sends(0)) / 1e6, 1),
+                                        "busiest_link_MB": round(p.busiest_link_bytes() / 1e6, 1),  # xGMI is point to point
+                                        "band_balance": p.balance, "band_edges": p.edges}
+    if not args.full:
+        print(json.dumps(result), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.close()
+        return
+
     per_round = sorted(src_mpix * args.steps / r for r in rounds)
     kernels.sort(key=lambda k: -k["total_ms"])
     dom = kernels[0]
@@ -553,26 +642,14 @@ def main():
     roofline["path_frac"] = {"algo_bytes_per_step": round(kbytes / psteps),
                              "over_wall": round(kbytes / psteps / (ms_per_step / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
                              "over_kernel_sum": round(kbytes / max(ksum, 1e-9) / 1e6 / HBM_PEAK_GBS, 4)}
-    bands_txt = f"{getattr(job, 'last_num_bands', wl['bands'])}-band " if wl["blender"] == "multiband" else ""
-    result = {
-        "metric": "warped+blended Mpix/s", "value": round(value, 1), "unit": "Mpix/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "u8/int16 (fixed-point remap, int32 pyramid sums, fp32 weights)",
-        "data": "synthetic",
-        "steps_executed": steps_executed,
-        "timed_rounds": {"rounds": len(rounds), "steps_per_round": args.steps, "seconds": round(dt_total, 4),
+    rounds_s = sum(rounds)
+    result.update({
+        "timed_rounds": {"rounds": len(rounds), "steps_per_round": args.steps, "seconds": round(rounds_s, 4),
+                         "value": round(src_mpix * args.steps * len(rounds) / rounds_s, 1),
                          "value_min": round(per_round[0], 1), "value_median": round(per_round[len(per_round) // 2], 1),
                          "value_max": round(per_round[-1], 1),
-                         "note": "rounds of exactly --steps steps, repeated until >= %.2g s are timed; value = all steps / all time" % args.min_seconds},
-        "config": {"workload": f"{wl['name']}; {wl['warper']} warp + {bands_txt}{wl['blender']} blend, inputs resident in HBM",
-                   "baseline_config": wl["cfg"], "frames_per_gpu": fpg,
-                   "sharding": ("contiguous yaw columns -> panorama column bands, "
-                                + ("warped-image strips" if getattr(jobs[0], "exchange", "strips") == "strips" else "per-level contribution strips")
-                                + f" over {jobs[0].transport.name} send/recv") if world > 1 else "single GPU",
-                   "ranks_share_a_gpu": bool(shared and world > 1),
-                   "panoramas_in_flight": len(jobs),
-                   "warped_mpix_per_step": round(warped_mpix, 2),
-                   "source_mpix_per_step": round(src_mpix, 2)},
+                         "note": "the headline's round of exactly --steps steps and more such rounds until >= %.2g s are timed; "
+                                 "value = all steps / all time" % args.min_seconds},
         "roofline": roofline,
         "kernels": [{"kernel": k["kernel"], "calls_per_step": k["calls"] / max(1, args.profile_steps),
                      "avg_us": round(k["total_ms"] / k["calls"] * 1e3, 2),
@@ -586,17 +663,10 @@ def main():
                         "note": "bytes the fused kernels move (algorithmic, per kernel) / summed kernel time: the bandwidth fraction of the path; "
                                 "kernels[].traffic = HBM bytes per launch from the PMC passes (2 x FETCH_SIZE + WRITE_SIZE, mean over the launches "
                                 "of that name), null unless the profile was taken on these very kernel sources"},
-    }
+    })
     if parity_n is not None:
         result["parity"] = parity_n
     if world > 1:
-        p = job.plan_
-        tr = jobs[0].transport
-        result["config"]["transport"] = dict(name=tr.name, **(tr.info() if hasattr(tr, "info") else {}))  # rccl: ncclCommCount, ncclGetVersion
-        result["config"]["exchange"] = {"messages": len(p.messages), "bytes_per_step": p.exchanged_bytes(),
-                                        "rank0_sends_MB": round(sum(m[4] for m in p.sends(0)) / 1e6, 1),
-                                        "busiest_link_MB": round(p.busiest_link_bytes() / 1e6, 1),  # xGMI is point to point
-                                        "band_balance": p.balance, "band_edges": p.edges}
         result["same_family_single_gpu"] = {
             "value_per_gpu": round(share, 1), "unit": "Mpix/s",
             "efficiency_vs_it": round(value / world / share, 4),

@@ -6,11 +6,12 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for i in $(seq $REPS); do
   for mode in base switch; do
     if [ $mode = switch ]; then export $SW; else unset ${SW%%=*}; fi
-    timeout 600 python bench.py --no-cpu-baseline --e2e-steps 0 ${AB_ARGS:---no-extra} --steps 20 > "$OUT/bench_${mode}_$i.json" 2> "$OUT/bench_${mode}_$i.err"
+    timeout 600 python bench.py --full --no-cpu-baseline --e2e-steps 0 ${AB_ARGS:---no-extra} --steps 20 > "$OUT/bench_${mode}_$i.json" 2> "$OUT/bench_${mode}_$i.err"
     python - "$OUT/bench_${mode}_$i.json" $mode <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
-print(sys.argv[2], "value", d["value"], "ms/step", d["ms_per_step"], " ".join("%s=%.1f" % (k["kernel"], k["avg_us"]) for k in d["kernels"]))
+tr=d["timed_rounds"]
+print(sys.argv[2], "value", tr["value"], "ms/step", round(tr["seconds"] * 1e3 / (tr["rounds"] * tr["steps_per_round"]), 4), " ".join("%s=%.1f" % (k["kernel"], k["avg_us"]) for k in d["kernels"]))
 PY
   done
 done

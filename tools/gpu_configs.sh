@@ -7,9 +7,10 @@ run() { name=$1; shift; timeout 600 python bench.py --no-cpu-baseline --e2e-step
 python - "$name" <<'PY'
 import json,sys
 d=json.loads(open(f"gpurun_out/configs/{sys.argv[1]}.json").read().strip().splitlines()[-1])
-print(sys.argv[1], d["value"], "Mpix/s", d["ms_per_step"], "ms/step;", d["config"]["workload"], "; dominant", d["roofline"]["kernel"], d["roofline"]["frac"])
+tr=d["timed_rounds"]
+print(sys.argv[1], tr["value"], "Mpix/s", round(tr["seconds"] * 1e3 / (tr["rounds"] * tr["steps_per_round"]), 4), "ms/step;", d["config"]["workload"], "; dominant", d["roofline"]["kernel"], d["roofline"]["frac"])
 PY
 }
-run config4_cyl7 --warper cylindrical --bands 7 --width 8000 --height 6000 --frames-per-gpu 8
-run config5_affine_feather --warper affine --blender feather --frames-per-gpu 16
-run config5_affine_no --warper affine --blender no --frames-per-gpu 16
+run config4_cyl7 --full --warper cylindrical --bands 7 --width 8000 --height 6000 --frames-per-gpu 8
+run config5_affine_feather --full --warper affine --blender feather --frames-per-gpu 16
+run config5_affine_no --full --warper affine --blender no --frames-per-gpu 16

@@ -273,6 +273,34 @@ int stx_block_gain_apply(stx_ctx* ctx, stx_buf* img_u8x3, const stx_buf* gain_ma
 #define STX_GAIN_MAP_BOUNDED 1
 int stx_block_gain_apply_batch(stx_ctx* ctx, int n, stx_buf* const* imgs_u8x3, const stx_buf* const* gain_maps_f32,
                                const int* full_wh_xy0, const int* flags);
+/* ---- exposure-gain estimation: ExposureCompensator::feed (stitching/exposure_error_compensator.py:39-41) ------------------------
+ * kind: the cv.detail ids of the compensators that estimate (ExposureCompensator_GAIN, _GAIN_BLOCKS, _CHANNELS, _CHANNELS_BLOCKS).
+ * The overlap statistics of every feed are one kernel launch over a table of unit pairs (whole images or blocks); the linear system
+ * is assembled and solved on the host (OpenCV's cv::solve(DECOMP_LU), eliminating only non-zero entries: the same bits as the dense
+ * loop).  Parity: a restatement of OpenCV 4.x from recollection; tests/numpy_exposure.py is the contract. */
+#define STX_EXPOSURE_GAIN 1
+#define STX_EXPOSURE_GAIN_BLOCKS 2
+#define STX_EXPOSURE_CHANNELS 3
+#define STX_EXPOSURE_CHANNELS_BLOCKS 4
+/* The whole feed of n u8x3 images and their u8x1 masks (pixels count where both masks are 255) at corners_xy.  Gains go to
+ * out_gains image after image: gain 1 value, channels 3 (BGR), gain_blocks bh x bw fp32 map values (filtered as getMatGains returns
+ * them), channels_blocks bh x bw x 3, with bw = ceil(w / block_size), bh = ceil(h / block_size).  *inout_count: capacity of
+ * out_gains in values; out_gains NULL: only writes the count needed (no GPU work).  The images are never modified.
+ * out_info (or NULL): {units, pair jobs, device statistics ms (HIP events, all feeds), host assembly + solve + filter ms}. */
+int stx_exposure_feed(stx_ctx* ctx, int kind, int n, const stx_buf* const* imgs_u8x3, const stx_buf* const* masks_u8,
+                      const int* corners_xy, int block_size, int nr_feeds, double* out_gains, long long* inout_count,
+                      double out_info[4]);
+/* The statistics of the first feed alone, per pair job: units (a, b) with a <= b, the count c of pixels both masks hold 255 in,
+ * and the sums of norms over them ({sum_a, sum_b} for the gain kinds; {B, G, R of a, B, G, R of b} for the channel kinds: six
+ * values per job either way).  out_ab NULL: only writes *inout_jobs (the pair enumeration runs, no GPU work). */
+int stx_exposure_stats(stx_ctx* ctx, int kind, int n, const stx_buf* const* imgs_u8x3, const stx_buf* const* masks_u8,
+                       const int* corners_xy, int block_size, long long* inout_jobs, int* out_ab, long long* out_c,
+                       double* out_sums);
+/* Host only (no context, no GPU): assembly + solve of GainCompensator::singleFeed from given statistics of m units.  npairs entries
+ * (i, j) with i <= j; n_iij_iji = {N(i,j), I(i,j), I(j,i)} each; pairs not listed have N = 0.  skip[u] != 0: unit u overlaps no
+ * other unit (gain 1).  out_gains: m values. */
+int stx_exposure_solve(int m, int npairs, const int* pairs_ij, const double* n_iij_iji, const unsigned char* skip,
+                       double* out_gains);
 /* stx_resize_linear_exact <- stitching/images.py:122-124 cv.resize(img, size, interpolation=cv.INTER_LINEAR_EXACT) (u8x1 / u8x3:
  *                            the final-resolution resize of Images.resize, next row N3)
  * stx_seam_mask_resize    <- stitching/seam_finder.py:37-43 SeamFinder.resize: cv.dilate(seam_mask, None), cv.resize(...,

@@ -3,6 +3,8 @@ unknown keys, so the back end is configured here / by environment, never through
 import os
 
 _device_resident = os.environ.get("STITCHING_AMD_DEVICE_RESIDENT", "0") not in ("0", "", "false", "False")
+EXPOSURE_ESTIMATORS = ("opencv", "device")
+_exposure_estimator = None  # None: STITCHING_AMD_EXPOSURE_ESTIMATOR decides at the first use
 
 
 def set_device_resident(on=True):
@@ -91,3 +93,29 @@ def pyrdown_mode():
     lanes = C.c_int()
     m = _lib.lib().stx_get_pyrdown_mode(C.byref(lanes))
     return {v: k for k, v in _lib.PYRDOWN_MODES.items()}[m], int(lanes.value)
+
+
+def _parse_exposure_estimator(mode):
+    if mode not in EXPOSURE_ESTIMATORS:
+        from .stitching_error import StitchingError
+
+        raise StitchingError(f"unknown exposure estimator {mode!r}: one of {list(EXPOSURE_ESTIMATORS)}")
+    return mode
+
+
+def set_exposure_estimator(mode):
+    """Who estimates the gains of an ExposureErrorCompensator built without estimator=: "opencv" (default: the cv.detail compensator
+    the reference builds, when cv2 is importable) or "device" (stitching_amd.ExposureEstimator: statistics in HIP, solve on the host;
+    the reference's parameter rules — "gain" / "gain_blocks" through createDefault, which ignores nr_feeds and block_size).
+    Process-wide; STITCHING_AMD_EXPOSURE_ESTIMATOR sets the start-up value.  Returns the previous mode."""
+    global _exposure_estimator
+    prev = exposure_estimator()
+    _exposure_estimator = _parse_exposure_estimator(mode)
+    return prev
+
+
+def exposure_estimator():
+    global _exposure_estimator
+    if _exposure_estimator is None:
+        _exposure_estimator = _parse_exposure_estimator(os.environ.get("STITCHING_AMD_EXPOSURE_ESTIMATOR", "opencv") or "opencv")
+    return _exposure_estimator

@@ -85,6 +85,8 @@ struct stx_ctx {
     std::vector<StxPendingEvent> prof_pending;
     std::vector<hipEvent_t> event_pool;
     hipEvent_t marks[16] = {};
+    // exposure estimation: sqrt(k) for k = 0 .. 3 * 255^2 in fp64, uploaded at the first feed (an allocator block: freed with the context)
+    double* exp_sqrt = nullptr;
 };
 
 #define STX_STAGE_SEGS 4
@@ -211,6 +213,16 @@ int stx_launch_block_gain_batch(stx_ctx* ctx, int n, stx_buf* const* imgs, const
 // that multiplies the gain in itself (the warp kernel's epilogue); wh = {w, h} per rectangle
 int stx_launch_gain_rows(stx_ctx* ctx, int n, const int* wh, const stx_buf* const* gmaps, const int* full_wh_xy0, float* const* Hs,
                          void* const* yts);
+// exposure-gain estimation (stx_exposure.hip, stx_exposure_host.cpp) ---------------------------------------------------------------
+struct StxExpImg { const uint8_t* img; long long istride; const uint8_t* mask; long long mstride; };
+// a pair job: images ia / ib, the intersection's top-left in each image (ax, ay) / (bx, by), its size w x h
+struct StxExpJob { int ia, ib, ax, ay, bx, by, w, h; };
+enum { STX_EXP_TREE = 0, STX_EXP_ORDERED = 1, STX_EXP_INT = 2 };
+int stx_launch_exposure_stats(stx_ctx* ctx, const StxExpImg* d_imgs, const StxExpJob* d_jobs, int njobs, int mode, const double* d_sqrt,
+                              long long* d_out_i, double* d_out_d, double algo_bytes);
+// one u8x3 image multiplied by per-block gains g (bpw blocks of bw x bh per row, 1 or 3 (g3) floats per block)
+struct StxExpBlockMul { uint8_t* img; long long stride; int w, h, bw, bh, bpw; const float* g; int g3; };
+int stx_launch_exposure_block_mul(stx_ctx* ctx, const StxExpBlockMul* d_tab, int n, int max_pixels);
 // cv::resize(INTER_LINEAR_EXACT) u8 (next rows N2 / N3); d_xt / d_yt: device tables of (offset, coeff1 | interior << 16)
 int stx_launch_resize_exact(stx_ctx* ctx, const stx_buf* src, stx_buf* dst, const int* d_xt, const int* d_yt, bool dilate,
                             const stx_buf* andmask);

@@ -1,7 +1,7 @@
 """ExposureErrorCompensator.apply on the device.
 
 The reference class (stitching/exposure_error_compensator.py:6-45) wraps cv.detail exposure compensators:
-`feed` estimates gains on low-resolution images (out of scope: a small least-squares solve, it stays in OpenCV),
+`feed` estimates gains on low-resolution images (a small least-squares solve: OpenCV's by default, see below),
 `apply(idx, corner, img, mask)` multiplies the final-resolution warped image by the gain, between warp and
 blend (stitching/stitcher.py:123,219-221).  This class keeps the surface and runs `apply` in HBM for the
 "gain" and "channel" compensators (one gain per image / per channel); gains come from `set_gains` — e.g. from
@@ -12,7 +12,9 @@ fp32 gain maps (one / three channels) with cv::resize(INTER_LINEAR) inside the s
 (stitching/exposure_error_compensator.py:25-37), `feed(corners, imgs, masks)` runs its estimation on the low-resolution
 images and hands `getMatGains()` to `set_gains` — so `Stitcher.estimate_exposure_errors` / `compensate_exposure_errors`
 (stitching/stitcher.py:210-221) work unmodified with this class in place of the reference's.  Any object with
-`feed(corners, imgs, masks)` and `getMatGains()` can be passed as `estimator=` instead.
+`feed(corners, imgs, masks)` and `getMatGains()` can be passed as `estimator=` instead.  With
+`config.set_exposure_estimator("device")` the constructor builds a `stitching_amd.ExposureEstimator` (estimation in HIP, no cv2), and
+`feed` hands it the images as they are: device images stay on the device.
 """
 import ctypes as C
 from collections import OrderedDict
@@ -47,7 +49,24 @@ class ExposureErrorCompensator:
         # agreement) compares it with the version it derived from
         self.gains_version = 0
         self._dev_gains = {}  # (context, image index) -> (DeviceImage of the gain map, STX_GAIN_MAP_BOUNDED flag): uploaded once
-        self.compensator = estimator if estimator is not None else self._cv_estimator(compensator, nr_feeds, block_size)
+        if estimator is not None:
+            self.compensator = estimator
+        elif config.exposure_estimator() == "device":
+            self.compensator = self._device_estimator(compensator, nr_feeds, block_size)
+        else:
+            self.compensator = self._cv_estimator(compensator, nr_feeds, block_size)
+
+    @staticmethod
+    def _device_estimator(compensator, nr_feeds, block_size):
+        """The ExposureEstimator standing for _cv_estimator's object, with its parameter rules ("gain" / "gain_blocks" through
+        createDefault: one feed, 32 x 32 blocks), or None for "no"."""
+        from .exposure_estimation import ExposureEstimator
+
+        if compensator in ("channel", "channel_blocks"):
+            return ExposureEstimator(compensator, nr_feeds, block_size)
+        if compensator in ("gain", "gain_blocks"):
+            return ExposureEstimator(compensator)
+        return None
 
     @staticmethod
     def _cv_estimator(compensator, nr_feeds, block_size):
@@ -82,6 +101,12 @@ class ExposureErrorCompensator:
         if self.compensator is None:
             raise StitchingError("gain estimation (ExposureCompensator::feed) needs OpenCV, which is not importable here: pass "
                                  "an estimator= object or call set_gains() with the gains of a cv2 compensator")
+        from .exposure_estimation import ExposureEstimator
+
+        if isinstance(self.compensator, ExposureEstimator):  # takes device images as they are
+            self.compensator.feed(list(corners), list(imgs), list(masks))
+            self.set_gains(self.compensator.getMatGains())
+            return
         host = lambda a: np.asarray(a.get() if hasattr(a, "get") else a)  # noqa: E731 - device images / cv.UMat -> numpy
         self.compensator.feed(list(corners), [host(i) for i in imgs], [host(m) for m in masks])
         self.set_gains([host(g) for g in self.compensator.getMatGains()])

@@ -1,0 +1,145 @@
+"""Exposure-gain estimation on the device: ExposureCompensator::feed for "gain", "gain_blocks", "channel" and "channel_blocks".
+
+`ExposureEstimator` is duck-typed like the cv.detail compensators the reference builds (stitching/exposure_error_compensator.py:25-41):
+`feed(corners, imgs, masks)` on the low-resolution warped images, then `getMatGains()`.  The overlap statistics of every feed are one
+HIP launch over a table of unit pairs (csrc/stx_exposure.hip); the small linear system is assembled and solved on the host
+(csrc/stx_exposure_host.cpp).  The algorithm restates OpenCV 4.x from recollection; tests/numpy_exposure.py is the contract and fidelity to
+real OpenCV is unpinned.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .device import DeviceImage, as_device, get_context
+from .stitching_error import StitchingError
+
+
+def _check_image(a, what, i):
+    """Shape / dtype check without a host copy of device images."""
+    if isinstance(a, DeviceImage):
+        ch, dt, hw = a.channels, a.dtype, (a.height, a.width)
+    else:
+        if not isinstance(a, np.ndarray) and hasattr(a, "get"):
+            a = a.get()
+        a = np.asarray(a)
+        if a.ndim not in (2, 3):
+            raise StitchingError(f"{what} {i}: expected an HxW or HxWxC array, got shape {a.shape}")
+        ch, dt, hw = (1 if a.ndim == 2 else a.shape[2]), a.dtype, a.shape[:2]
+    want = 3 if what == "image" else 1
+    if dt != np.uint8 or ch != want:
+        raise StitchingError(f"{what} {i}: exposure estimation needs u8 with {want} channel(s), got {dt} with {ch}")
+    if hw[0] == 0 or hw[1] == 0:
+        raise StitchingError(f"{what} {i}: empty image")
+    return a, hw
+
+
+def _block_grid(w, h, bl):
+    bpw, bph = -(-w // bl), -(-h // bl)
+    return bpw, bph
+
+
+class ExposureEstimator:
+    """ExposureCompensator::feed on the device.  kind: "gain" | "gain_blocks" | "channel" | "channel_blocks"; nr_feeds and
+    block_size as cv.detail_ChannelsCompensator(nr_feeds) / cv.detail_BlocksChannelsCompensator(bl, bl, nr_feeds) take them."""
+
+    def __init__(self, kind, nr_feeds=1, block_size=32):
+        if kind not in _lib.EXPOSURE_KINDS:
+            raise StitchingError(f"unknown exposure estimator kind {kind!r}: one of {sorted(_lib.EXPOSURE_KINDS)}")
+        if int(nr_feeds) < 1 or int(block_size) < 1:
+            raise StitchingError("nr_feeds and block_size must be >= 1")
+        self.kind, self.nr_feeds, self.block_size = kind, int(nr_feeds), int(block_size)
+        self.gains = []
+        self.info = None  # of the last feed: units, pair jobs, device statistics ms, host solve + filter ms
+
+    def _prepare(self, corners, imgs, masks):
+        imgs, masks, corners = list(imgs), list(masks), [tuple(int(v) for v in c) for c in corners]
+        if not (len(imgs) == len(masks) == len(corners)):
+            raise StitchingError("feed needs as many corners, images and masks")
+        sizes = []
+        for i, (im, mk) in enumerate(zip(imgs, masks)):
+            im, hw = _check_image(im, "image", i)
+            mk, mhw = _check_image(mk, "mask", i)
+            if hw != mhw:
+                raise StitchingError(f"mask {i} is {mhw[1]}x{mhw[0]}, its image {hw[1]}x{hw[0]}")
+            imgs[i], masks[i] = im, mk
+            sizes.append(hw)
+        ctxs = {id(a.ctx): a.ctx for a in imgs + masks if isinstance(a, DeviceImage)}
+        if len(ctxs) > 1:
+            raise StitchingError("device images of more than one context")
+        ctx = next(iter(ctxs.values())) if ctxs else get_context()
+        d_imgs = [as_device(a, ctx) for a in imgs]
+        d_masks = [as_device(a, ctx) for a in masks]
+        n = len(imgs)
+        cs = np.ascontiguousarray(np.asarray(corners, np.int32).reshape(n, 2))
+        return ctx, n, d_imgs, d_masks, cs, sizes
+
+    def feed(self, corners, imgs, masks):
+        """Estimate the gains (numpy arrays, cv.UMat-likes or DeviceImages of one context; the images are not modified)."""
+        corners, imgs, masks = list(corners), list(imgs), list(masks)
+        if not corners and not imgs and not masks:
+            return
+        ctx, n, d_imgs, d_masks, cs, sizes = self._prepare(corners, imgs, masks)
+        kind = _lib.EXPOSURE_KINDS[self.kind]
+        ia, ma = (C.c_void_p * n)(*[a._h for a in d_imgs]), (C.c_void_p * n)(*[a._h for a in d_masks])
+        cp = cs.ctypes.data_as(C.POINTER(C.c_int))
+        count = C.c_longlong(0)
+        _lib.check(ctx._lib.stx_exposure_feed(ctx.handle, kind, n, ia, ma, cp, self.block_size, self.nr_feeds, None, C.byref(count), None))
+        out = np.zeros(max(1, count.value), np.float64)
+        info = np.zeros(4, np.float64)
+        _lib.check(ctx._lib.stx_exposure_feed(ctx.handle, kind, n, ia, ma, cp, self.block_size, self.nr_feeds,
+                                              out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(count),
+                                              info.ctypes.data_as(C.POINTER(C.c_double))))
+        self.info = {"units": int(info[0]), "pair_jobs": int(info[1]), "stats_ms": float(info[2]), "solve_ms": float(info[3])}
+        gains, o = [], 0
+        for h, w in sizes:
+            if self.kind == "gain":
+                gains.append(out[o:o + 1].reshape(1, 1).copy())
+                o += 1
+            elif self.kind == "channel":
+                gains.append(out[o:o + 3].reshape(3, 1).copy())
+                o += 3
+            else:
+                bpw, bph = _block_grid(w, h, self.block_size)
+                k = bpw * bph * (3 if self.kind == "channel_blocks" else 1)
+                g = out[o:o + k].astype(np.float32)
+                gains.append(g.reshape(bph, bpw, 3) if self.kind == "channel_blocks" else g.reshape(bph, bpw))
+                o += k
+        self.gains = gains
+
+    def getMatGains(self):  # noqa: N802 - the cv.detail name
+        """Per image: "gain" (1, 1) float64, "channel" (3, 1) float64 BGR, the block kinds their filtered float32 gain maps."""
+        return [g.copy() for g in self.gains]
+
+    def stats(self, corners, imgs, masks):
+        """The first feed's overlap statistics per pair job: (ab (J, 2) int, c (J,) int64, sums (J, 6) float64) — sums are
+        {sum_a, sum_b, 0...} for the gain kinds and {B, G, R of a, B, G, R of b} for the channel kinds."""
+        ctx, n, d_imgs, d_masks, cs, _ = self._prepare(corners, imgs, masks)
+        kind = _lib.EXPOSURE_KINDS[self.kind]
+        ia, ma = (C.c_void_p * n)(*[a._h for a in d_imgs]), (C.c_void_p * n)(*[a._h for a in d_masks])
+        cp = cs.ctypes.data_as(C.POINTER(C.c_int))
+        nj = C.c_longlong(0)
+        _lib.check(ctx._lib.stx_exposure_stats(ctx.handle, kind, n, ia, ma, cp, self.block_size, C.byref(nj), None, None, None))
+        J = max(1, nj.value)
+        ab, c, s = np.zeros((J, 2), np.int32), np.zeros(J, np.int64), np.zeros((J, 6), np.float64)
+        _lib.check(ctx._lib.stx_exposure_stats(ctx.handle, kind, n, ia, ma, cp, self.block_size, C.byref(nj),
+                                               ab.ctypes.data_as(C.POINTER(C.c_int)), c.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                               s.ctypes.data_as(C.POINTER(C.c_double))))
+        k = nj.value
+        return ab[:k], c[:k], s[:k]
+
+
+def solve_gains(m, pairs, n_iij_iji, skip):
+    """Host only (no GPU): GainCompensator::singleFeed's assembly + cv::solve from given statistics.  pairs (P, 2) with i <= j,
+    n_iij_iji (P, 3) = N(i,j), I(i,j), I(j,i); skip (m,) bool.  -> gains (m,) float64."""
+    pairs = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+    vals = np.ascontiguousarray(np.asarray(n_iij_iji, np.float64).reshape(-1, 3))
+    sk = np.ascontiguousarray(np.asarray(skip, bool).astype(np.uint8).reshape(-1))
+    if sk.size != m or vals.shape[0] != pairs.shape[0]:
+        raise StitchingError("solve_gains: skip must hold m values and n_iij_iji one row per pair")
+    out = np.zeros(max(1, m), np.float64)
+    L = _lib.lib()
+    _lib.check(L.stx_exposure_solve(int(m), pairs.shape[0], pairs.ctypes.data_as(C.POINTER(C.c_int)),
+                                    vals.ctypes.data_as(C.POINTER(C.c_double)), sk.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                    out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out[:m]

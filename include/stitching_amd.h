@@ -301,6 +301,24 @@ int stx_exposure_stats(stx_ctx* ctx, int kind, int n, const stx_buf* const* imgs
  * other unit (gain 1).  out_gains: m values. */
 int stx_exposure_solve(int m, int npairs, const int* pairs_ij, const double* n_iij_iji, const unsigned char* skip,
                        double* out_gains);
+/* ---- seam finding: SeamFinder::find of the "voronoi" and "no" finders (stitching/seam_finder.py:33-35) -------------------------
+ * kind: STX_SEAM_VORONOI (VoronoiSeamFinder: PairwiseSeamFinder::run over the overlapping pairs (i, j), i < j, in order; a gap of
+ * 10 pixels around each overlap; dist1 < dist2 of the L1 distances (saturated at 8192) zeroes mask j there, anything else mask i) or
+ * STX_SEAM_NO (NoSeamFinder: the masks unchanged).  Parity: a restatement of OpenCV 4.x from recollection;
+ * tests/numpy_seams.py is the contract. */
+#define STX_SEAM_NO 0
+#define STX_SEAM_VORONOI 1
+#define STX_SEAM_GAP 10
+/* n u8x1 masks of images of sizes_wh = {w, h} per image at corners_xy; every mask must be its image's size.  masks_out[i]: new
+ * buffers (the inputs are never written).  The pairs run level by level (stx_seam_schedule), two launches per level.
+ * out_info (or NULL): {pairs, levels, device ms of the levels, device ms including the copy of the inputs} (HIP events). */
+int stx_seam_find(stx_ctx* ctx, int kind, int n, const int* sizes_wh, const int* corners_xy, const stx_buf* const* masks_in,
+                  stx_buf** masks_out, double out_info[4]);
+/* Host only (no context, no GPU): the overlapping pairs in PairwiseSeamFinder::run's order, out_pairs = {i, j, roi x, y, w, h} each,
+ * and the dependency level of each (0: depends on no earlier pair; else 1 + the highest level among the earlier pairs that share
+ * an image with it where one's roi meets the other's roi +- STX_SEAM_GAP clipped to that image).  Running the levels in order, pairs
+ * of one level in any order, gives the sequential result.  out_pairs NULL: only writes *inout_npairs. */
+int stx_seam_schedule(int n, const int* sizes_wh, const int* corners_xy, int* inout_npairs, int* out_pairs, int* out_levels);
 /* stx_resize_linear_exact <- stitching/images.py:122-124 cv.resize(img, size, interpolation=cv.INTER_LINEAR_EXACT) (u8x1 / u8x3:
  *                            the final-resolution resize of Images.resize, next row N3)
  * stx_seam_mask_resize    <- stitching/seam_finder.py:37-43 SeamFinder.resize: cv.dilate(seam_mask, None), cv.resize(...,

@@ -5,6 +5,8 @@ import os
 _device_resident = os.environ.get("STITCHING_AMD_DEVICE_RESIDENT", "0") not in ("0", "", "false", "False")
 EXPOSURE_ESTIMATORS = ("opencv", "device")
 _exposure_estimator = None  # None: STITCHING_AMD_EXPOSURE_ESTIMATOR decides at the first use
+SEAM_ESTIMATORS = ("opencv", "device")
+_seam_estimator = None  # None: STITCHING_AMD_SEAM_ESTIMATOR decides at the first use
 
 
 def set_device_resident(on=True):
@@ -119,3 +121,28 @@ def exposure_estimator():
     if _exposure_estimator is None:
         _exposure_estimator = _parse_exposure_estimator(os.environ.get("STITCHING_AMD_EXPOSURE_ESTIMATOR", "opencv") or "opencv")
     return _exposure_estimator
+
+
+def _parse_seam_estimator(mode):
+    if mode not in SEAM_ESTIMATORS:
+        from .stitching_error import StitchingError
+
+        raise StitchingError(f"unknown seam estimator {mode!r}: one of {list(SEAM_ESTIMATORS)}")
+    return mode
+
+
+def set_seam_estimator(mode):
+    """Who finds the seams of a SeamFinder built without estimator=: "opencv" (default: the cv.detail finder the reference builds, when
+    cv2 is importable) or "device" (stitching_amd.SeamEstimator in HIP for the "voronoi" and "no" finders; "dp_*" / "gc_*" keep the
+    cv.detail finder).  Process-wide; STITCHING_AMD_SEAM_ESTIMATOR sets the start-up value.  Returns the previous mode."""
+    global _seam_estimator
+    prev = seam_estimator()
+    _seam_estimator = _parse_seam_estimator(mode)
+    return prev
+
+
+def seam_estimator():
+    global _seam_estimator
+    if _seam_estimator is None:
+        _seam_estimator = _parse_seam_estimator(os.environ.get("STITCHING_AMD_SEAM_ESTIMATOR", "opencv") or "opencv")
+    return _seam_estimator

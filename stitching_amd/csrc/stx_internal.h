@@ -223,6 +223,12 @@ int stx_launch_exposure_stats(stx_ctx* ctx, const StxExpImg* d_imgs, const StxEx
 // one u8x3 image multiplied by per-block gains g (bpw blocks of bw x bh per row, 1 or 3 (g3) floats per block)
 struct StxExpBlockMul { uint8_t* img; long long stride; int w, h, bw, bh, bpw; const float* g; int g3; };
 int stx_launch_exposure_block_mul(stx_ctx* ctx, const StxExpBlockMul* d_tab, int n, int max_pixels);
+// seam finding (stx_seams.hip, stx_seams_host.cpp) ----------------------------------------------------------------------------------
+// a pair of one level: masks i (m1) and j (m2) with their strides and sizes, the window's top-left in each image (roi - gap - corner),
+// window ww x wh, roi rw x rh (at (gap, gap) of the window), off: the pair's u16 distances in the level's arena (mask i's wh x rw plane,
+// then mask j's)
+struct StxSeamPair { uint8_t* m1; uint8_t* m2; long long s1, s2, off; int w1, h1, w2, h2, ox1, oy1, ox2, oy2, ww, wh, rw, rh; };
+int stx_launch_seam_level(stx_ctx* ctx, const StxSeamPair* d_pairs, int np, int max_rows, int max_cols, uint16_t* d_arena, double algo_bytes);
 // cv::resize(INTER_LINEAR_EXACT) u8 (next rows N2 / N3); d_xt / d_yt: device tables of (offset, coeff1 | interior << 16)
 int stx_launch_resize_exact(stx_ctx* ctx, const stx_buf* src, stx_buf* dst, const int* d_xt, const int* d_yt, bool dilate,
                             const stx_buf* andmask);

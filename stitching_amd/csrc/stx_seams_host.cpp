@@ -1,0 +1,195 @@
+// stx_seams_host.cpp — host side of seam finding (SeamFinder::find for "voronoi" and "no"): PairwiseSeamFinder::run's pairs, their
+// dependency levels, the result buffers and the launches of stx_seams.hip.  tests/numpy_seams.py is the contract.
+#include <algorithm>
+#include <vector>
+
+#include "stx_internal.h"
+
+namespace {
+
+struct SeamPlanPair { int i, j, x, y, w, h, level; };
+
+struct Rect { int x0, y0, x1, y1; };
+bool meets(const Rect& a, const Rect& b) { return a.x0 < b.x1 && b.x0 < a.x1 && a.y0 < b.y1 && b.y0 < a.y1; }
+Rect clip(const Rect& a, const Rect& b) { return {std::max(a.x0, b.x0), std::max(a.y0, b.y0), std::min(a.x1, b.x1), std::min(a.y1, b.y1)}; }
+
+// run()'s pairs in order with their overlapRoi, and each pair's level: 0 without dependencies, else 1 + the highest level of the earlier
+// pairs it depends on.  q depends on an earlier p when they share an image k and, in k, the write region of one (its roi) meets the
+// read window of the other (roi +- gap, clipped to k).  Pairs of one level then touch disjoint pixels of every image, and running the
+// levels in order gives the sequential result.
+int seam_plan(int n, const int* sizes, const int* corners, std::vector<SeamPlanPair>& out, int* nlevels)
+{
+    if (n < 0 || (n > 0 && (!sizes || !corners))) return stx_fail(STX_ERR_INVALID, "bad argument");
+    for (int k = 0; k < n; k++)
+        if (sizes[2 * k] <= 0 || sizes[2 * k + 1] <= 0) return stx_fail(STX_ERR_INVALID, "image %d has no pixels", k);
+    auto rect = [&](int k) {
+        return Rect{corners[2 * k], corners[2 * k + 1], corners[2 * k] + sizes[2 * k], corners[2 * k + 1] + sizes[2 * k + 1]};
+    };
+    out.clear();
+    for (int i = 0; i + 1 < n; i++)
+        for (int j = i + 1; j < n; j++) {
+            const Rect r = clip(rect(i), rect(j));
+            if (r.x0 < r.x1 && r.y0 < r.y1) out.push_back({i, j, r.x0, r.y0, r.x1 - r.x0, r.y1 - r.y0, 0});
+        }
+    const int g = STX_SEAM_GAP;
+    int levels = out.empty() ? 0 : 1;
+    for (size_t q = 0; q < out.size(); q++) {
+        SeamPlanPair& Q = out[q];
+        const Rect wq{Q.x, Q.y, Q.x + Q.w, Q.y + Q.h}, rq{Q.x - g, Q.y - g, Q.x + Q.w + g, Q.y + Q.h + g};
+        for (size_t p = 0; p < q; p++) {
+            const SeamPlanPair& Pp = out[p];
+            if (Pp.level < Q.level) continue;  // cannot raise Q's level
+            const Rect wp{Pp.x, Pp.y, Pp.x + Pp.w, Pp.y + Pp.h}, rp{Pp.x - g, Pp.y - g, Pp.x + Pp.w + g, Pp.y + Pp.h + g};
+            const int shared[2] = {Q.i, Q.j};
+            for (int k : shared) {
+                if (k != Pp.i && k != Pp.j) continue;
+                const Rect img = rect(k);
+                if (meets(wp, clip(rq, img)) || meets(wq, clip(rp, img))) {
+                    Q.level = Pp.level + 1;
+                    break;
+                }
+            }
+        }
+        levels = std::max(levels, Q.level + 1);
+    }
+    *nlevels = levels;
+    return STX_OK;
+}
+
+struct SeamRun {
+    stx_ctx* ctx = nullptr;
+    StxSeamPair* d_pairs = nullptr;
+    uint16_t* d_arena = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    ~SeamRun()
+    {
+        if (!ctx) return;
+        hipStreamSynchronize(ctx->stream);
+        stx_dev_free(ctx, d_pairs);
+        stx_dev_free(ctx, d_arena);
+        for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
+    }
+};
+
+}  // namespace
+
+STX_EXPORT int stx_seam_schedule(int n, const int* sizes_wh, const int* corners_xy, int* inout_npairs, int* out_pairs, int* out_levels)
+{
+    if (!inout_npairs) return stx_fail(STX_ERR_INVALID, "inout_npairs is null");
+    std::vector<SeamPlanPair> plan;
+    int nlevels = 0;
+    STX_TRY(seam_plan(n, sizes_wh, corners_xy, plan, &nlevels));
+    const int np = (int)plan.size();
+    if (!out_pairs) { *inout_npairs = np; return STX_OK; }
+    if (*inout_npairs < np || !out_levels) return stx_fail(STX_ERR_INVALID, "output arrays hold %d pairs, %d needed", *inout_npairs, np);
+    for (int p = 0; p < np; p++) {
+        const SeamPlanPair& P = plan[p];
+        const int v[6] = {P.i, P.j, P.x, P.y, P.w, P.h};
+        for (int k = 0; k < 6; k++) out_pairs[6 * p + k] = v[k];
+        out_levels[p] = P.level;
+    }
+    *inout_npairs = np;
+    return STX_OK;
+}
+
+STX_EXPORT int stx_seam_find(stx_ctx* ctx, int kind, int n, const int* sizes_wh, const int* corners_xy, const stx_buf* const* masks_in,
+                             stx_buf** masks_out, double out_info[4])
+{
+    if (kind != STX_SEAM_NO && kind != STX_SEAM_VORONOI) return stx_fail(STX_ERR_INVALID, "unknown seam finder kind %d", kind);
+    if (!ctx) return stx_fail(STX_ERR_INVALID, "ctx is null");
+    if (n < 0 || (n > 0 && (!sizes_wh || !corners_xy || !masks_in || !masks_out))) return stx_fail(STX_ERR_INVALID, "bad argument");
+    for (int k = 0; k < n; k++) {
+        const stx_buf* m = masks_in[k];
+        if (!m) return stx_fail(STX_ERR_INVALID, "null mask %d", k);
+        if (m->elem != STX_U8 || m->c != 1) return stx_fail(STX_ERR_INVALID, "seam finding needs u8x1 masks (mask %d)", k);
+        if (m->w != sizes_wh[2 * k] || m->h != sizes_wh[2 * k + 1])
+            return stx_fail(STX_ERR_INVALID, "mask %d is %dx%d, its image %dx%d", k, m->w, m->h, sizes_wh[2 * k], sizes_wh[2 * k + 1]);
+        if (m->ctx != ctx) return stx_fail(STX_ERR_INVALID, "mask %d belongs to another context", k);
+    }
+    std::vector<SeamPlanPair> plan;
+    int nlevels = 0;
+    if (kind == STX_SEAM_VORONOI) STX_TRY(seam_plan(n, sizes_wh, corners_xy, plan, &nlevels));
+    if (out_info) { out_info[0] = (double)plan.size(); out_info[1] = nlevels; out_info[2] = 0.0; out_info[3] = 0.0; }
+    for (int k = 0; k < n; k++) masks_out[k] = nullptr;
+    if (n == 0) return STX_OK;
+    STX_TRY(stx_set_device(ctx));
+    SeamRun X;
+    X.ctx = ctx;
+    auto fail = [&](int rc) {
+        hipStreamSynchronize(ctx->stream);
+        for (int k = 0; k < n; k++) { if (masks_out[k]) stx_buf_release(masks_out[k]); masks_out[k] = nullptr; }
+        return rc;
+    };
+    if (out_info) {
+        for (hipEvent_t& e : X.ev)
+            if (hipEventCreate(&e) != hipSuccess) return fail(stx_fail(STX_ERR_HIP, "hipEventCreate failed"));
+        if (hipEventRecord(X.ev[0], ctx->stream) != hipSuccess) return fail(stx_fail(STX_ERR_HIP, "hipEventRecord failed"));
+    }
+    // the results: copies of the inputs (the caller's masks are never written)
+    for (int k = 0; k < n; k++) {
+        const stx_buf* m = masks_in[k];
+        int rc = stx_buf_new(ctx, m->w, m->h, 1, STX_U8, &masks_out[k]);
+        if (rc != STX_OK) return fail(rc);
+        masks_out[k]->mask_binary = m->mask_binary;  // zeroing keeps a 0 / 255 mask binary
+        if (hipMemcpy2DAsync(masks_out[k]->ptr, masks_out[k]->stride, m->ptr, m->stride, (size_t)m->w, m->h, hipMemcpyDeviceToDevice,
+                             ctx->stream) != hipSuccess)
+            return fail(stx_fail(STX_ERR_HIP, "hipMemcpy2DAsync of a seam mask failed"));
+    }
+    if (out_info && hipEventRecord(X.ev[1], ctx->stream) != hipSuccess) return fail(stx_fail(STX_ERR_HIP, "hipEventRecord failed"));
+    if (!plan.empty()) {
+        // pairs grouped by level (stable: run() order inside a level), arena offsets per level, one arena of the largest level
+        std::vector<int> order(plan.size());
+        for (size_t p = 0; p < plan.size(); p++) order[p] = (int)p;
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return plan[a].level < plan[b].level; });
+        std::vector<StxSeamPair> tab(plan.size());
+        std::vector<int> lstart(nlevels + 1, 0), lrows(nlevels, 0), lcols(nlevels, 0);
+        std::vector<long long> lsize(nlevels, 0);
+        std::vector<double> lbytes(nlevels, 0.0);
+        const int g = STX_SEAM_GAP;
+        for (size_t t = 0; t < order.size(); t++) {
+            const SeamPlanPair& P = plan[order[t]];
+            const stx_buf* a = masks_out[P.i];
+            const stx_buf* b = masks_out[P.j];
+            StxSeamPair& S = tab[t];
+            S.m1 = a->ptr; S.s1 = (long long)a->stride; S.w1 = a->w; S.h1 = a->h;
+            S.m2 = b->ptr; S.s2 = (long long)b->stride; S.w2 = b->w; S.h2 = b->h;
+            S.ox1 = P.x - g - corners_xy[2 * P.i]; S.oy1 = P.y - g - corners_xy[2 * P.i + 1];
+            S.ox2 = P.x - g - corners_xy[2 * P.j]; S.oy2 = P.y - g - corners_xy[2 * P.j + 1];
+            S.ww = P.w + 2 * g; S.wh = P.h + 2 * g; S.rw = P.w; S.rh = P.h;
+            // the roi (written unchecked by the column kernel) lies inside both images
+            if (S.ox1 + g < 0 || S.oy1 + g < 0 || S.ox1 + g + P.w > a->w || S.oy1 + g + P.h > a->h || S.ox2 + g < 0 || S.oy2 + g < 0 ||
+                S.ox2 + g + P.w > b->w || S.oy2 + g + P.h > b->h)
+                return fail(stx_fail(STX_ERR_INVALID, "internal: seam roi outside its images"));
+            S.off = lsize[P.level];
+            lsize[P.level] += 2ll * S.wh * S.rw;
+            lstart[P.level + 1]++;
+            lrows[P.level] = std::max(lrows[P.level], S.wh);
+            lcols[P.level] = std::max(lcols[P.level], S.rw);
+            lbytes[P.level] += 2.0 * S.ww * S.wh + 12.0 * S.wh * S.rw + (double)S.rw * S.rh;
+        }
+        for (int l = 0; l < nlevels; l++) lstart[l + 1] += lstart[l];
+        const long long arena = *std::max_element(lsize.begin(), lsize.end());
+        void* p = nullptr;
+        int rc = stx_dev_alloc(ctx, sizeof(StxSeamPair) * tab.size(), &p);
+        if (rc != STX_OK) return fail(rc);
+        X.d_pairs = (StxSeamPair*)p;
+        if ((rc = stx_dev_alloc(ctx, sizeof(uint16_t) * (size_t)arena, &p)) != STX_OK) return fail(rc);
+        X.d_arena = (uint16_t*)p;
+        if (hipMemcpyAsync(X.d_pairs, tab.data(), sizeof(StxSeamPair) * tab.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+            return fail(stx_fail(STX_ERR_HIP, "seam pair table upload failed"));
+        for (int l = 0; l < nlevels; l++)
+            if ((rc = stx_launch_seam_level(ctx, X.d_pairs + lstart[l], lstart[l + 1] - lstart[l], lrows[l], lcols[l], X.d_arena,
+                                            lbytes[l])) != STX_OK)
+                return fail(rc);
+    }
+    if (out_info && hipEventRecord(X.ev[2], ctx->stream) != hipSuccess) return fail(stx_fail(STX_ERR_HIP, "hipEventRecord failed"));
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(stx_fail(STX_ERR_HIP, "seam finding failed"));
+    if (out_info) {
+        float a = 0.f, b = 0.f;
+        if (hipEventElapsedTime(&a, X.ev[1], X.ev[2]) != hipSuccess || hipEventElapsedTime(&b, X.ev[0], X.ev[2]) != hipSuccess)
+            return fail(stx_fail(STX_ERR_HIP, "hipEventElapsedTime failed"));
+        out_info[2] = a;
+        out_info[3] = b;
+    }
+    return STX_OK;
+}

@@ -1,0 +1,92 @@
+"""Seam finding on the device: SeamFinder::find for the "voronoi" and "no" finders.
+
+`SeamEstimator` is duck-typed like the cv.detail finders the reference builds (stitching/seam_finder.py:14-35): `find(imgs, corners,
+masks)` on the low-resolution warped images returns the seam masks.  The images are read for their sizes only.  "voronoi" runs
+PairwiseSeamFinder::run's pairs level by level (host schedule: csrc/stx_seams_host.cpp), two HIP launches per level
+(csrc/stx_seams.hip); "no" returns copies of the masks.  The algorithm restates OpenCV 4.x from recollection; tests/numpy_seams.py is
+the contract and fidelity to real OpenCV is unpinned.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib, config
+from .device import DeviceImage, as_device, get_context
+from .stitching_error import StitchingError
+
+
+def _size(a, what, i):
+    """(w, h) and the array (numpy or DeviceImage), without a host copy of device images."""
+    if isinstance(a, DeviceImage):
+        return (a.width, a.height), a
+    if not isinstance(a, np.ndarray) and hasattr(a, "get"):
+        a = a.get()
+    a = np.asarray(a)
+    if a.ndim not in (2, 3):
+        raise StitchingError(f"{what} {i}: expected an HxW or HxWxC array, got shape {a.shape}")
+    return (a.shape[1], a.shape[0]), a
+
+
+def schedule(corners, sizes):
+    """Host only (no GPU): run()'s overlapping pairs and their dependency levels.  -> (pairs (P, 6) int32 rows i, j, x, y, w, h of the
+    roi; levels (P,) int32)."""
+    n = len(sizes)
+    cs = np.ascontiguousarray(np.asarray(corners, np.int32).reshape(n, 2))
+    ss = np.ascontiguousarray(np.asarray(sizes, np.int32).reshape(n, 2))
+    ip = C.POINTER(C.c_int)
+    L = _lib.lib()
+    count = C.c_int(0)
+    _lib.check(L.stx_seam_schedule(n, ss.ctypes.data_as(ip), cs.ctypes.data_as(ip), C.byref(count), None, None))
+    pairs = np.zeros((max(1, count.value), 6), np.int32)
+    levels = np.zeros(max(1, count.value), np.int32)
+    _lib.check(L.stx_seam_schedule(n, ss.ctypes.data_as(ip), cs.ctypes.data_as(ip), C.byref(count), pairs.ctypes.data_as(ip),
+                                   levels.ctypes.data_as(ip)))
+    return pairs[:count.value], levels[:count.value]
+
+
+class SeamEstimator:
+    """SeamFinder::find on the device.  kind: "voronoi" (VoronoiSeamFinder) | "no" (NoSeamFinder).  Construction needs no GPU."""
+
+    def __init__(self, kind):
+        if kind not in _lib.SEAM_KINDS:
+            raise StitchingError(f"unknown device seam finder {kind!r}: one of {sorted(_lib.SEAM_KINDS)}")
+        self.kind = kind
+        self.info = None  # of the last call: pairs, levels, device ms of the levels, device ms with the copy of the inputs
+
+    def find(self, imgs, corners, masks):
+        """Seam masks for images `imgs` (numpy arrays, cv.UMat-likes or DeviceImages: only their sizes are read) at `corners` with
+        u8 masks `masks` (never written).  Returns new masks: DeviceImages when any mask is a DeviceImage or config.device_resident(),
+        numpy arrays otherwise."""
+        imgs, masks, corners = list(imgs), list(masks), [tuple(int(v) for v in c) for c in corners]
+        if not (len(imgs) == len(masks) == len(corners)):
+            raise StitchingError("find needs as many images, corners and masks")
+        n = len(imgs)
+        if n == 0:
+            self.info = {"pairs": 0, "levels": 0, "device_ms": 0.0, "device_ms_with_copy": 0.0}
+            return []
+        sizes = []
+        for i in range(n):
+            wh, _ = _size(imgs[i], "image", i)
+            mwh, m = _size(masks[i], "mask", i)
+            if isinstance(m, np.ndarray) and (m.ndim != 2 or m.dtype != np.uint8):
+                raise StitchingError(f"mask {i}: seam finding needs u8 masks with one channel, got {m.dtype} of shape {m.shape}")
+            if mwh != wh:
+                raise StitchingError(f"mask {i} is {mwh[0]}x{mwh[1]}, its image {wh[0]}x{wh[1]}")
+            masks[i] = m
+            sizes.append(wh)
+        ctxs = {id(a.ctx): a.ctx for a in imgs + masks if isinstance(a, DeviceImage)}
+        if len(ctxs) > 1:
+            raise StitchingError("device images of more than one context")
+        ctx = next(iter(ctxs.values())) if ctxs else get_context()
+        resident = config.device_resident() or any(isinstance(m, DeviceImage) for m in masks)
+        d_masks = [as_device(m, ctx) for m in masks]
+        ss = np.ascontiguousarray(np.asarray(sizes, np.int32).reshape(n, 2))
+        cs = np.ascontiguousarray(np.asarray(corners, np.int32).reshape(n, 2))
+        ip = C.POINTER(C.c_int)
+        ma, outs = (C.c_void_p * n)(*[m._h for m in d_masks]), (C.c_void_p * n)()
+        info = np.zeros(4, np.float64)
+        _lib.check(ctx._lib.stx_seam_find(ctx.handle, _lib.SEAM_KINDS[self.kind], n, ss.ctypes.data_as(ip), cs.ctypes.data_as(ip), ma,
+                                          outs, info.ctypes.data_as(C.POINTER(C.c_double))))
+        self.info = {"pairs": int(info[0]), "levels": int(info[1]), "device_ms": float(info[2]), "device_ms_with_copy": float(info[3])}
+        res = [DeviceImage(ctx, C.c_void_p(outs[i])) for i in range(n)]
+        return res if resident else [r.numpy() for r in res]

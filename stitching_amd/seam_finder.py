@@ -1,7 +1,8 @@
 """SeamFinder.resize on the device and the INTER_LINEAR_EXACT resize behind it (row N3).
 
-The reference's SeamFinder (stitching/seam_finder.py:11-146) finds seams on ~0.1 Mpx images with OpenCV's graph-cut /
-dynamic-programming finders — sequential, tiny, out of scope — and then `resize`s every seam mask to the final
+The reference's SeamFinder (stitching/seam_finder.py:11-146) finds seams on ~0.1 Mpx images with OpenCV's finders — graph cut and
+dynamic programming stay OpenCV's; "voronoi" and "no" run on the device with config.set_seam_estimator("device")
+(seam_estimation.py) — and then `resize`s every seam mask to the final
 resolution: dilate, cv.resize(INTER_LINEAR_EXACT), AND with the final warped mask (`:37-43`).  That result is the
 mask `Blender.feed` receives (stitching/stitcher.py:124,127), so it sits directly in front of the hot path; here it
 is one fused kernel on device-resident masks.  `resize_linear_exact` is the same resize for images
@@ -12,7 +13,10 @@ import numpy as np
 
 from . import _lib, config
 from .device import DeviceImage, as_device, get_context
+from .seam_estimation import SeamEstimator
 from .stitching_error import StitchingError
+
+DEVICE_SEAM_FINDERS = ("voronoi", "no")  # the finders config.set_seam_estimator("device") runs as a SeamEstimator
 
 
 def resize_linear_exact(img, size, ctx=None, device_resident=None):
@@ -35,11 +39,17 @@ class SeamFinder:
 
     def __init__(self, finder=DEFAULT_SEAM_FINDER, estimator=None):
         """`estimator`: any object with find(imgs_float, corners, masks) -> seam masks; default: the cv.detail finder the
-        reference builds for this name (stitching/seam_finder.py:14-35) when cv2 is importable."""
+        reference builds for this name (stitching/seam_finder.py:14-35) when cv2 is importable, or with
+        config.set_seam_estimator("device") a stitching_amd.SeamEstimator for "voronoi" and "no"."""
         if finder not in self.SEAM_FINDER_CHOICES:
             raise StitchingError(f"unknown seam finder {finder!r}")
         self.finder_type = finder
-        self.finder = estimator if estimator is not None else self._cv_finder(finder)
+        if estimator is not None:
+            self.finder = estimator
+        elif config.seam_estimator() == "device" and finder in DEVICE_SEAM_FINDERS:
+            self.finder = SeamEstimator(finder)
+        else:
+            self.finder = self._cv_finder(finder)
 
     @staticmethod
     def _cv_finder(finder):
@@ -54,11 +64,16 @@ class SeamFinder:
         return cv.detail.SeamFinder_createDefault(cv.detail.SeamFinder_VORONOI_SEAM if finder == "voronoi" else cv.detail.SeamFinder_NO)
 
     def find(self, imgs, corners, masks):
-        """stitching/seam_finder.py:33-35: seam estimation on the ~0.1 Mpx images (graph cut / dynamic programming in
-        OpenCV: sequential, tiny, outside the MI355X hot path) — delegated; the masks it returns go to `resize`."""
+        """stitching/seam_finder.py:33-35: seam estimation on the ~0.1 Mpx images — delegated to the finder (graph cut / dynamic
+        programming stay OpenCV's; a SeamEstimator gets the images untouched); the masks it returns go to `resize`."""
         if self.finder is None:
+            if config.seam_estimator() == "device":
+                raise StitchingError(f"seam finder {self.finder_type!r} needs OpenCV, which is not importable here: the device seam "
+                                     f"estimator covers {' and '.join(repr(f) for f in DEVICE_SEAM_FINDERS)}")
             raise StitchingError("seam estimation needs OpenCV, which is not importable here: pass an estimator= object "
                                  "or give seam masks found elsewhere to SeamFinder.resize")
+        if isinstance(self.finder, SeamEstimator):  # reads the images' sizes only: device images stay on the device
+            return self.finder.find(list(imgs), list(corners), list(masks))
         host = lambda a: np.asarray(a.get() if hasattr(a, "get") else a)  # noqa: E731
         imgs_float = [host(img).astype(np.float32) for img in imgs]
         return self.finder.find(imgs_float, list(corners), [host(m) for m in masks])

@@ -319,6 +319,16 @@ int stx_seam_find(stx_ctx* ctx, int kind, int n, const int* sizes_wh, const int*
  * an image with it where one's roi meets the other's roi +- STX_SEAM_GAP clipped to that image).  Running the levels in order, pairs
  * of one level in any order, gives the sequential result.  out_pairs NULL: only writes *inout_npairs. */
 int stx_seam_schedule(int n, const int* sizes_wh, const int* corners_xy, int* inout_npairs, int* out_pairs, int* out_levels);
+/* ---- cropping: Cropper.estimate_largest_interior_rectangle (stitching/cropper.py:91-106) -----------------------------------------
+ * mask_u8x1: the panorama mask (views and pitched buffers allowed; nonzero means true), never copied to the host.
+ * out_contours = {foreground components (8-connected), holes (4-connected background components of the zero-framed mask that do
+ * not reach its frame)}: findContours' hierarchy is a single entry exactly when they are {1, 0}.  out_xywh: the largest rectangle of
+ * true cells, ties broken by smallest y, then smallest x, then largest w; {0, 0, 0, 0} for a mask without true cells.  The rectangle
+ * is computed whatever the counts are.  Exact integer arithmetic: the result does not depend on scheduling.  Parity: the reference's
+ * lir(grid, contour) returns the same area; which of several equal-area rectangles it picks is unpinned;
+ * tests/numpy_lir.py is the contract.  Six launches, one synchronisation at the end.  At most 2^31 - 2 pixels.
+ * out_info (or NULL): {device ms of the launches} (HIP events). */
+int stx_crop_lir(stx_ctx* ctx, const stx_buf* mask_u8x1, int out_xywh[4], int out_contours[2], double out_info[1]);
 /* stx_resize_linear_exact <- stitching/images.py:122-124 cv.resize(img, size, interpolation=cv.INTER_LINEAR_EXACT) (u8x1 / u8x3:
  *                            the final-resolution resize of Images.resize, next row N3)
  * stx_seam_mask_resize    <- stitching/seam_finder.py:37-43 SeamFinder.resize: cv.dilate(seam_mask, None), cv.resize(...,

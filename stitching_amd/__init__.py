@@ -6,6 +6,7 @@ from .blender import Blender
 from .camera import CameraParams
 from .config import (device_resident, exposure_estimator, pyrdown_mode, remap_mode, seam_estimator, set_device_resident,
                      set_exposure_estimator, set_pyrdown_mode, set_remap_mode, set_seam_estimator, set_trig_mode, trig_mode)
+from .cropper import Cropper, Rectangle
 from .device import Context, DeviceImage, as_device, device_count, get_context, pinned_empty, set_default_device
 from .exposure_error_compensator import ExposureErrorCompensator
 from .exposure_estimation import ExposureEstimator
@@ -17,7 +18,7 @@ from .timelapser import Timelapser
 from .warper import Warper
 
 __all__ = [
-    "Blender", "CameraParams", "Context", "DeviceImage", "ExposureErrorCompensator", "ExposureEstimator", "Images", "MegapixDownscaler", "MegapixScaler", "StitchingError", "StitchingWarning",
+    "Blender", "CameraParams", "Context", "Cropper", "Rectangle", "DeviceImage", "ExposureErrorCompensator", "ExposureEstimator", "Images", "MegapixDownscaler", "MegapixScaler", "StitchingError", "StitchingWarning",
     "SeamEstimator", "SeamFinder", "Timelapser", "Warper", "resize_linear_exact",
     "as_device", "device_count", "pinned_empty", "device_resident", "get_context", "set_default_device", "set_device_resident", "set_trig_mode", "trig_mode", "set_remap_mode", "remap_mode", "set_pyrdown_mode", "pyrdown_mode",
     "set_exposure_estimator", "exposure_estimator", "set_seam_estimator", "seam_estimator",

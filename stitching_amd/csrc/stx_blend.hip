@@ -1717,7 +1717,7 @@ struct Seam1K {
 };
 struct Seam1BatchK { Seam1K k[SEAM_BATCH]; int pitch, raw_bytes; };
 
-// interpolationLinear<ufixedpoint16>::getCoeffs for destination index v: (offset, coeff1 | interior << 16) — stx_api.cpp linear_exact_table
+// interpolationLinear<ufixedpoint16>::getCoeffs for destination index v: (offset, coeff1 | interior << 16) — stx_resize_host.cpp linear_exact_table
 STX_DEV int2 seam1_coeff(int v, double scale, int src_n)
 {
     const double fval = scale * ((double)v + 0.5) - 0.5;
@@ -1885,14 +1885,13 @@ int stx_launch_resize_exact(stx_ctx* ctx, const stx_buf* src, stx_buf* dst, cons
     const bool fast = dilate && andmask && ((uintptr_t)dst->ptr & 3) == 0 && (dst->stride & 3) == 0 && ((uintptr_t)andmask->ptr & 3) == 0 &&
                       (andmask->stride & 3) == 0 && (size_t)((dst->w + 3) & ~3) <= andmask->stride && (size_t)((dst->w + 3) & ~3) <= dst->stride;
     if (fast) {
-        void* tmp = nullptr;
+        StxDevBlock tmp;  // back to the allocator behind the second launch: stream-ordered reuse
         const size_t tstride = ((size_t)src->w + 63) & ~(size_t)63;
         STX_TRY(stx_dev_alloc(ctx, tstride * src->h, &tmp));
         hipLaunchKernelGGL(dilate3x3_kernel, dim3((src->w + 63) / 64, (src->h + 3) / 4), dim3(256), 0, ctx->stream, src->ptr,
-                           (long long)src->stride, src->w, src->h, (uint8_t*)tmp, (long long)tstride);
-        K.src = (const uint8_t*)tmp; K.sstride = (long long)tstride;
+                           (long long)src->stride, src->w, src->h, (uint8_t*)tmp.get(), (long long)tstride);
+        K.src = (const uint8_t*)tmp.get(); K.sstride = (long long)tstride;
         hipLaunchKernelGGL(seam_resize4_kernel, dim3((dst->w + 255) / 256, (dst->h + 4 * SEAM_ROWS - 1) / (4 * SEAM_ROWS)), dim3(256), 0, ctx->stream, K);
-        stx_dev_free(ctx, tmp);  // stream-ordered reuse
     } else if (dilate) hipLaunchKernelGGL((resize_exact_kernel<1, true>), grid, dim3(256), 0, ctx->stream, K);
     else if (src->c == 1) hipLaunchKernelGGL((resize_exact_kernel<1, false>), grid, dim3(256), 0, ctx->stream, K);
     else if (src->c == 3) hipLaunchKernelGGL((resize_exact_kernel<3, false>), grid, dim3(256), 0, ctx->stream, K);

@@ -2475,12 +2475,12 @@ bool stx_fast_mb_level(stx_ctx* ctx, const MbLevelK& K)
         const size_t seg_cap = (size_t)((KT.tiles.tiles_x + STX_DEFER_SEGS - 1) / STX_DEFER_SEGS) * (size_t)KT.tiles.tiles_y * (unsigned)LV_THREADS;
         const size_t counters = (size_t)STX_DEFER_SEGS * 128;
         KT.defer_segs = segs;
-        void* q = nullptr;
+        StxDevBlock q;
         if (stx_dev_alloc(ctx, counters + seg_cap * (size_t)segs * sizeof(unsigned long long), &q) != STX_OK) return false;
-        KT.defer_count = reinterpret_cast<unsigned*>(q);
-        KT.defer_list = reinterpret_cast<unsigned long long*>(reinterpret_cast<uint8_t*>(q) + counters);
+        KT.defer_count = reinterpret_cast<unsigned*>(q.get());
+        KT.defer_list = reinterpret_cast<unsigned long long*>(reinterpret_cast<uint8_t*>(q.get()) + counters);
         KT.defer_cap = (unsigned)seg_cap;
-        hipMemsetAsync(q, 0, counters, st);
+        hipMemsetAsync(q.get(), 0, counters, st);
         hipLaunchKernelGGL((mb_level0_pk_kernel<false, true>), grid, dim3(LV_THREADS), 0, st, KT);
         {
             StxProfScope prof2(ctx, "mb_level0_deferred", 0.0);  // inside the caller's "mb_level0" bracket: that one times both launches
@@ -2490,13 +2490,12 @@ bool stx_fast_mb_level(stx_ctx* ctx, const MbLevelK& K)
         if (stats) {
             std::vector<unsigned> hc(counters / 4);
             hipStreamSynchronize(st);
-            hipMemcpy(hc.data(), q, counters, hipMemcpyDeviceToHost);
+            hipMemcpy(hc.data(), q.get(), counters, hipMemcpyDeviceToHost);
             unsigned long long tot = 0; unsigned mx = 0;
             for (int sgi = 0; sgi < segs; sgi++) { tot += hc[32 * sgi]; mx = std::max(mx, hc[32 * sgi]); }
             fprintf(stderr, "[stitching_amd] level-0 deferral: %llu of %llu patches queued (%d segments, fullest %u of %zu)\n", tot,
                     (unsigned long long)KT.tiles.tiles_x * KT.tiles.tiles_y * (unsigned long long)LV_THREADS, segs, mx, seg_cap);
         }
-        stx_dev_free(ctx, q);
     } else if (K.emit) {
         if (K.level == 0) hipLaunchKernelGGL((mb_level_fast_kernel<true, false, true, false>), grid, dim3(LV_THREADS), 0, st, KT);
         else if (K.all_u8) hipLaunchKernelGGL((mb_level_fast_kernel<false, false, true, true>), grid, dim3(LV_THREADS), 0, st, KT);

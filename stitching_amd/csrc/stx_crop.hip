@@ -291,13 +291,13 @@ __global__ __launch_bounds__(CROP_WG) void crop_reduce_kernel(const CropBest* be
 
 struct CropRun {
     stx_ctx* ctx = nullptr;
-    void* blocks[4] = {nullptr, nullptr, nullptr, nullptr};
+    StxDevBlock blocks[4];
     hipEvent_t ev[2] = {nullptr, nullptr};
     ~CropRun()
     {
         if (!ctx) return;
         hipStreamSynchronize(ctx->stream);
-        for (void* p : blocks) stx_dev_free(ctx, p);
+        for (StxDevBlock& p : blocks) p.reset();  // behind the synchronisation, in the order they were taken
         for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
     }
 };
@@ -320,16 +320,16 @@ STX_EXPORT int stx_crop_lir(stx_ctx* ctx, const stx_buf* mask, int out_xywh[4], 
     const long long N = (long long)W * H;
     const int grid = std::min(H, CROP_ROWS_GRID);
     const bool in_lds = W <= CROP_LDS_MAX_W;
-    void** lab = &X.blocks[0];
-    void** scratch = &X.blocks[1];
-    void** best = &X.blocks[2];
-    void** res = &X.blocks[3];
+    StxDevBlock* lab = &X.blocks[0];
+    StxDevBlock* scratch = &X.blocks[1];
+    StxDevBlock* best = &X.blocks[2];
+    StxDevBlock* res = &X.blocks[3];
     STX_TRY(stx_dev_alloc(ctx, sizeof(int) * (size_t)(N + 1), lab));
     STX_TRY(stx_dev_alloc(ctx, in_lds ? 4 : sizeof(int) * 2 * (size_t)W * grid, scratch));
     STX_TRY(stx_dev_alloc(ctx, sizeof(CropBest) * (size_t)H, best));
     STX_TRY(stx_dev_alloc(ctx, sizeof(int) * 8, res));
-    int* d_lab = (int*)*lab;
-    int* d_res = (int*)*res;
+    int* d_lab = (int*)lab->get();
+    int* d_res = (int*)res->get();
     if (out_info) {
         for (hipEvent_t& e : X.ev) STX_HIP(hipEventCreate(&e));
         STX_HIP(hipEventRecord(X.ev[0], ctx->stream));
@@ -360,14 +360,14 @@ STX_EXPORT int stx_crop_lir(stx_ctx* ctx, const stx_buf* mask, int out_xywh[4], 
         STX_TRY(crop_check_launch("crop_cols"));
     }
     {
-        CropRowsK K{d_v, W, H, (int*)*scratch, (CropBest*)*best};
+        CropRowsK K{d_v, W, H, (int*)scratch->get(), (CropBest*)best->get()};
         StxProfScope prof(ctx, "crop_rows", (double)N * 4);
         hipLaunchKernelGGL(crop_rows_kernel, dim3(grid), dim3(CROP_WG), in_lds ? sizeof(int) * 3 * (size_t)W : 0, ctx->stream, K);
         STX_TRY(crop_check_launch("crop_rows"));
     }
     {
         StxProfScope prof(ctx, "crop_reduce", (double)H * sizeof(CropBest));
-        hipLaunchKernelGGL(crop_reduce_kernel, dim3(1), dim3(CROP_WG), 0, ctx->stream, (const CropBest*)*best, H, d_res);
+        hipLaunchKernelGGL(crop_reduce_kernel, dim3(1), dim3(CROP_WG), 0, ctx->stream, (const CropBest*)best->get(), H, d_res);
         STX_TRY(crop_check_launch("crop_reduce"));
     }
     if (out_info) STX_HIP(hipEventRecord(X.ev[1], ctx->stream));

@@ -279,27 +279,27 @@ int exp_sqrt_table(stx_ctx* ctx)
     if (ctx->exp_sqrt) return STX_OK;
     std::vector<double> t(EXP_SQRT_N);
     for (int k = 0; k < EXP_SQRT_N; k++) t[k] = std::sqrt((double)k);
-    void* d = nullptr;
+    StxDevBlock d;
     STX_TRY(stx_dev_alloc(ctx, t.size() * sizeof(double), &d));
-    STX_HIP(hipMemcpyAsync(d, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    STX_HIP(hipMemcpyAsync(d.get(), t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     STX_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->exp_sqrt = (double*)d;
+    ctx->exp_sqrt = (double*)d.release();  // the context's from here
     return STX_OK;
 }
 
-// device side of the feeds: the job table once, the statistics of one feed per call
+// device side of the feeds: the job table once, the statistics of one feed per call; between feeds the multiplied images and their gain tables
 struct ExpRun {
     stx_ctx* ctx = nullptr;
-    StxExpImg* d_imgs = nullptr;
-    StxExpJob* d_jobs = nullptr;
-    long long* d_oi = nullptr;
-    double* d_od = nullptr;
+    std::vector<StxBufRef> scratch;  // the images multiplied between feeds (the caller's are never written)
+    StxDevBlock d_bg, d_bt;          // float gains per block, StxExpBlockMul per image
+    StxDevBlock d_imgs, d_jobs, d_oi, d_od;
     hipEvent_t ev[2] = {nullptr, nullptr};
     ~ExpRun()
     {
         if (!ctx) return;
         hipStreamSynchronize(ctx->stream);
-        stx_dev_free(ctx, d_imgs); stx_dev_free(ctx, d_jobs); stx_dev_free(ctx, d_oi); stx_dev_free(ctx, d_od);
+        scratch.clear();  // everything goes back behind the synchronisation, in this order
+        for (StxDevBlock* p : {&d_bg, &d_bt, &d_imgs, &d_jobs, &d_oi, &d_od}) p->reset();
         for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
     }
 };
@@ -313,25 +313,25 @@ int exp_stats(ExpRun& X, const ExpPlan& P, const stx_buf* const* imgs, const stx
     od.assign(2 * (size_t)nj, 0.0);
     if (nj == 0) return STX_OK;
     if (!X.d_jobs) {
-        void* p;
-        STX_TRY(stx_dev_alloc(ctx, sizeof(StxExpImg) * P.n, &p)); X.d_imgs = (StxExpImg*)p;
-        STX_TRY(stx_dev_alloc(ctx, sizeof(StxExpJob) * nj, &p)); X.d_jobs = (StxExpJob*)p;
-        STX_TRY(stx_dev_alloc(ctx, sizeof(long long) * 7 * nj, &p)); X.d_oi = (long long*)p;
-        STX_TRY(stx_dev_alloc(ctx, sizeof(double) * 2 * nj, &p)); X.d_od = (double*)p;
-        STX_HIP(hipMemcpyAsync(X.d_jobs, P.jobs.data(), sizeof(StxExpJob) * nj, hipMemcpyHostToDevice, ctx->stream));
+        STX_TRY(stx_dev_alloc(ctx, sizeof(StxExpImg) * P.n, &X.d_imgs));
+        STX_TRY(stx_dev_alloc(ctx, sizeof(StxExpJob) * nj, &X.d_jobs));
+        STX_TRY(stx_dev_alloc(ctx, sizeof(long long) * 7 * nj, &X.d_oi));
+        STX_TRY(stx_dev_alloc(ctx, sizeof(double) * 2 * nj, &X.d_od));
+        STX_HIP(hipMemcpyAsync(X.d_jobs.get(), P.jobs.data(), sizeof(StxExpJob) * nj, hipMemcpyHostToDevice, ctx->stream));
     }
     std::vector<StxExpImg> tab(P.n);
     double bytes = 0.0;
     for (int i = 0; i < P.n; i++) tab[i] = {imgs[i]->ptr, (long long)imgs[i]->stride, masks[i]->ptr, (long long)masks[i]->stride};
     for (const StxExpJob& J : P.jobs) bytes += 8.0 * J.w * J.h;
-    STX_HIP(hipMemcpyAsync(X.d_imgs, tab.data(), sizeof(StxExpImg) * P.n, hipMemcpyHostToDevice, ctx->stream));
+    STX_HIP(hipMemcpyAsync(X.d_imgs.get(), tab.data(), sizeof(StxExpImg) * P.n, hipMemcpyHostToDevice, ctx->stream));
     const int mode = kind_channels(P.kind) ? STX_EXP_INT : (P.kind == STX_EXPOSURE_GAIN_BLOCKS ? STX_EXP_ORDERED : STX_EXP_TREE);
     if (ms && !X.ev[0]) { STX_HIP(hipEventCreate(&X.ev[0])); STX_HIP(hipEventCreate(&X.ev[1])); }
     if (ms) STX_HIP(hipEventRecord(X.ev[0], ctx->stream));
-    STX_TRY(stx_launch_exposure_stats(ctx, X.d_imgs, X.d_jobs, nj, mode, ctx->exp_sqrt, X.d_oi, X.d_od, bytes));
+    STX_TRY(stx_launch_exposure_stats(ctx, (const StxExpImg*)X.d_imgs.get(), (const StxExpJob*)X.d_jobs.get(), nj, mode, ctx->exp_sqrt,
+                                      (long long*)X.d_oi.get(), (double*)X.d_od.get(), bytes));
     if (ms) STX_HIP(hipEventRecord(X.ev[1], ctx->stream));
-    STX_HIP(hipMemcpyAsync(oi.data(), X.d_oi, sizeof(long long) * 7 * nj, hipMemcpyDeviceToHost, ctx->stream));
-    STX_HIP(hipMemcpyAsync(od.data(), X.d_od, sizeof(double) * 2 * nj, hipMemcpyDeviceToHost, ctx->stream));
+    STX_HIP(hipMemcpyAsync(oi.data(), X.d_oi.get(), sizeof(long long) * 7 * nj, hipMemcpyDeviceToHost, ctx->stream));
+    STX_HIP(hipMemcpyAsync(od.data(), X.d_od.get(), sizeof(double) * 2 * nj, hipMemcpyDeviceToHost, ctx->stream));
     STX_HIP(hipStreamSynchronize(ctx->stream));
     if (ms) {
         float e = 0.f;
@@ -412,42 +412,31 @@ STX_EXPORT int stx_exposure_feed(stx_ctx* ctx, int kind, int n, const stx_buf* c
     const int m = P.units, planes = kind_channels(kind) ? 3 : 1;
     const bool blocks = kind_blocks(kind);
     std::vector<double> acc((size_t)planes * m, 1.0), g((size_t)planes * m, 1.0);
-    std::vector<stx_buf*> scratch;  // the images multiplied between feeds (the caller's are never written)
     std::vector<const stx_buf*> cur(imgs, imgs + n);
     ExpRun X;
     X.ctx = ctx;
-    float* d_bg = nullptr;
-    StxExpBlockMul* d_bt = nullptr;
-    auto cleanup = [&]() {
-        hipStreamSynchronize(ctx->stream);
-        for (stx_buf* s : scratch) stx_buf_release(s);
-        stx_dev_free(ctx, d_bg);
-        stx_dev_free(ctx, d_bt);
-    };
+    std::vector<StxBufRef>& scratch = X.scratch;
     double stats_ms = 0.0, host_ms = 0.0;
     std::vector<long long> oi;
     std::vector<double> od;
-    int rc = STX_OK;
-    for (int feed = 0; feed < nr_feeds && rc == STX_OK; feed++) {
+    for (int feed = 0; feed < nr_feeds; feed++) {
         if (feed > 0) {
             if (scratch.empty()) {
-                for (int i = 0; i < n && rc == STX_OK; i++) {
-                    stx_buf* s = nullptr;
-                    rc = stx_buf_new(ctx, imgs[i]->w, imgs[i]->h, 3, STX_U8, &s);
-                    if (rc != STX_OK) break;
-                    scratch.push_back(s);
+                for (int i = 0; i < n; i++) {
+                    scratch.emplace_back();
+                    StxBufRef& s = scratch.back();
+                    STX_TRY(stx_buf_new(ctx, imgs[i]->w, imgs[i]->h, 3, STX_U8, &s));
                     if (hipMemcpy2DAsync(s->ptr, s->stride, imgs[i]->ptr, imgs[i]->stride, 3 * (size_t)imgs[i]->w, imgs[i]->h,
                                          hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
-                        rc = stx_fail(STX_ERR_HIP, "hipMemcpy2DAsync of an exposure scratch image failed");
-                    cur[i] = s;
+                        return stx_fail(STX_ERR_HIP, "hipMemcpy2DAsync of an exposure scratch image failed");
+                    cur[i] = s.get();
                 }
-                if (rc != STX_OK) break;
             }
             if (!blocks) {  // one gain (BGR triple) per image: cv::multiply as GainCompensator::apply
-                for (int i = 0; i < n && rc == STX_OK; i++) {
+                for (int i = 0; i < n; i++) {
                     float g3[3];
                     for (int c = 0; c < 3; c++) g3[c] = (float)g[(size_t)(planes == 3 ? c : 0) * m + i];
-                    rc = stx_launch_gain_apply(ctx, scratch[i], g3);
+                    STX_TRY(stx_launch_gain_apply(ctx, scratch[i].get(), g3));
                 }
             } else {
                 std::vector<float> hg((size_t)m * planes);
@@ -461,34 +450,29 @@ STX_EXPORT int stx_exposure_feed(stx_ctx* ctx, int kind, int n, const stx_buf* c
                               nullptr, planes == 3};
                     maxpx = std::max(maxpx, scratch[i]->w * scratch[i]->h);
                 }
-                void* p = nullptr;
-                if (!d_bg) {
-                    if ((rc = stx_dev_alloc(ctx, hg.size() * sizeof(float), &p)) != STX_OK) break;
-                    d_bg = (float*)p;
-                    if ((rc = stx_dev_alloc(ctx, tab.size() * sizeof(StxExpBlockMul), &p)) != STX_OK) break;
-                    d_bt = (StxExpBlockMul*)p;
+                if (!X.d_bg) {
+                    STX_TRY(stx_dev_alloc(ctx, hg.size() * sizeof(float), &X.d_bg));
+                    STX_TRY(stx_dev_alloc(ctx, tab.size() * sizeof(StxExpBlockMul), &X.d_bt));
                 }
+                float* const d_bg = (float*)X.d_bg.get();
+                StxExpBlockMul* const d_bt = (StxExpBlockMul*)X.d_bt.get();
                 for (int i = 0; i < n; i++) tab[i].g = d_bg + (size_t)P.grid[i].first * planes;
                 hipStreamSynchronize(ctx->stream);  // the previous feed's tables may still be read
                 if (hipMemcpyAsync(d_bg, hg.data(), hg.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-                    hipMemcpyAsync(d_bt, tab.data(), tab.size() * sizeof(StxExpBlockMul), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-                    rc = stx_fail(STX_ERR_HIP, "exposure gain table upload failed");
-                    break;
-                }
-                rc = stx_launch_exposure_block_mul(ctx, d_bt, n, maxpx);
-                if (rc == STX_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = stx_fail(STX_ERR_HIP, "exposure block multiply failed");
+                    hipMemcpyAsync(d_bt, tab.data(), tab.size() * sizeof(StxExpBlockMul), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+                    return stx_fail(STX_ERR_HIP, "exposure gain table upload failed");
+                STX_TRY(stx_launch_exposure_block_mul(ctx, d_bt, n, maxpx));
+                if (hipStreamSynchronize(ctx->stream) != hipSuccess) return stx_fail(STX_ERR_HIP, "exposure block multiply failed");
             }
-            if (rc != STX_OK) break;
         }
-        rc = exp_stats(X, P, cur.data(), masks, oi, od, out_info ? &stats_ms : nullptr);
-        if (rc != STX_OK) break;
+        STX_TRY(exp_stats(X, P, cur.data(), masks, oi, od, out_info ? &stats_ms : nullptr));
         const auto t0 = std::chrono::steady_clock::now();
         const int nj = (int)P.jobs.size();
         std::vector<char> skip(m, 1);
         for (int j = 0; j < nj; j++)
             if (oi[7 * (size_t)j] > 0 && P.ab[2 * j] != P.ab[2 * j + 1]) skip[P.ab[2 * j]] = skip[P.ab[2 * j + 1]] = 0;
         std::vector<PairStat> pairs(nj);
-        for (int c = 0; c < planes && rc == STX_OK; c++) {
+        for (int c = 0; c < planes; c++) {
             for (int j = 0; j < nj; j++) {
                 const long long cnt = oi[7 * (size_t)j];
                 const double nn = (double)std::max(1LL, cnt);
@@ -499,12 +483,11 @@ STX_EXPORT int stx_exposure_feed(stx_ctx* ctx, int kind, int n, const stx_buf* c
                 }
                 pairs[j] = {P.ab[2 * j], P.ab[2 * j + 1], nn, cnt > 0 ? sa / nn : 0.0, cnt > 0 ? sb / nn : 0.0};
             }
-            rc = exp_solve(m, pairs, skip, g.data() + (size_t)c * m);
+            STX_TRY(exp_solve(m, pairs, skip, g.data() + (size_t)c * m));
         }
         for (size_t k = 0; k < acc.size(); k++) acc[k] = acc[k] * g[k];
         host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
-    if (rc != STX_OK) { cleanup(); return rc; }
     const auto t0 = std::chrono::steady_clock::now();
     double* o = out_gains;
     for (int i = 0; i < n; i++) {
@@ -522,6 +505,5 @@ STX_EXPORT int stx_exposure_feed(stx_ctx* ctx, int kind, int n, const stx_buf* c
     }
     host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (out_info) { out_info[2] = stats_ms; out_info[3] = host_ms; }
-    cleanup();
     return STX_OK;
 }

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -95,6 +96,20 @@ int stx_dev_alloc(stx_ctx* ctx, size_t bytes, void** out);
 int stx_stage_upload(stx_ctx* ctx, void* d, const void* h, size_t bytes);
 void stx_dev_free(stx_ctx* ctx, void* p);
 int stx_set_device(stx_ctx* ctx);
+// owner of one allocator block: whatever leaves the scope early (STX_TRY / STX_HIP) gives it back.  reset() where the last launch that
+// uses a scratch block has been queued (stream-ordered reuse: the next stx_dev_alloc may hand it out again), release() to pass it on.
+struct StxDevFree { stx_ctx* ctx; void operator()(void* p) const { stx_dev_free(ctx, p); } };
+using StxDevBlock = std::unique_ptr<void, StxDevFree>;
+inline int stx_dev_alloc(stx_ctx* ctx, size_t bytes, StxDevBlock* out)
+{
+    void* p = nullptr;
+    STX_TRY(stx_dev_alloc(ctx, bytes, &p));
+    *out = StxDevBlock(p, StxDevFree{ctx});
+    return STX_OK;
+}
+// small host array -> a fresh block through the context's pinned ring (asynchronous)
+int upload_small(stx_ctx* ctx, const void* h, size_t bytes, StxDevBlock* d_out);
+size_t align_up(size_t v, size_t a);
 
 // profiling bracket around one kernel launch
 struct StxProfScope {
@@ -131,6 +146,28 @@ inline int stx_elem_bytes(int elem) { return elem == STX_U8 ? 1 : (elem == STX_S
 int stx_buf_new(stx_ctx* ctx, int w, int h, int c, int elem, stx_buf** out);
 void stx_buf_retain(stx_buf* b);
 void stx_buf_release(stx_buf* b);
+// owner of one reference to an image: dropped at scope exit, handed to the caller with release()
+struct StxBufRelease { void operator()(stx_buf* b) const { stx_buf_release(b); } };
+using StxBufRef = std::unique_ptr<stx_buf, StxBufRelease>;
+inline int stx_buf_new(stx_ctx* ctx, int w, int h, int c, int elem, StxBufRef* out)
+{
+    stx_buf* b = nullptr;
+    STX_TRY(stx_buf_new(ctx, w, h, c, elem, &b));
+    out->reset(b);
+    return STX_OK;
+}
+// the raw pointers of a vector of handles, for the launchers' argument arrays
+inline std::vector<stx_buf*> stx_buf_ptrs(const std::vector<StxBufRef>& v)
+{
+    std::vector<stx_buf*> p;
+    for (const StxBufRef& b : v) p.push_back(b.get());
+    return p;
+}
+
+// process-wide arithmetic modes (stx_modes.cpp): the value now, read from the environment on first use ------------------------------
+int trig_mode_now();     // STX_TRIG_*
+int remap_mode_now();    // STX_REMAP_*
+int pyrdown_now();       // STX_PYRDOWN_* | lanes << 8
 
 // ---------------------------------------------------------------------------------------------
 // projector (host side of ProjectorBase::setCameraParams)
@@ -206,6 +243,7 @@ int stx_launch_mb_coarse(stx_ctx* ctx, const MbLevelK& K_level_Bm2, double algo_
 
 // pointwise exposure gain (next row N1) --------------------------------------------------------------
 int stx_launch_gain_apply(stx_ctx* ctx, stx_buf* img, const float g[3]);
+int block_gain_check(stx_ctx* ctx, const stx_buf* img, const stx_buf* gain_map);  // img may be null: the map alone
 int stx_launch_block_gain(stx_ctx* ctx, stx_buf* img, const stx_buf* gmap, const int* d_xt, const int* d_yt);
 int stx_launch_block_gain_batch(stx_ctx* ctx, int n, stx_buf* const* imgs, const stx_buf* const* gmaps, const int* full_wh_xy0,
                                 float* const* Hs, void* const* yts, const int* fast);
@@ -271,5 +309,30 @@ struct NoGatherK {
 };
 int stx_launch_no_gather(stx_ctx* ctx, const NoGatherK& K, double algo_bytes);
 
-// simple blenders --------------------------------------------------------------------------------
-
+// blender state (stx_blend_host.cpp; the strip sharding of stx_strips_host.cpp reads its geometry) ---------------------------------
+struct stx_blender {
+    stx_ctx* ctx = nullptr;
+    int kind = 0, num_bands = 0;
+    float sharpness = 0.02f;
+    int rx = 0, ry = 0, rw = 0, rh = 0;  // dst_roi_ (padded for multiband)
+    int fw = 0, fh = 0;                  // dst_roi_final_ size
+    bool finished = false;
+    // multiband (deferred gather)
+    std::vector<StxMbImage> images;   // kept sorted by .order (the global feed order)
+    std::vector<char> built;          // pyramid of images[i] exists (kind 0)
+    std::vector<stx_buf*> held;
+    std::vector<void*> pyr_allocs;
+    StxMbImage* d_all = nullptr;      // device copy of `images` as the pyramid pass uploaded it, while it still equals `images` (else null)
+    int band_x0 = 0, band_x1 = 0;     // columns of the final roi this blender produces (sharded blending)
+    int next_order = 0;
+    int pyr_mode = 0;                 // STX_PYRDOWN_* | lanes << 8, captured at stx_blend_create: one summation order per panorama
+                                      // whatever stx_set_pyrdown_mode is called with between feed() and blend()
+    // no: deferred gather over the fed images (stx_launch_no_gather)
+    std::vector<NoImg> no_images;
+    // feather: deferred gather as well (stx_launch_feather_weights / _gather)
+    std::vector<FeatherImg> feather_images;
+};
+// MultiBandBlender::feed geometry: the feed rectangle (tl_new .. br_new) relative to the padded roi
+void mb_feed_rect(const stx_blender* b, int w, int h, int tlx, int tly, int* fx, int* fy, int* fw, int* fh);
+// level-0 column range [sx0, sx1) of the contribution an image fed at [fx, fx + fw) owes the owner of the columns [bx0, bx1)
+bool mb_contrib_range(const stx_blender* b, int fx, int fw, int bx0, int bx1, int* sx0, int* sx1);

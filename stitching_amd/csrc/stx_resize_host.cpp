@@ -1,0 +1,312 @@
+// stx_resize_host.cpp — host side of the pointwise passes between warp and feed: exposure gains (one per image, block maps) and
+// cv::resize(INTER_LINEAR_EXACT) of images and seam masks.  Compiled with -ffp-contract=off: the coefficient tables restate OpenCV's
+// baseline (non-FMA) evaluation order.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "stx_internal.h"
+
+// "next" rows: exposure gain between warp and feed (N1)
+STX_EXPORT int stx_gain_apply(stx_ctx* ctx, stx_buf* img, const float gains_bgr[3])
+{
+    if (!ctx || !img || !gains_bgr) return stx_fail(STX_ERR_INVALID, "null argument");
+    if (img->elem != STX_U8 || img->c != 3) return stx_fail(STX_ERR_INVALID, "gain apply needs a u8x3 image");
+    if (img->ctx != ctx) return stx_fail(STX_ERR_INVALID, "image belongs to another context");
+    STX_TRY(stx_set_device(ctx));
+    return stx_launch_gain_apply(ctx, img, gains_bgr);
+}
+
+// interpolationLinear<ufixedpoint16>::getCoeffs of cv::resize(INTER_LINEAR_EXACT) [OCV-MEM]: all in double precision
+// (softdouble upstream = IEEE double; this file is compiled with -ffp-contract=off)
+static void linear_exact_table(int src_n, int dst_n, std::vector<int>& t)
+{
+    t.resize(2 * (size_t)dst_n);
+    const double inv_scale = (double)dst_n / (double)src_n;
+    const double scale = 1.0 / inv_scale;
+    for (int v = 0; v < dst_n; v++) {
+        const double fval = scale * ((double)v + 0.5) - 0.5;
+        const int ival = (int)std::floor(fval);
+        int ofs = 0, c1 = 0, interior = 0;
+        if (ival >= 0 && src_n > 1) {
+            if (ival < src_n - 1) { ofs = ival; c1 = (int)std::nearbyint((fval - (double)ival) * 256.0); interior = 1; }
+            else ofs = src_n - 1;
+        }
+        t[2 * (size_t)v] = ofs;
+        t[2 * (size_t)v + 1] = c1 | (interior << 16);
+    }
+}
+
+static int resize_impl(stx_ctx* ctx, const stx_buf* src, int dw, int dh, bool dilate, const stx_buf* andmask, stx_buf** out)
+{
+    if (src->elem != STX_U8 || (src->c != 1 && src->c != 3)) return stx_fail(STX_ERR_UNSUPPORTED, "resize needs a u8x1 or u8x3 image");
+    if (dw <= 0 || dh <= 0) return stx_fail(STX_ERR_INVALID, "resize to %dx%d", dw, dh);
+    if (src->ctx->device != ctx->device) return stx_fail(STX_ERR_INVALID, "image lives on another device");
+    std::vector<int> xt, yt;
+    linear_exact_table(src->w, dw, xt);
+    linear_exact_table(src->h, dh, yt);
+    const size_t nx = xt.size();
+    xt.resize((nx + 7) & ~(size_t)7, 0);  // entries in whole groups of 4 columns (the 4-pixel seam kernel reads 4 at once), 32-byte rows
+    std::vector<int> both(xt);
+    both.insert(both.end(), yt.begin(), yt.end());
+    StxDevBlock d_tab;
+    STX_TRY(upload_small(ctx, both.data(), both.size() * sizeof(int), &d_tab));
+    StxBufRef dst;
+    STX_TRY(stx_buf_new(ctx, dw, dh, src->c, STX_U8, &dst));
+    STX_TRY(stx_launch_resize_exact(ctx, src, dst.get(), (const int*)d_tab.get(), (const int*)d_tab.get() + xt.size(), dilate, andmask));
+    *out = dst.release();
+    return STX_OK;
+}
+
+// coefficient set-up of cv::resize(INTER_LINEAR) for CV_32F [OCV-MEM]: f = (float)((d + 0.5) * scale - 0.5), s = floor(f),
+// f -= s; horizontal offsets are clamped with f = 0 at both ends, vertical ones are not (rows are clamped when fetched)
+static void linear_f32_table(int src_n, int dst_n, bool clamp_offsets, std::vector<int>& t)
+{
+    t.resize(2 * (size_t)dst_n);
+    const double scale = 1.0 / ((double)dst_n / (double)src_n);
+    for (int d = 0; d < dst_n; d++) {
+        float f = (float)(((double)d + 0.5) * scale - 0.5);
+        int sidx = (int)std::floor(f);
+        f = f - (float)sidx;
+        if (clamp_offsets) {
+            if (sidx < 0) { sidx = 0; f = 0.f; }
+            else if (sidx >= src_n - 1) { sidx = src_n - 1; f = 0.f; }
+        }
+        int bits;
+        memcpy(&bits, &f, 4);
+        t[2 * (size_t)d] = sidx;
+        t[2 * (size_t)d + 1] = bits;
+    }
+}
+
+// one image through the one-pixel-per-lane kernel: any alignment (views), any gain-map size
+static int block_gain_plain(stx_ctx* ctx, stx_buf* img, const stx_buf* gain_map)
+{
+    std::vector<int> xt, yt;
+    linear_f32_table(gain_map->w, img->w, true, xt);
+    linear_f32_table(gain_map->h, img->h, false, yt);
+    const size_t nx = xt.size();
+    xt.resize((nx + 7) & ~(size_t)7, 0);  // entries in whole groups of 4 columns (the 4-pixel seam kernel reads 4 at once), 32-byte rows
+    std::vector<int> both(xt);
+    both.insert(both.end(), yt.begin(), yt.end());
+    StxDevBlock d_tab;
+    STX_TRY(upload_small(ctx, both.data(), both.size() * sizeof(int), &d_tab));
+    return stx_launch_block_gain(ctx, img, gain_map, (const int*)d_tab.get(), (const int*)d_tab.get() + xt.size());
+}
+
+int block_gain_check(stx_ctx* ctx, const stx_buf* img, const stx_buf* gain_map)
+{
+    if (!gain_map) return stx_fail(STX_ERR_INVALID, "null argument");
+    if (img && (img->elem != STX_U8 || img->c != 3)) return stx_fail(STX_ERR_INVALID, "block gain apply needs a u8x3 image");
+    if (gain_map->elem != STX_F32 || (gain_map->c != 1 && gain_map->c != 3))
+        return stx_fail(STX_ERR_INVALID, "the gain map must be f32x1 (gain_blocks) or f32x3 (channel_blocks)");
+    if ((img && img->ctx != ctx) || gain_map->ctx->device != ctx->device) return stx_fail(STX_ERR_INVALID, "buffers belong to another context");
+    return STX_OK;
+}
+
+// flags_or_null[i] & STX_GAIN_MAP_BOUNDED: the caller has checked that every gain of map i is finite and |g| < 2^31 / 255 (then no
+// product p * g can leave the int range, and the kernel drops the cvRound overflow test)
+STX_EXPORT int stx_block_gain_apply_batch(stx_ctx* ctx, int n, stx_buf* const* imgs, const stx_buf* const* gain_maps,
+                                          const int* full_wh_xy0, const int* flags_or_null)
+{
+    if (!ctx || n < 0 || (n > 0 && (!imgs || !gain_maps))) return stx_fail(STX_ERR_INVALID, "bad argument");
+    if (n == 0) return STX_OK;
+    STX_TRY(stx_set_device(ctx));
+    for (int i = 0; i < n; i++) {
+        if (!imgs[i]) return stx_fail(STX_ERR_INVALID, "null argument");
+        STX_TRY(block_gain_check(ctx, imgs[i], gain_maps[i]));
+        if (full_wh_xy0) {
+            const int* q = full_wh_xy0 + 4 * i;
+            if (q[2] < 0 || q[3] < 0 || q[2] + imgs[i]->w > q[0] || q[3] + imgs[i]->h > q[1])
+                return stx_fail(STX_ERR_INVALID, "image %d: rectangle (%d,%d,%dx%d) outside the full image %dx%d", i, q[2], q[3], imgs[i]->w, imgs[i]->h, q[0], q[1]);
+        }
+    }
+    // the batched kernels want whole buffers of the library's own (dword rows, 4-pixel groups) and gain maps of block size (their
+    // horizontally interpolated rows are kept: gh x w floats); anything else takes the plain kernel, one image at a time
+    std::vector<stx_buf*> bi;
+    std::vector<const stx_buf*> bg;
+    std::vector<int> sub, fast, plain;
+    size_t scratch = 0;
+    std::vector<size_t> offH, offY;
+    // classify and validate EVERY image before anything is launched: the product is written in place, so a call that fails must not
+    // have multiplied some of its images already (a caller could not retry it)
+    for (int i = 0; i < n; i++) {
+        const stx_buf* im = imgs[i];
+        const bool whole = !im->parent && ((uintptr_t)im->ptr & 3) == 0 && (im->stride & 3) == 0 && (size_t)((im->w + 3) & ~3) * 3 <= im->stride;
+        const size_t hbytes = (size_t)gain_maps[i]->h * ((im->w + 3) & ~3) * gain_maps[i]->c * sizeof(float);
+        int first_c = -1;
+        for (int j = 0; j < i && first_c < 0; j++)
+            if (std::find(plain.begin(), plain.end(), j) == plain.end()) first_c = gain_maps[j]->c;
+        const bool same_c = first_c < 0 || gain_maps[i]->c == first_c;
+        if (!whole || hbytes > ((size_t)64 << 20) || !same_c) {
+            if (full_wh_xy0 && (full_wh_xy0[4 * i] != im->w || full_wh_xy0[4 * i + 1] != im->h))
+                return stx_fail(STX_ERR_UNSUPPORTED, "image %d: a rectangle of a larger image must be a whole buffer with a block-sized gain map", i);
+            plain.push_back(i);
+        }
+    }
+    for (int i : plain) STX_TRY(block_gain_plain(ctx, imgs[i], gain_maps[i]));
+    for (int i = 0; i < n; i++) {
+        if (std::find(plain.begin(), plain.end(), i) != plain.end()) continue;
+        const stx_buf* im = imgs[i];
+        const size_t hbytes = (size_t)gain_maps[i]->h * ((im->w + 3) & ~3) * gain_maps[i]->c * sizeof(float);
+        bi.push_back(imgs[i]); bg.push_back(gain_maps[i]);
+        for (int k = 0; k < 4; k++) sub.push_back(full_wh_xy0 ? full_wh_xy0[4 * i + k] : (k == 0 ? im->w : (k == 1 ? im->h : 0)));
+        fast.push_back(flags_or_null && (flags_or_null[i] & STX_GAIN_MAP_BOUNDED) ? 1 : 0);
+        offH.push_back(scratch); scratch += align_up(hbytes, 256);
+        offY.push_back(scratch); scratch += align_up((size_t)im->h * 8, 256);
+    }
+    if (bi.empty()) return STX_OK;
+    StxDevBlock d;
+    STX_TRY(stx_dev_alloc(ctx, scratch, &d));
+    std::vector<float*> Hs(bi.size());
+    std::vector<void*> yts(bi.size());
+    for (size_t i = 0; i < bi.size(); i++) { Hs[i] = (float*)((uint8_t*)d.get() + offH[i]); yts[i] = (uint8_t*)d.get() + offY[i]; }
+    return stx_launch_block_gain_batch(ctx, (int)bi.size(), bi.data(), bg.data(), sub.data(), Hs.data(), yts.data(), fast.data());
+}
+
+STX_EXPORT int stx_block_gain_apply(stx_ctx* ctx, stx_buf* img, const stx_buf* gain_map)
+{
+    if (!ctx) return stx_fail(STX_ERR_INVALID, "null argument");
+    return stx_block_gain_apply_batch(ctx, 1, &img, &gain_map, nullptr, nullptr);
+}
+
+STX_EXPORT int stx_resize_linear_exact(stx_ctx* ctx, const stx_buf* src, int dst_w, int dst_h, stx_buf** out)
+{
+    if (!ctx || !src || !out) return stx_fail(STX_ERR_INVALID, "null argument");
+    STX_TRY(stx_set_device(ctx));
+    return resize_impl(ctx, src, dst_w, dst_h, false, nullptr, out);
+}
+
+STX_EXPORT int stx_seam_mask_resize(stx_ctx* ctx, const stx_buf* seam_mask, const stx_buf* final_mask, stx_buf** out)
+{
+    if (!ctx || !seam_mask || !final_mask || !out) return stx_fail(STX_ERR_INVALID, "null argument");
+    if (seam_mask->c != 1 || seam_mask->elem != STX_U8 || final_mask->c != 1 || final_mask->elem != STX_U8)
+        return stx_fail(STX_ERR_INVALID, "seam masks are u8x1");
+    STX_TRY(stx_set_device(ctx));
+    if (seam_mask->ctx->device == ctx->device && final_mask->ctx->device == ctx->device) {  // the one-launch form first
+        StxBufRef d;
+        STX_TRY(stx_buf_new(ctx, final_mask->w, final_mask->h, 1, STX_U8, &d));
+        stx_buf* const dp = d.get();
+        bool done = false;
+        STX_TRY(stx_launch_seam_resize_lds(ctx, 1, &seam_mask, &final_mask, &dp, nullptr, &done));
+        if (done) { *out = d.release(); return STX_OK; }
+    }
+    return resize_impl(ctx, seam_mask, final_mask->w, final_mask->h, true, final_mask, out);
+}
+
+// SeamFinder.resize for all images of a panorama: one table upload, one dilate launch and one resize launch per 16 images.
+// Falls back to the per-image call when a buffer does not meet the 4-pixel kernel's alignment needs.
+// sub: null -> final_masks[i] is the whole final mask; else {full_w, full_h, x0, y0} per image: final_masks[i] is the
+// rectangle at (x0, y0) of a final mask of size full_w x full_h (the seam mask is enlarged to THAT size, only the
+// rectangle is produced; x0 a multiple of 4)
+static int seam_resize_batch_impl(stx_ctx* ctx, int n, const stx_buf* const* seam_masks, const stx_buf* const* final_masks,
+                                  const int* sub, stx_buf** outs)
+{
+    if (!ctx || n < 0 || (n > 0 && (!seam_masks || !final_masks || !outs))) return stx_fail(STX_ERR_INVALID, "null argument");
+    STX_TRY(stx_set_device(ctx));
+    bool fast = true;
+    for (int i = 0; i < n && sub; i++) {
+        const int* q = sub + 4 * i;
+        if (!final_masks[i] || q[2] < 0 || q[3] < 0 || (q[2] & 3) || q[2] + final_masks[i]->w > q[0] || q[3] + final_masks[i]->h > q[1])
+            return stx_fail(STX_ERR_INVALID, "seam mask rectangle %d outside its final mask (or x0 not a multiple of 4)", i);
+    }
+    for (int i = 0; i < n; i++) {
+        const stx_buf *s = seam_masks[i], *m = final_masks[i];
+        if (!s || !m) return stx_fail(STX_ERR_INVALID, "null argument");
+        if (s->c != 1 || s->elem != STX_U8 || m->c != 1 || m->elem != STX_U8) return stx_fail(STX_ERR_INVALID, "seam masks are u8x1");
+        if (s->ctx->device != ctx->device || m->ctx->device != ctx->device) return stx_fail(STX_ERR_INVALID, "image lives on another device");
+        fast = fast && ((uintptr_t)m->ptr & 3) == 0 && (m->stride & 3) == 0 && (size_t)((m->w + 3) & ~3) <= m->stride;
+    }
+    if (n == 0) return STX_OK;
+    // final masks the 4-pixel kernel cannot read in place (a view that starts on an odd byte, a pitch that is not a multiple
+    // of 4): whole masks go through the per-image call; rectangles (sub) are first copied into aligned buffers of their own
+    std::vector<StxBufRef> aligned;  // released on every path below
+    std::vector<const stx_buf*> fm(final_masks, final_masks + n);
+    if (!fast && !sub) {
+        std::vector<StxBufRef> made(n);
+        for (int i = 0; i < n; i++) {
+            const int rc1 = stx_seam_mask_resize(ctx, seam_masks[i], final_masks[i], &outs[i]);
+            if (rc1 != STX_OK) {  // hand nothing out: `made` releases what the earlier iterations produced
+                std::fill(outs, outs + i, nullptr);
+                return rc1;
+            }
+            made[i].reset(outs[i]);
+        }
+        for (StxBufRef& m : made) m.release();
+        return STX_OK;
+    }
+    if (!fast) {
+        for (int i = 0; i < n; i++) {
+            const stx_buf* m = final_masks[i];
+            if (((uintptr_t)m->ptr & 3) == 0 && (m->stride & 3) == 0 && (size_t)((m->w + 3) & ~3) <= m->stride) continue;
+            aligned.emplace_back();
+            StxBufRef& c = aligned.back();
+            STX_TRY(stx_buf_new(ctx, m->w, m->h, 1, STX_U8, &c));
+            STX_HIP(hipMemcpy2DAsync(c->ptr, c->stride, m->ptr, m->stride, (size_t)m->w, (size_t)m->h, hipMemcpyDeviceToDevice, ctx->stream));
+            c->mask_binary = m->mask_binary;
+            fm[i] = c.get();
+        }
+    }
+    final_masks = fm.data();
+    {
+        // the one-launch form: nothing to upload, no scratch (whole buffers of the library's own qualify; anything else: the tables below)
+        std::vector<StxBufRef> d1(n);
+        for (int i = 0; i < n; i++) STX_TRY(stx_buf_new(ctx, final_masks[i]->w, final_masks[i]->h, 1, STX_U8, &d1[i]));
+        bool done = false;
+        STX_TRY(stx_launch_seam_resize_lds(ctx, n, seam_masks, final_masks, stx_buf_ptrs(d1).data(), sub, &done));
+        if (done) {
+            for (int i = 0; i < n; i++) outs[i] = d1[i].release();
+            return STX_OK;
+        }
+    }
+    // tables of all images in one upload: per image xt (dw rounded up to 4 entries) then yt
+    std::vector<int> all;
+    std::vector<size_t> xoff(n), yoff(n);
+    for (int i = 0; i < n; i++) {
+        std::vector<int> xt, yt;
+        linear_exact_table(seam_masks[i]->w, sub ? sub[4 * i] : final_masks[i]->w, xt);
+        linear_exact_table(seam_masks[i]->h, sub ? sub[4 * i + 1] : final_masks[i]->h, yt);
+        if (sub) {  // the rectangle's slice of the tables (2 ints per destination column / row)
+            const int x0 = sub[4 * i + 2], y0 = sub[4 * i + 3];
+            xt = std::vector<int>(xt.begin() + 2 * (size_t)x0, xt.begin() + 2 * (size_t)(x0 + final_masks[i]->w));
+            yt = std::vector<int>(yt.begin() + 2 * (size_t)y0, yt.begin() + 2 * (size_t)(y0 + final_masks[i]->h));
+        }
+        xt.resize((xt.size() + 7) & ~(size_t)7, 0);
+        xoff[i] = all.size();
+        all.insert(all.end(), xt.begin(), xt.end());
+        yoff[i] = all.size();
+        all.insert(all.end(), yt.begin(), yt.end());
+        all.resize((all.size() + 7) & ~(size_t)7, 0);  // keep every table 32-byte aligned
+    }
+    StxDevBlock d_tab;
+    STX_TRY(upload_small(ctx, all.data(), all.size() * sizeof(int), &d_tab));
+    std::vector<StxBufRef> dsts(n);
+    std::vector<StxDevBlock> tmps(n);  // (declared after d_tab: returned to the allocator first)
+    std::vector<uint8_t*> tptr(n);
+    std::vector<size_t> tstride(n);
+    std::vector<const int*> dx(n), dy(n);
+    for (int i = 0; i < n; i++) {
+        STX_TRY(stx_buf_new(ctx, final_masks[i]->w, final_masks[i]->h, 1, STX_U8, &dsts[i]));
+        tstride[i] = ((size_t)seam_masks[i]->w + 63) & ~(size_t)63;
+        STX_TRY(stx_dev_alloc(ctx, tstride[i] * seam_masks[i]->h, &tmps[i]));
+        tptr[i] = (uint8_t*)tmps[i].get();
+        dx[i] = (const int*)d_tab.get() + xoff[i];
+        dy[i] = (const int*)d_tab.get() + yoff[i];
+    }
+    STX_TRY(stx_launch_seam_resize_batch(ctx, n, seam_masks, final_masks, stx_buf_ptrs(dsts).data(), dx.data(), dy.data(), tptr.data(), tstride.data()));
+    for (int i = 0; i < n; i++) outs[i] = dsts[i].release();
+    return STX_OK;  // the scratch blocks go back here: stream-ordered reuse
+}
+
+STX_EXPORT int stx_seam_mask_resize_batch(stx_ctx* ctx, int n, const stx_buf* const* seam_masks, const stx_buf* const* final_masks,
+                                          stx_buf** outs)
+{
+    return seam_resize_batch_impl(ctx, n, seam_masks, final_masks, nullptr, outs);
+}
+
+STX_EXPORT int stx_seam_mask_resize_batch_sub(stx_ctx* ctx, int n, const stx_buf* const* seam_masks, const stx_buf* const* final_masks,
+                                              const int* full_wh_xy0, stx_buf** outs)
+{
+    if (!full_wh_xy0 && n > 0) return stx_fail(STX_ERR_INVALID, "null argument");
+    return seam_resize_batch_impl(ctx, n, seam_masks, final_masks, full_wh_xy0, outs);
+}

@@ -58,15 +58,14 @@ int seam_plan(int n, const int* sizes, const int* corners, std::vector<SeamPlanP
 
 struct SeamRun {
     stx_ctx* ctx = nullptr;
-    StxSeamPair* d_pairs = nullptr;
-    uint16_t* d_arena = nullptr;
+    StxDevBlock d_pairs, d_arena;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     ~SeamRun()
     {
         if (!ctx) return;
         hipStreamSynchronize(ctx->stream);
-        stx_dev_free(ctx, d_pairs);
-        stx_dev_free(ctx, d_arena);
+        d_pairs.reset();  // behind the synchronisation
+        d_arena.reset();
         for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
     }
 };
@@ -113,29 +112,24 @@ STX_EXPORT int stx_seam_find(stx_ctx* ctx, int kind, int n, const int* sizes_wh,
     for (int k = 0; k < n; k++) masks_out[k] = nullptr;
     if (n == 0) return STX_OK;
     STX_TRY(stx_set_device(ctx));
+    std::vector<StxBufRef> outs(n);  // handed to masks_out at the end; on a failure released behind X's synchronisation
     SeamRun X;
     X.ctx = ctx;
-    auto fail = [&](int rc) {
-        hipStreamSynchronize(ctx->stream);
-        for (int k = 0; k < n; k++) { if (masks_out[k]) stx_buf_release(masks_out[k]); masks_out[k] = nullptr; }
-        return rc;
-    };
     if (out_info) {
         for (hipEvent_t& e : X.ev)
-            if (hipEventCreate(&e) != hipSuccess) return fail(stx_fail(STX_ERR_HIP, "hipEventCreate failed"));
-        if (hipEventRecord(X.ev[0], ctx->stream) != hipSuccess) return fail(stx_fail(STX_ERR_HIP, "hipEventRecord failed"));
+            if (hipEventCreate(&e) != hipSuccess) return stx_fail(STX_ERR_HIP, "hipEventCreate failed");
+        if (hipEventRecord(X.ev[0], ctx->stream) != hipSuccess) return stx_fail(STX_ERR_HIP, "hipEventRecord failed");
     }
     // the results: copies of the inputs (the caller's masks are never written)
     for (int k = 0; k < n; k++) {
         const stx_buf* m = masks_in[k];
-        int rc = stx_buf_new(ctx, m->w, m->h, 1, STX_U8, &masks_out[k]);
-        if (rc != STX_OK) return fail(rc);
-        masks_out[k]->mask_binary = m->mask_binary;  // zeroing keeps a 0 / 255 mask binary
-        if (hipMemcpy2DAsync(masks_out[k]->ptr, masks_out[k]->stride, m->ptr, m->stride, (size_t)m->w, m->h, hipMemcpyDeviceToDevice,
+        STX_TRY(stx_buf_new(ctx, m->w, m->h, 1, STX_U8, &outs[k]));
+        outs[k]->mask_binary = m->mask_binary;  // zeroing keeps a 0 / 255 mask binary
+        if (hipMemcpy2DAsync(outs[k]->ptr, outs[k]->stride, m->ptr, m->stride, (size_t)m->w, m->h, hipMemcpyDeviceToDevice,
                              ctx->stream) != hipSuccess)
-            return fail(stx_fail(STX_ERR_HIP, "hipMemcpy2DAsync of a seam mask failed"));
+            return stx_fail(STX_ERR_HIP, "hipMemcpy2DAsync of a seam mask failed");
     }
-    if (out_info && hipEventRecord(X.ev[1], ctx->stream) != hipSuccess) return fail(stx_fail(STX_ERR_HIP, "hipEventRecord failed"));
+    if (out_info && hipEventRecord(X.ev[1], ctx->stream) != hipSuccess) return stx_fail(STX_ERR_HIP, "hipEventRecord failed");
     if (!plan.empty()) {
         // pairs grouped by level (stable: run() order inside a level), arena offsets per level, one arena of the largest level
         std::vector<int> order(plan.size());
@@ -148,8 +142,8 @@ STX_EXPORT int stx_seam_find(stx_ctx* ctx, int kind, int n, const int* sizes_wh,
         const int g = STX_SEAM_GAP;
         for (size_t t = 0; t < order.size(); t++) {
             const SeamPlanPair& P = plan[order[t]];
-            const stx_buf* a = masks_out[P.i];
-            const stx_buf* b = masks_out[P.j];
+            const stx_buf* a = outs[P.i].get();
+            const stx_buf* b = outs[P.j].get();
             StxSeamPair& S = tab[t];
             S.m1 = a->ptr; S.s1 = (long long)a->stride; S.w1 = a->w; S.h1 = a->h;
             S.m2 = b->ptr; S.s2 = (long long)b->stride; S.w2 = b->w; S.h2 = b->h;
@@ -159,7 +153,7 @@ STX_EXPORT int stx_seam_find(stx_ctx* ctx, int kind, int n, const int* sizes_wh,
             // the roi (written unchecked by the column kernel) lies inside both images
             if (S.ox1 + g < 0 || S.oy1 + g < 0 || S.ox1 + g + P.w > a->w || S.oy1 + g + P.h > a->h || S.ox2 + g < 0 || S.oy2 + g < 0 ||
                 S.ox2 + g + P.w > b->w || S.oy2 + g + P.h > b->h)
-                return fail(stx_fail(STX_ERR_INVALID, "internal: seam roi outside its images"));
+                return stx_fail(STX_ERR_INVALID, "internal: seam roi outside its images");
             S.off = lsize[P.level];
             lsize[P.level] += 2ll * S.wh * S.rw;
             lstart[P.level + 1]++;
@@ -169,27 +163,24 @@ STX_EXPORT int stx_seam_find(stx_ctx* ctx, int kind, int n, const int* sizes_wh,
         }
         for (int l = 0; l < nlevels; l++) lstart[l + 1] += lstart[l];
         const long long arena = *std::max_element(lsize.begin(), lsize.end());
-        void* p = nullptr;
-        int rc = stx_dev_alloc(ctx, sizeof(StxSeamPair) * tab.size(), &p);
-        if (rc != STX_OK) return fail(rc);
-        X.d_pairs = (StxSeamPair*)p;
-        if ((rc = stx_dev_alloc(ctx, sizeof(uint16_t) * (size_t)arena, &p)) != STX_OK) return fail(rc);
-        X.d_arena = (uint16_t*)p;
-        if (hipMemcpyAsync(X.d_pairs, tab.data(), sizeof(StxSeamPair) * tab.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-            return fail(stx_fail(STX_ERR_HIP, "seam pair table upload failed"));
+        STX_TRY(stx_dev_alloc(ctx, sizeof(StxSeamPair) * tab.size(), &X.d_pairs));
+        STX_TRY(stx_dev_alloc(ctx, sizeof(uint16_t) * (size_t)arena, &X.d_arena));
+        const StxSeamPair* d_pairs = (const StxSeamPair*)X.d_pairs.get();
+        if (hipMemcpyAsync(X.d_pairs.get(), tab.data(), sizeof(StxSeamPair) * tab.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+            return stx_fail(STX_ERR_HIP, "seam pair table upload failed");
         for (int l = 0; l < nlevels; l++)
-            if ((rc = stx_launch_seam_level(ctx, X.d_pairs + lstart[l], lstart[l + 1] - lstart[l], lrows[l], lcols[l], X.d_arena,
-                                            lbytes[l])) != STX_OK)
-                return fail(rc);
+            STX_TRY(stx_launch_seam_level(ctx, d_pairs + lstart[l], lstart[l + 1] - lstart[l], lrows[l], lcols[l], (uint16_t*)X.d_arena.get(),
+                                          lbytes[l]));
     }
-    if (out_info && hipEventRecord(X.ev[2], ctx->stream) != hipSuccess) return fail(stx_fail(STX_ERR_HIP, "hipEventRecord failed"));
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(stx_fail(STX_ERR_HIP, "seam finding failed"));
+    if (out_info && hipEventRecord(X.ev[2], ctx->stream) != hipSuccess) return stx_fail(STX_ERR_HIP, "hipEventRecord failed");
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return stx_fail(STX_ERR_HIP, "seam finding failed");
     if (out_info) {
         float a = 0.f, b = 0.f;
         if (hipEventElapsedTime(&a, X.ev[1], X.ev[2]) != hipSuccess || hipEventElapsedTime(&b, X.ev[0], X.ev[2]) != hipSuccess)
-            return fail(stx_fail(STX_ERR_HIP, "hipEventElapsedTime failed"));
+            return stx_fail(STX_ERR_HIP, "hipEventElapsedTime failed");
         out_info[2] = a;
         out_info[3] = b;
     }
+    for (int k = 0; k < n; k++) masks_out[k] = outs[k].release();
     return STX_OK;
 }

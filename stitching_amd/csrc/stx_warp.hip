@@ -1254,9 +1254,9 @@ int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, cons
     size_t total = 0;
     // in float2 units: dw4 column entries + dh4 / 4 row blocks of 16 floats + dh4 floats (rb), rounded up to 3 dh4 float2
     for (int i = 0; i < n; i++) total += (((size_t)Ks[i].dw + 3) & ~(size_t)3) + 3 * (((size_t)Ks[i].dh + 3) & ~(size_t)3) + 32;
-    void* tab = nullptr;
+    StxDevBlock tab;
     STX_TRY(stx_dev_alloc(ctx, total * sizeof(float2), &tab));
-    float2* cursor = (float2*)tab;
+    float2* cursor = (float2*)tab.get();
     for (int base = 0, m = 0; base < n; base += m) {
         // a launch takes up to WARP_BATCH images of one remap model (the sampling block is compiled per model), all with or all without a gain
         const int rm = Ks[base].src ? Ks[base].remap : STX_REMAP_Q15;
@@ -1285,10 +1285,8 @@ int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, cons
             gx = std::max(gx, (K.dw + WARP_TW - 1) / WARP_TW);
             gy = std::max(gy, (K.dh + WARP_TH - 1) / WARP_TH);
             fast = fast && fast_ok(K) && dbg != 2;
-            if (gain && (!fast_ok(K) || dbg)) {
-                stx_dev_free(ctx, tab);
+            if (gain && (!fast_ok(K) || dbg))
                 return stx_fail(STX_ERR_UNSUPPORTED, "a fused gain needs the tuned warp kernel (image %d does not qualify)", base + i);
-            }
             tab_bytes += (double)K.dw * sizeof(float2) + (double)K.dh * 5 * sizeof(float);
             bytes += algo_bytes[base + i];
         }
@@ -1319,10 +1317,7 @@ int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, cons
                 wgs += own;
                 wg_max = std::max(wg_max, own);
             }
-            if (wgs >= (1ull << 31)) {
-                stx_dev_free(ctx, tab);
-                return stx_fail(STX_ERR_UNSUPPORTED, "warp batch of %llu tiles exceeds the grid", wgs);
-            }
+            if (wgs >= (1ull << 31)) return stx_fail(STX_ERR_UNSUPPORTED, "warp batch of %llu tiles exceeds the grid", wgs);
             const bool flat = !STX_WARP_ZGRID && !dbg && (double)wgs < 0.95 * (double)(wg_max * (unsigned long long)m);
             const dim3 gf(flat ? (unsigned)wgs : (unsigned)wg_max, 1, flat ? 1 : m);
             // STITCHING_AMD_WARP_LDS (diagnostic): bytes of dynamic LDS requested on top of the kernel's own — an occupancy limit
@@ -1369,7 +1364,7 @@ int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, cons
             }
         }
     }
-    stx_dev_free(ctx, tab);
+    tab.reset();  // stream-ordered reuse
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return stx_fail(STX_ERR_HIP, "warp kernel launch failed: %s", hipGetErrorString(e));
     return STX_OK;

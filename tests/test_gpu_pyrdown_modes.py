@@ -31,7 +31,7 @@ def _inputs():
 
 
 def _weight_pyramid_of_export(packed, rect, nb):
-    """the fp32 weight planes W_0 .. W_nb out of a packed contribution strip (csrc/stx_api.cpp mb_contrib_layout: per level three
+    """the fp32 weight planes W_0 .. W_nb out of a packed contribution strip (csrc/stx_blend_host.cpp mb_contrib_layout: per level three
     int16 planes, row pitch a multiple of 32 samples, then the weights, pitch a multiple of 16; every section on a 256-byte boundary)"""
     raw = np.asarray(packed).reshape(-1)
     w, h = rect[2], rect[3]

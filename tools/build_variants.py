@@ -15,7 +15,8 @@ with `=` for "what the Makefile ships for this file" and an empty field for "no 
     gpurun -- 'bash tools/gpu_ab_lib.sh <tag> 2 "base|stitching_amd/libv_base.so|| " ...'
 
 Objects are cached in /tmp/stx_variants by (file, flags, source digest); the libraries are git-ignored and travel to the GPU box.
-`--clean` removes stitching_amd/libv_*.so.  Variants share the HOST objects (stx_api.cpp, stx_comm.cpp) of the default flags.
+`--clean` removes stitching_amd/libv_*.so.  The sources are the Makefile's SRCS: the three kernel files above get a spec column, every
+other file (host units, kernels without a flag variable) is one shared object of the default flags.
 """
 import argparse
 import concurrent.futures as cf
@@ -34,11 +35,23 @@ MK_VARS = {"stx_warp.hip": "WARP_EXTRA", "stx_blend.hip": "BLEND_EXTRA", "stx_bl
 
 
 def makefile_var(name):
-    for line in open(os.path.join(CSRC, "Makefile")):
+    text = open(os.path.join(CSRC, "Makefile")).read().replace("\\\n", " ")  # continuation lines joined
+    for line in text.splitlines():
         m = re.match(rf"{name}\s*\??=\s*(.*)$", line)
         if m:
             return m.group(1).strip()
     raise SystemExit(f"no {name} in the Makefile")
+
+
+def makefile_sources():
+    """Every source file the Makefile compiles (SRCS holds the names without suffix)."""
+    srcs = []
+    for stem in makefile_var("SRCS").split():
+        found = [stem + ext for ext in (".cpp", ".hip") if os.path.exists(os.path.join(CSRC, stem + ext))]
+        if len(found) != 1:
+            raise SystemExit(f"SRCS names {stem}: expected exactly one of {stem}.cpp / {stem}.hip")
+        srcs += found
+    return srcs
 
 
 def source_digest():
@@ -90,7 +103,11 @@ def main():
             flags[f] = (shipped[f] + " " + p[1:].strip()).strip() if p.startswith("=") else p
         variants.append((parts[0], flags))
     digest = source_digest()
-    jobs = {("stx_api.cpp", ""), ("stx_comm.cpp", "")} | {(f, fl[f]) for _, fl in variants for f in FILES}
+    shared = [f for f in makefile_sources() if f not in FILES]
+    missing = [f for f in FILES if f not in makefile_sources()]
+    if missing:
+        raise SystemExit(f"the Makefile no longer lists {missing}")
+    jobs = {(f, "") for f in shared} | {(f, fl[f]) for _, fl in variants for f in FILES}
     objs = {}
     with cf.ThreadPoolExecutor(args.jobs) as ex:
         for src, flags, out, err in ex.map(lambda j: compile_obj(j[0], j[1], digest), sorted(jobs)):
@@ -99,7 +116,7 @@ def main():
             objs[(src, flags)] = out
     specs = []
     for label, fl in variants:
-        parts = [objs[("stx_api.cpp", "")], objs[("stx_comm.cpp", "")]] + [objs[(f, fl[f])] for f in FILES]
+        parts = [objs[(f, "")] for f in shared] + [objs[(f, fl[f])] for f in FILES]
         if any(p is None for p in parts):
             print(f"skipping {label}: an object failed to build", file=sys.stderr)
             continue

@@ -276,8 +276,8 @@ int stx_block_gain_apply_batch(stx_ctx* ctx, int n, stx_buf* const* imgs_u8x3, c
 /* ---- exposure-gain estimation: ExposureCompensator::feed (stitching/exposure_error_compensator.py:39-41) ------------------------
  * kind: the cv.detail ids of the compensators that estimate (ExposureCompensator_GAIN, _GAIN_BLOCKS, _CHANNELS, _CHANNELS_BLOCKS).
  * The overlap statistics of every feed are one kernel launch over a table of unit pairs (whole images or blocks); the linear system
- * is assembled and solved on the host (OpenCV's cv::solve(DECOMP_LU), eliminating only non-zero entries: the same bits as the dense
- * loop).  Parity: a restatement of OpenCV 4.x from recollection; tests/numpy_exposure.py is the contract. */
+ * is assembled on the host and solved there by default (OpenCV's cv::solve(DECOMP_LU), eliminating only non-zero entries: the same bits
+ * as the dense loop) or on the device (below: the same bits again).  Parity: a restatement of OpenCV 4.x from recollection; tests/numpy_exposure.py is the contract. */
 #define STX_EXPOSURE_GAIN 1
 #define STX_EXPOSURE_GAIN_BLOCKS 2
 #define STX_EXPOSURE_CHANNELS 3
@@ -301,6 +301,37 @@ int stx_exposure_stats(stx_ctx* ctx, int kind, int n, const stx_buf* const* imgs
  * other unit (gain 1).  out_gains: m values. */
 int stx_exposure_solve(int m, int npairs, const int* pairs_ij, const double* n_iij_iji, const unsigned char* skip,
                        double* out_gains);
+/* ---- the gain systems solved on the device -------------------------------------------------------------------------------------
+ * cv::solve(DECOMP_LU) as a dense fp64 elimination in HIP, returning THE SAME BITS as the host solve above: partial pivoting by the
+ * largest |a[j][i]| (the smallest row among equal magnitudes), alpha = a[j][i] * (-1 / a[i][i]), a[j][k] = a[j][k] + alpha * a[i][k]
+ * as one rounded product and one rounded sum (no FMA), every element updated by the pivots in ascending order; a blocked right-looking
+ * scheme (32 pivots per step: panel, row swaps + the panel's rows, trailing update) with the pivot indices on the device and no host
+ * synchronisation before the end.  The back substitution is one dependent chain: the non-zeros of U and the transformed right side are
+ * compacted on the device, copied back and substituted on the host in the host solve's order.  Inputs must be finite and hold no -0.
+ * Limit: the dense matrix takes 8 n^2 bytes of device memory; more than 16384 unknowns (2 GiB) are refused with STX_ERR_INVALID —
+ * there is no fall-back to the host.  A singular system fails with STX_ERR_INVALID, "exposure system is singular at row %d".
+ * Which one to pick: the device from a few thousand unknowns on (DESIGN.md section 9 has the measured table); below, the host.
+ *
+ * The solver of stx_exposure_feed is a process-wide mode: STX_EXPOSURE_SOLVER_HOST (default) or _DEVICE; STITCHING_AMD_EXPOSURE_SOLVER
+ * (host | device) sets the start-up value.  stx_exposure_feed_ex takes it per call (STX_EXPOSURE_SOLVER_DEFAULT: the mode). */
+#define STX_EXPOSURE_SOLVER_DEFAULT (-1)
+#define STX_EXPOSURE_SOLVER_HOST 0
+#define STX_EXPOSURE_SOLVER_DEVICE 1
+int stx_set_exposure_solver(int mode);
+int stx_get_exposure_solver(void);
+/* stx_exposure_feed with the solver given.  out_info (or NULL): {units, pair jobs, device statistics ms, assembly + solve + filter ms
+ * (wall clock: with the device solver it covers the device elimination and the host tail), the solver used, device elimination ms (HIP
+ * events), compaction + copy + back substitution ms, non-zeros of U — the last three summed over the solves, 0 with the host solver}. */
+int stx_exposure_feed_ex(stx_ctx* ctx, int kind, int n, const stx_buf* const* imgs_u8x3, const stx_buf* const* masks_u8,
+                         const int* corners_xy, int block_size, int nr_feeds, int solver, double* out_gains, long long* inout_count,
+                         double out_info[8]);
+/* The twin of stx_exposure_solve: the same assembly, systems of more than 3 unknowns eliminated on ctx's device (up to 3: Cramer's rule
+ * on the host, as there).  out_info (or NULL): {device elimination ms, compaction + copy + back substitution ms, non-zeros of U, 0}. */
+int stx_exposure_solve_device(stx_ctx* ctx, int m, int npairs, const int* pairs_ij, const double* n_iij_iji, const unsigned char* skip,
+                              double* out_gains, double out_info[4]);
+/* The elimination alone, for tests and tools: A (n x n, row-major, host) x = b by the device LU for every n >= 1 -> x_out[n], the bits
+ * of tests/numpy_exposure.py::lu_solve(A, b, skip_zeros=False).  out_info as stx_exposure_solve_device. */
+int stx_lu_solve_device(stx_ctx* ctx, int n, const double* A_dense_host, const double* b_host, double* x_out, double out_info[4]);
 /* ---- seam finding: SeamFinder::find of the "voronoi" and "no" finders (stitching/seam_finder.py:33-35) -------------------------
  * kind: STX_SEAM_VORONOI (VoronoiSeamFinder: PairwiseSeamFinder::run over the overlapping pairs (i, j), i < j, in order; a gap of
  * 10 pixels around each overlap; dist1 < dist2 of the L1 distances (saturated at 8192) zeroes mask j there, anything else mask i) or

@@ -4,8 +4,9 @@ hand-written HIP kernels behind the C ABI in include/stitching_amd.h (loaded wit
 PyTorch, no OpenCV, no CPU fallback)."""
 from .blender import Blender
 from .camera import CameraParams
-from .config import (device_resident, exposure_estimator, pyrdown_mode, remap_mode, seam_estimator, set_device_resident,
-                     set_exposure_estimator, set_pyrdown_mode, set_remap_mode, set_seam_estimator, set_trig_mode, trig_mode)
+from .config import (device_resident, exposure_estimator, exposure_solver, pyrdown_mode, remap_mode, seam_estimator, set_device_resident,
+                     set_exposure_estimator, set_exposure_solver, set_pyrdown_mode, set_remap_mode, set_seam_estimator, set_trig_mode,
+                     trig_mode)
 from .cropper import Cropper, Rectangle
 from .device import Context, DeviceImage, as_device, device_count, get_context, pinned_empty, set_default_device
 from .exposure_error_compensator import ExposureErrorCompensator
@@ -21,6 +22,6 @@ __all__ = [
     "Blender", "CameraParams", "Context", "Cropper", "Rectangle", "DeviceImage", "ExposureErrorCompensator", "ExposureEstimator", "Images", "MegapixDownscaler", "MegapixScaler", "StitchingError", "StitchingWarning",
     "SeamEstimator", "SeamFinder", "Timelapser", "Warper", "resize_linear_exact",
     "as_device", "device_count", "pinned_empty", "device_resident", "get_context", "set_default_device", "set_device_resident", "set_trig_mode", "trig_mode", "set_remap_mode", "remap_mode", "set_pyrdown_mode", "pyrdown_mode",
-    "set_exposure_estimator", "exposure_estimator", "set_seam_estimator", "seam_estimator",
+    "set_exposure_estimator", "exposure_estimator", "set_exposure_solver", "exposure_solver", "set_seam_estimator", "seam_estimator",
 ]
 __version__ = "0.1.0"

@@ -123,6 +123,29 @@ def exposure_estimator():
     return _exposure_estimator
 
 
+def set_exposure_solver(mode):
+    """Where ExposureEstimator solves its gain systems (include/stitching_amd.h STX_EXPOSURE_SOLVER_*): "host" (default: the sparse LU on
+    one CPU thread) or "device" (the dense fp64 LU in HIP: the same bits; worth it from a few thousand unknowns on, i.e. the block
+    compensators on many frames — DESIGN.md section 9).  An ExposureEstimator built with solver= keeps its own.  Process-wide;
+    STITCHING_AMD_EXPOSURE_SOLVER sets the start-up value.  Returns the previous mode."""
+    from . import _lib
+
+    L = _lib.lib()
+    prev = exposure_solver()
+    if mode not in _lib.EXPOSURE_SOLVERS:
+        from .stitching_error import StitchingError
+
+        raise StitchingError(f"unknown exposure solver {mode!r}: one of {sorted(_lib.EXPOSURE_SOLVERS)}")
+    _lib.check(L.stx_set_exposure_solver(_lib.EXPOSURE_SOLVERS[mode]))
+    return prev
+
+
+def exposure_solver():
+    from . import _lib
+
+    return {v: k for k, v in _lib.EXPOSURE_SOLVERS.items()}[_lib.lib().stx_get_exposure_solver()]
+
+
 def _parse_seam_estimator(mode):
     if mode not in SEAM_ESTIMATORS:
         from .stitching_error import StitchingError

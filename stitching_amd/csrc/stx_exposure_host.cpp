@@ -96,8 +96,27 @@ int lu_solve_sparse(std::vector<SparseRow>& R, std::vector<double>& b)
     return STX_OK;
 }
 
-// GainCompensator::singleFeed's system over the non-skipped units, solved: gains of all m units (skipped ones 1)
-int exp_solve(int m, const std::vector<PairStat>& pairs, const std::vector<char>& skip, double* gains)
+// The same system by the dense LU on the device (stx_solve.hip): the assembled rows and b (as column m) are its entries.  acc (or null)
+// gathers {device elimination ms, compaction + copy + back substitution ms, non-zeros of U} over the solves of a feed.
+int lu_solve_device(stx_ctx* dev, const std::vector<SparseRow>& R, std::vector<double>& b, double* acc)
+{
+    const int m = (int)R.size();
+    std::vector<StxLuEntry> ent;
+    for (int r = 0; r < m; r++) {
+        for (const auto& e : R[r]) ent.push_back({r, e.first, e.second});
+        if (b[r] != 0.0) ent.push_back({r, m, b[r]});
+    }
+    double info[3] = {0.0, 0.0, 0.0};
+    STX_TRY(stx_lu_device(dev, m, ent.data(), ent.size(), b.data(), info));
+    if (acc)
+        for (int k = 0; k < 3; k++) acc[k] += info[k];
+    return STX_OK;
+}
+
+// GainCompensator::singleFeed's system over the non-skipped units, solved: gains of all m units (skipped ones 1).  dev: null for the
+// host LU, else the context whose device runs the elimination (more than 3 unknowns; Cramer's rule stays on the host)
+int exp_solve(int m, const std::vector<PairStat>& pairs, const std::vector<char>& skip, double* gains, stx_ctx* dev = nullptr,
+              double* dev_acc = nullptr)
 {
     std::vector<int> k(m, -1);
     int mm = 0;
@@ -143,7 +162,8 @@ int exp_solve(int m, const std::vector<PairStat>& pairs, const std::vector<char>
             for (auto& e : R[r]) S[r * mm + e.first] = e.second;
         solve_small(mm, S, b.data(), x.data());
     } else {
-        STX_TRY(lu_solve_sparse(R, b));
+        if (dev) STX_TRY(lu_solve_device(dev, R, b, dev_acc));
+        else STX_TRY(lu_solve_sparse(R, b));
         x = b;
     }
     for (int u = 0; u < m; u++)
@@ -350,8 +370,10 @@ int exp_check_ctx(stx_ctx* ctx, const ExpPlan& P, const stx_buf* const* imgs)
 
 }  // namespace
 
-STX_EXPORT int stx_exposure_solve(int m, int npairs, const int* pairs_ij, const double* n_iij_iji, const unsigned char* skip,
-                                  double* out_gains)
+namespace {
+
+int exp_solve_abi(stx_ctx* dev, int m, int npairs, const int* pairs_ij, const double* n_iij_iji, const unsigned char* skip, double* out_gains,
+                  double* dev_acc)
 {
     if (m < 0 || npairs < 0 || (m > 0 && (!skip || !out_gains)) || (npairs > 0 && (!pairs_ij || !n_iij_iji)))
         return stx_fail(STX_ERR_INVALID, "bad argument");
@@ -362,7 +384,46 @@ STX_EXPORT int stx_exposure_solve(int m, int npairs, const int* pairs_ij, const 
         pairs[p] = {i, j, n_iij_iji[3 * p], n_iij_iji[3 * p + 1], n_iij_iji[3 * p + 2]};
     }
     std::vector<char> sk(skip, skip + m);
-    return exp_solve(m, pairs, sk, out_gains);
+    return exp_solve(m, pairs, sk, out_gains, dev, dev_acc);
+}
+
+}  // namespace
+
+STX_EXPORT int stx_exposure_solve(int m, int npairs, const int* pairs_ij, const double* n_iij_iji, const unsigned char* skip,
+                                  double* out_gains)
+{
+    return exp_solve_abi(nullptr, m, npairs, pairs_ij, n_iij_iji, skip, out_gains, nullptr);
+}
+
+STX_EXPORT int stx_exposure_solve_device(stx_ctx* ctx, int m, int npairs, const int* pairs_ij, const double* n_iij_iji,
+                                         const unsigned char* skip, double* out_gains, double out_info[4])
+{
+    if (!ctx) return stx_fail(STX_ERR_INVALID, "ctx is null");
+    double acc[3] = {0.0, 0.0, 0.0};
+    if (out_info) out_info[0] = out_info[1] = out_info[2] = out_info[3] = 0.0;
+    STX_TRY(exp_solve_abi(ctx, m, npairs, pairs_ij, n_iij_iji, skip, out_gains, acc));
+    if (out_info) { out_info[0] = acc[0]; out_info[1] = acc[1]; out_info[2] = acc[2]; }
+    return STX_OK;
+}
+
+STX_EXPORT int stx_lu_solve_device(stx_ctx* ctx, int n, const double* A, const double* b, double* x_out, double out_info[4])
+{
+    if (!ctx) return stx_fail(STX_ERR_INVALID, "ctx is null");
+    if (n < 1 || !A || !b || !x_out) return stx_fail(STX_ERR_INVALID, "bad argument");
+    if (n > STX_LU_MAX_N)
+        return stx_fail(STX_ERR_INVALID, "device LU: n = %d unknowns exceed the limit of %d (the dense fp64 matrix takes 8 n^2 bytes)", n,
+                        STX_LU_MAX_N);
+    std::vector<StxLuEntry> ent;
+    for (int r = 0; r < n; r++) {
+        for (int c = 0; c < n; c++)
+            if (A[(size_t)r * n + c] != 0.0) ent.push_back({r, c, A[(size_t)r * n + c]});
+        if (b[r] != 0.0) ent.push_back({r, n, b[r]});
+    }
+    double info[3] = {0.0, 0.0, 0.0};
+    if (out_info) out_info[0] = out_info[1] = out_info[2] = out_info[3] = 0.0;
+    STX_TRY(stx_lu_device(ctx, n, ent.data(), ent.size(), x_out, info));
+    if (out_info) { out_info[0] = info[0]; out_info[1] = info[1]; out_info[2] = info[2]; }
+    return STX_OK;
 }
 
 STX_EXPORT int stx_exposure_stats(stx_ctx* ctx, int kind, int n, const stx_buf* const* imgs, const stx_buf* const* masks,
@@ -397,6 +458,20 @@ STX_EXPORT int stx_exposure_feed(stx_ctx* ctx, int kind, int n, const stx_buf* c
                                  const int* corners_xy, int block_size, int nr_feeds, double* out_gains, long long* inout_count,
                                  double out_info[4])
 {
+    double info[8];
+    STX_TRY(stx_exposure_feed_ex(ctx, kind, n, imgs, masks, corners_xy, block_size, nr_feeds, STX_EXPOSURE_SOLVER_DEFAULT, out_gains,
+                                 inout_count, out_info ? info : nullptr));
+    if (out_info && out_gains)
+        for (int k = 0; k < 4; k++) out_info[k] = info[k];
+    return STX_OK;
+}
+
+STX_EXPORT int stx_exposure_feed_ex(stx_ctx* ctx, int kind, int n, const stx_buf* const* imgs, const stx_buf* const* masks,
+                                    const int* corners_xy, int block_size, int nr_feeds, int solver, double* out_gains,
+                                    long long* inout_count, double out_info[8])
+{
+    if (solver == STX_EXPOSURE_SOLVER_DEFAULT) solver = exposure_solver_now();
+    if (solver != STX_EXPOSURE_SOLVER_HOST && solver != STX_EXPOSURE_SOLVER_DEVICE) return stx_fail(STX_ERR_INVALID, "exposure solver %d", solver);
     if (!inout_count) return stx_fail(STX_ERR_INVALID, "inout_count is null");
     if (nr_feeds < 1) return stx_fail(STX_ERR_INVALID, "nr_feeds must be >= 1");
     ExpPlan P;
@@ -404,7 +479,10 @@ STX_EXPORT int stx_exposure_feed(stx_ctx* ctx, int kind, int n, const stx_buf* c
     if (!out_gains) { *inout_count = P.out_count; return STX_OK; }
     if (*inout_count < P.out_count) return stx_fail(STX_ERR_INVALID, "out_gains holds %lld values, %lld needed", *inout_count, P.out_count);
     *inout_count = P.out_count;
-    if (out_info) { out_info[0] = P.units; out_info[1] = (double)P.jobs.size(); out_info[2] = 0.0; out_info[3] = 0.0; }
+    if (out_info) {
+        for (int k = 0; k < 8; k++) out_info[k] = 0.0;
+        out_info[0] = P.units; out_info[1] = (double)P.jobs.size(); out_info[4] = solver;
+    }
     if (n == 0) return STX_OK;
     STX_TRY(exp_check_ctx(ctx, P, imgs));
     STX_TRY(stx_set_device(ctx));
@@ -416,7 +494,8 @@ STX_EXPORT int stx_exposure_feed(stx_ctx* ctx, int kind, int n, const stx_buf* c
     ExpRun X;
     X.ctx = ctx;
     std::vector<StxBufRef>& scratch = X.scratch;
-    double stats_ms = 0.0, host_ms = 0.0;
+    double stats_ms = 0.0, host_ms = 0.0, dev_acc[3] = {0.0, 0.0, 0.0};
+    stx_ctx* const solve_on = solver == STX_EXPOSURE_SOLVER_DEVICE ? ctx : nullptr;
     std::vector<long long> oi;
     std::vector<double> od;
     for (int feed = 0; feed < nr_feeds; feed++) {
@@ -483,7 +562,7 @@ STX_EXPORT int stx_exposure_feed(stx_ctx* ctx, int kind, int n, const stx_buf* c
                 }
                 pairs[j] = {P.ab[2 * j], P.ab[2 * j + 1], nn, cnt > 0 ? sa / nn : 0.0, cnt > 0 ? sb / nn : 0.0};
             }
-            STX_TRY(exp_solve(m, pairs, skip, g.data() + (size_t)c * m));
+            STX_TRY(exp_solve(m, pairs, skip, g.data() + (size_t)c * m, solve_on, dev_acc));
         }
         for (size_t k = 0; k < acc.size(); k++) acc[k] = acc[k] * g[k];
         host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -504,6 +583,9 @@ STX_EXPORT int stx_exposure_feed(stx_ctx* ctx, int kind, int n, const stx_buf* c
         for (float v : map) *o++ = v;
     }
     host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (out_info) { out_info[2] = stats_ms; out_info[3] = host_ms; }
+    if (out_info) {
+        out_info[2] = stats_ms; out_info[3] = host_ms;
+        for (int k = 0; k < 3; k++) out_info[5 + k] = dev_acc[k];
+    }
     return STX_OK;
 }

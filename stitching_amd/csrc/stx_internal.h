@@ -168,6 +168,7 @@ inline std::vector<stx_buf*> stx_buf_ptrs(const std::vector<StxBufRef>& v)
 int trig_mode_now();     // STX_TRIG_*
 int remap_mode_now();    // STX_REMAP_*
 int pyrdown_now();       // STX_PYRDOWN_* | lanes << 8
+int exposure_solver_now();  // STX_EXPOSURE_SOLVER_*
 
 // ---------------------------------------------------------------------------------------------
 // projector (host side of ProjectorBase::setCameraParams)
@@ -261,6 +262,12 @@ int stx_launch_exposure_stats(stx_ctx* ctx, const StxExpImg* d_imgs, const StxEx
 // one u8x3 image multiplied by per-block gains g (bpw blocks of bw x bh per row, 1 or 3 (g3) floats per block)
 struct StxExpBlockMul { uint8_t* img; long long stride; int w, h, bw, bh, bpw; const float* g; int g3; };
 int stx_launch_exposure_block_mul(stx_ctx* ctx, const StxExpBlockMul* d_tab, int n, int max_pixels);
+// cv::solve(DECOMP_LU) in fp64 on the device (stx_solve.hip): the n x n system given by its non-zero entries (col < n) and its right side
+// (col == n) -> x[n], the bits of the host's lu_solve_sparse.  The dense matrix takes 8 n^2 bytes of device memory: n <= STX_LU_MAX_N
+// (2 GiB).  out (or null): {device ms of scatter + elimination, ms of compaction + copy + host back substitution, non-zeros of U}.
+struct StxLuEntry { int row, col; double v; };
+constexpr int STX_LU_MAX_N = 16384;
+int stx_lu_device(stx_ctx* ctx, int n, const StxLuEntry* entries, size_t count, double* x, double out[3]);
 // seam finding (stx_seams.hip, stx_seams_host.cpp) ----------------------------------------------------------------------------------
 // a pair of one level: masks i (m1) and j (m2) with their strides and sizes, the window's top-left in each image (roi - gap - corner),
 // window ww x wh, roi rw x rh (at (gap, gap) of the window), off: the pair's u16 distances in the level's arena (mask i's wh x rw plane,

@@ -1,6 +1,6 @@
-// stx_modes.cpp — the three process-wide arithmetic modes: which sinf / cosf the projectors follow (stx_device_math.h), the interpolation
-// model of the image samples, the pyrDown order of the fp32 weight pyramids (include/stitching_amd.h).  Process-wide like the libm they
-// stand for; each is initialised from its environment variable on first use and set by its stx_set_* call afterwards.
+// stx_modes.cpp — the process-wide modes: which sinf / cosf the projectors follow (stx_device_math.h), the interpolation
+// model of the image samples, the pyrDown order of the fp32 weight pyramids, where the exposure gain systems are solved
+// (include/stitching_amd.h).  Process-wide like the libm they stand for; each is initialised from its environment variable on first use and set by its stx_set_* call afterwards.
 #include <cstdlib>
 #include <cstring>
 
@@ -59,6 +59,15 @@ int parse_pyrdown(const char* e)
     return mode | (lanes << 8);
 }
 
+// STITCHING_AMD_EXPOSURE_SOLVER = host | device
+int parse_exposure_solver(const char* e)
+{
+    if (e && !strcmp(e, "device")) return STX_EXPOSURE_SOLVER_DEVICE;
+    if (e && *e && strcmp(e, "host")) fprintf(stderr, "[stitching_amd] STITCHING_AMD_EXPOSURE_SOLVER=%s is not one of host, device: using host\n", e);
+    return STX_EXPOSURE_SOLVER_HOST;
+}
+
+Mode g_exposure_solver{"STITCHING_AMD_EXPOSURE_SOLVER", parse_exposure_solver};
 Mode g_trig{"STITCHING_AMD_TRIG", parse_trig}, g_remap{"STITCHING_AMD_REMAP", parse_remap}, g_pyrdown{"STITCHING_AMD_PYRDOWN", parse_pyrdown};
 
 }  // namespace
@@ -66,6 +75,7 @@ Mode g_trig{"STITCHING_AMD_TRIG", parse_trig}, g_remap{"STITCHING_AMD_REMAP", pa
 int trig_mode_now() { return g_trig.now(); }
 int remap_mode_now() { return g_remap.now(); }
 int pyrdown_now() { return g_pyrdown.now(); }
+int exposure_solver_now() { return g_exposure_solver.now(); }
 
 STX_EXPORT int stx_get_trig_mode(void) { return trig_mode_now(); }
 
@@ -97,5 +107,14 @@ STX_EXPORT int stx_set_pyrdown_mode(int mode, int lanes)
     const bool known = mode == STX_PYRDOWN_SCALAR || (mode & ~STX_PYRDOWN_FMA) == STX_PYRDOWN_SIMD_V || (mode & ~STX_PYRDOWN_FMA) == STX_PYRDOWN_SIMD_HV;
     if (!known || (lanes != 4 && lanes != 8 && lanes != 16)) return stx_fail(STX_ERR_INVALID, "pyrDown mode %d, lanes %d", mode, lanes);
     g_pyrdown.v.store(mode | (lanes << 8));
+    return STX_OK;
+}
+
+STX_EXPORT int stx_get_exposure_solver(void) { return exposure_solver_now(); }
+
+STX_EXPORT int stx_set_exposure_solver(int mode)
+{
+    if (mode != STX_EXPOSURE_SOLVER_HOST && mode != STX_EXPOSURE_SOLVER_DEVICE) return stx_fail(STX_ERR_INVALID, "exposure solver %d", mode);
+    g_exposure_solver.v.store(mode);
     return STX_OK;
 }

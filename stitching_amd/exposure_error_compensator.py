@@ -13,7 +13,8 @@ fp32 gain maps (one / three channels) with cv::resize(INTER_LINEAR) inside the s
 images and hands `getMatGains()` to `set_gains` — so `Stitcher.estimate_exposure_errors` / `compensate_exposure_errors`
 (stitching/stitcher.py:210-221) work unmodified with this class in place of the reference's.  Any object with
 `feed(corners, imgs, masks)` and `getMatGains()` can be passed as `estimator=` instead.  With
-`config.set_exposure_estimator("device")` the constructor builds a `stitching_amd.ExposureEstimator` (estimation in HIP, no cv2), and
+`config.set_exposure_estimator("device")` the constructor builds a `stitching_amd.ExposureEstimator` (estimation in HIP, no cv2; its gain
+systems solved where `config.exposure_solver()` says), and
 `feed` hands it the images as they are: device images stay on the device.
 """
 import ctypes as C
@@ -62,10 +63,11 @@ class ExposureErrorCompensator:
         createDefault: one feed, 32 x 32 blocks), or None for "no"."""
         from .exposure_estimation import ExposureEstimator
 
+        solver = config.exposure_solver()  # the process-wide choice at construction, as the estimator switch itself is read here
         if compensator in ("channel", "channel_blocks"):
-            return ExposureEstimator(compensator, nr_feeds, block_size)
+            return ExposureEstimator(compensator, nr_feeds, block_size, solver=solver)
         if compensator in ("gain", "gain_blocks"):
-            return ExposureEstimator(compensator)
+            return ExposureEstimator(compensator, solver=solver)
         return None
 
     @staticmethod

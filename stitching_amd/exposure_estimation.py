@@ -2,8 +2,8 @@
 
 `ExposureEstimator` is duck-typed like the cv.detail compensators the reference builds (stitching/exposure_error_compensator.py:25-41):
 `feed(corners, imgs, masks)` on the low-resolution warped images, then `getMatGains()`.  The overlap statistics of every feed are one
-HIP launch over a table of unit pairs (csrc/stx_exposure.hip); the small linear system is assembled and solved on the host
-(csrc/stx_exposure_host.cpp).  The algorithm restates OpenCV 4.x from recollection; tests/numpy_exposure.py is the contract and fidelity to
+HIP launch over a table of unit pairs (csrc/stx_exposure.hip); the linear system is assembled on the host and solved there
+(csrc/stx_exposure_host.cpp, the default) or by a dense fp64 LU on the device (csrc/stx_solve.hip, solver="device": the same bits).  The algorithm restates OpenCV 4.x from recollection; tests/numpy_exposure.py is the contract and fidelity to
 real OpenCV is unpinned.
 """
 import ctypes as C
@@ -41,16 +41,21 @@ def _block_grid(w, h, bl):
 
 class ExposureEstimator:
     """ExposureCompensator::feed on the device.  kind: "gain" | "gain_blocks" | "channel" | "channel_blocks"; nr_feeds and
-    block_size as cv.detail_ChannelsCompensator(nr_feeds) / cv.detail_BlocksChannelsCompensator(bl, bl, nr_feeds) take them."""
+    block_size as cv.detail_ChannelsCompensator(nr_feeds) / cv.detail_BlocksChannelsCompensator(bl, bl, nr_feeds) take them.
+    solver: "host" | "device" — where the gain systems are solved; None: config.exposure_solver() at every feed."""
 
-    def __init__(self, kind, nr_feeds=1, block_size=32):
+    def __init__(self, kind, nr_feeds=1, block_size=32, solver=None):
         if kind not in _lib.EXPOSURE_KINDS:
             raise StitchingError(f"unknown exposure estimator kind {kind!r}: one of {sorted(_lib.EXPOSURE_KINDS)}")
         if int(nr_feeds) < 1 or int(block_size) < 1:
             raise StitchingError("nr_feeds and block_size must be >= 1")
-        self.kind, self.nr_feeds, self.block_size = kind, int(nr_feeds), int(block_size)
+        if solver is not None and solver not in _lib.EXPOSURE_SOLVERS:
+            raise StitchingError(f"unknown exposure solver {solver!r}: one of {sorted(_lib.EXPOSURE_SOLVERS)}")
+        self.kind, self.nr_feeds, self.block_size, self.solver = kind, int(nr_feeds), int(block_size), solver
         self.gains = []
-        self.info = None  # of the last feed: units, pair jobs, device statistics ms, host solve + filter ms
+        # of the last feed: units, pair jobs, device statistics ms, assembly + solve + filter ms (wall clock, whichever solver), the solver
+        # used and, of the device solver, elimination ms / compaction + copy + back substitution ms / non-zeros of U
+        self.info = None
 
     def _prepare(self, corners, imgs, masks):
         imgs, masks, corners = list(imgs), list(masks), [tuple(int(v) for v in c) for c in corners]
@@ -84,13 +89,18 @@ class ExposureEstimator:
         ia, ma = (C.c_void_p * n)(*[a._h for a in d_imgs]), (C.c_void_p * n)(*[a._h for a in d_masks])
         cp = cs.ctypes.data_as(C.POINTER(C.c_int))
         count = C.c_longlong(0)
-        _lib.check(ctx._lib.stx_exposure_feed(ctx.handle, kind, n, ia, ma, cp, self.block_size, self.nr_feeds, None, C.byref(count), None))
+        solver = -1 if self.solver is None else _lib.EXPOSURE_SOLVERS[self.solver]
+        _lib.check(ctx._lib.stx_exposure_feed_ex(ctx.handle, kind, n, ia, ma, cp, self.block_size, self.nr_feeds, solver, None,
+                                                 C.byref(count), None))
         out = np.zeros(max(1, count.value), np.float64)
-        info = np.zeros(4, np.float64)
-        _lib.check(ctx._lib.stx_exposure_feed(ctx.handle, kind, n, ia, ma, cp, self.block_size, self.nr_feeds,
-                                              out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(count),
-                                              info.ctypes.data_as(C.POINTER(C.c_double))))
-        self.info = {"units": int(info[0]), "pair_jobs": int(info[1]), "stats_ms": float(info[2]), "solve_ms": float(info[3])}
+        info = np.zeros(8, np.float64)
+        _lib.check(ctx._lib.stx_exposure_feed_ex(ctx.handle, kind, n, ia, ma, cp, self.block_size, self.nr_feeds, solver,
+                                                 out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(count),
+                                                 info.ctypes.data_as(C.POINTER(C.c_double))))
+        names = {v: k for k, v in _lib.EXPOSURE_SOLVERS.items()}
+        self.info = {"units": int(info[0]), "pair_jobs": int(info[1]), "stats_ms": float(info[2]), "solve_ms": float(info[3]),
+                     "solver": names[int(info[4])], "device_lu_ms": float(info[5]), "host_tail_ms": float(info[6]),
+                     "u_nonzeros": int(info[7])}
         gains, o = [], 0
         for h, w in sizes:
             if self.kind == "gain":
@@ -129,9 +139,12 @@ class ExposureEstimator:
         return ab[:k], c[:k], s[:k]
 
 
-def solve_gains(m, pairs, n_iij_iji, skip):
-    """Host only (no GPU): GainCompensator::singleFeed's assembly + cv::solve from given statistics.  pairs (P, 2) with i <= j,
-    n_iij_iji (P, 3) = N(i,j), I(i,j), I(j,i); skip (m,) bool.  -> gains (m,) float64."""
+def solve_gains(m, pairs, n_iij_iji, skip, solver="host", ctx=None):
+    """GainCompensator::singleFeed's assembly + cv::solve from given statistics.  pairs (P, 2) with i <= j,
+    n_iij_iji (P, 3) = N(i,j), I(i,j), I(j,i); skip (m,) bool.  -> gains (m,) float64.  solver "host": no GPU; "device": the
+    elimination on ctx's device (the default context when None), the same bits."""
+    if solver not in _lib.EXPOSURE_SOLVERS:
+        raise StitchingError(f"unknown exposure solver {solver!r}: one of {sorted(_lib.EXPOSURE_SOLVERS)}")
     pairs = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
     vals = np.ascontiguousarray(np.asarray(n_iij_iji, np.float64).reshape(-1, 3))
     sk = np.ascontiguousarray(np.asarray(skip, bool).astype(np.uint8).reshape(-1))
@@ -139,7 +152,30 @@ def solve_gains(m, pairs, n_iij_iji, skip):
         raise StitchingError("solve_gains: skip must hold m values and n_iij_iji one row per pair")
     out = np.zeros(max(1, m), np.float64)
     L = _lib.lib()
+    if solver == "device":
+        ctx = ctx or get_context()
+        _lib.check(L.stx_exposure_solve_device(ctx.handle, int(m), pairs.shape[0], pairs.ctypes.data_as(C.POINTER(C.c_int)),
+                                               vals.ctypes.data_as(C.POINTER(C.c_double)), sk.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                               out.ctypes.data_as(C.POINTER(C.c_double)), None))
+        return out[:m]
     _lib.check(L.stx_exposure_solve(int(m), pairs.shape[0], pairs.ctypes.data_as(C.POINTER(C.c_int)),
                                     vals.ctypes.data_as(C.POINTER(C.c_double)), sk.ctypes.data_as(C.POINTER(C.c_ubyte)),
                                     out.ctypes.data_as(C.POINTER(C.c_double))))
     return out[:m]
+
+
+def lu_solve_device(A, b, ctx=None, want_info=False):
+    """A x = b by the device LU alone (stx_lu_solve_device; tests and tools): the bits of cv::solve(DECOMP_LU)'s dense loop for every
+    n >= 1.  -> x (n,) float64, with want_info also {"device_lu_ms", "host_tail_ms", "u_nonzeros"}."""
+    A = np.ascontiguousarray(np.asarray(A, np.float64))
+    b = np.ascontiguousarray(np.asarray(b, np.float64).reshape(-1))
+    if A.ndim != 2 or A.shape[0] != A.shape[1] or A.shape[0] < 1 or b.size != A.shape[0]:
+        raise StitchingError("lu_solve_device: A must be n x n with n >= 1 and b hold n values")
+    ctx = ctx or get_context()
+    x, info = np.zeros(A.shape[0], np.float64), np.zeros(4, np.float64)
+    dp = C.POINTER(C.c_double)
+    _lib.check(ctx._lib.stx_lu_solve_device(ctx.handle, A.shape[0], A.ctypes.data_as(dp), b.ctypes.data_as(dp), x.ctypes.data_as(dp),
+                                            info.ctypes.data_as(dp)))
+    if want_info:
+        return x, {"device_lu_ms": float(info[0]), "host_tail_ms": float(info[1]), "u_nonzeros": int(info[2])}
+    return x

@@ -367,6 +367,10 @@ int stx_crop_lir(stx_ctx* ctx, const stx_buf* mask_u8x1, int out_xywh[4], int ou
  *                            one fused kernel, the result is what Blender.feed receives (stitching/stitcher.py:124,127) */
 int stx_resize_linear_exact(stx_ctx* ctx, const stx_buf* src_u8, int dst_w, int dst_h, stx_buf** out);
 int stx_seam_mask_resize(stx_ctx* ctx, const stx_buf* seam_mask_u8x1, const stx_buf* final_mask_u8x1, stx_buf** out);
+/* stx_resize_linear_exact for n images of unequal sizes (u8x1 and u8x3 mixed, views included) in one launch: the generator loop of
+ * Images.resize (stitching/images.py:72-77, stitching/stitcher.py:167-168).  dst_wh = {w, h} per image; outs[i] is byte for byte what
+ * stx_resize_linear_exact(srcs[i], w, h) returns.  n <= 0 is STX_ERR_INVALID; a failing call hands nothing out. */
+int stx_resize_linear_exact_batch(stx_ctx* ctx, int n, const stx_buf* const* srcs_u8, const int* dst_wh, stx_buf** outs);
 /* the same for all n images of a panorama (the generator loop stitching/stitcher.py:223-225): one table upload, one dilate
  * and one resize launch per 16 images */
 int stx_seam_mask_resize_batch(stx_ctx* ctx, int n, const stx_buf* const* seam_masks, const stx_buf* const* final_masks,

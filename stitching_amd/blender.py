@@ -84,26 +84,27 @@ class Blender:
         _lib.check(_lib.lib().stx_result_roi(len(c), c.ctypes.data_as(ip), s.ctypes.data_as(ip), out))
         return tuple(int(v) for v in out)
 
-    def prepare(self, corners, sizes):
-        dst_sz = Blender.result_roi(corners, sizes)
-        blend_width = np.sqrt(dst_sz[2] * dst_sz[3]) * self.blend_strength / 100
-        ctx = self.ctx or get_context()
-
-        if self.blender_type == "no" or blend_width < 1:
-            self.blender = _BlenderHandle(ctx, _lib.BLEND_NO, 0, 0.0, dst_sz)
-
-        elif self.blender_type == "multiband":
+    @staticmethod
+    def plan(blender_type, blend_strength, dst_sz):
+        """(STX_BLEND_* kind, number of bands, sharpness) of the cv.detail blender stitching/blender.py:24-38 builds for a panorama roi
+        dst_sz = (x, y, w, h): host arithmetic only"""
+        blend_width = np.sqrt(dst_sz[2] * dst_sz[3]) * blend_strength / 100
+        if blender_type == "no" or blend_width < 1:
+            return _lib.BLEND_NO, 0, 0.0
+        if blender_type == "multiband":
             num_bands = int((np.log(blend_width) / np.log(2.0) - 1.0))
             # blend_width == 1 exactly gives -1: cv2's setNumBands(-1) then shifts by a negative count in prepare()
             # (undefined behaviour in the reference); 0 bands — the single-level blend of blend_width in (1, 4) — is the limit
-            self.blender = _BlenderHandle(ctx, _lib.BLEND_MULTIBAND, max(num_bands, 0), 0.0, dst_sz)
+            return _lib.BLEND_MULTIBAND, max(num_bands, 0), 0.0
+        if blender_type == "feather":
+            return _lib.BLEND_FEATHER, 0, 1.0 / blend_width
+        # the reference leaves self.blender = None and fails on .prepare(); be explicit
+        raise StitchingError(f"unknown blender type {blender_type!r}")
 
-        elif self.blender_type == "feather":
-            self.blender = _BlenderHandle(ctx, _lib.BLEND_FEATHER, 0, 1.0 / blend_width, dst_sz)
-
-        else:
-            # the reference leaves self.blender = None and fails on .prepare(); be explicit
-            raise StitchingError(f"unknown blender type {self.blender_type!r}")
+    def prepare(self, corners, sizes):
+        dst_sz = Blender.result_roi(corners, sizes)
+        kind, num_bands, sharpness = Blender.plan(self.blender_type, self.blend_strength, dst_sz)
+        self.blender = _BlenderHandle(self.ctx or get_context(), kind, num_bands, sharpness, dst_sz)
 
     def feed(self, img, mask, corner):
         if self.blender is None:
@@ -125,7 +126,9 @@ class Blender:
 
     @classmethod
     def create_panorama(cls, imgs, masks, corners, sizes):
-        blender = cls("no")
+        imgs, masks = list(imgs), list(masks)
+        # device images: on their own context (the blender's launches then follow the stream that made them)
+        blender = cls("no", ctx=next((a.ctx for a in masks + imgs if isinstance(a, DeviceImage)), None))
         blender.prepare(corners, sizes)
         for img, mask, corner in zip(imgs, masks, corners):
             blender.feed(img, mask, corner)

@@ -1535,13 +1535,11 @@ STX_DEV uint32_t resize_src(const ResizeK& P, int x, int y, int ch)
         }
     return m;
 }
+// one destination pixel (x, y) from its table entries tx / ty = (offset, coeff1 | interior << 16): the body of the single-image and of
+// the batched kernel
 template <int C, bool DILATE>
-__global__ __launch_bounds__(256) void resize_exact_kernel(ResizeK P)
+STX_DEV void resize_exact_pixel(const ResizeK& P, int x, int y, int2 tx, int2 ty)
 {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= P.dw || y >= P.dh) return;
-    const int2 tx = P.xt[x], ty = P.yt[y];
     const int ox = tx.x, oy = ty.x;
     const uint32_t cx1 = (uint32_t)tx.y & 0xffffu, cx0 = 256u - cx1, cy1 = (uint32_t)ty.y & 0xffffu, cy0 = 256u - cy1;
     const bool iy = (ty.y >> 16) != 0;
@@ -1560,6 +1558,14 @@ __global__ __launch_bounds__(256) void resize_exact_kernel(ResizeK P)
         if (P.andmask) v &= P.andmask[(long long)y * P.amstride + x];
         P.dst[(long long)y * P.dstride + x * C + ch] = (uint8_t)v;
     }
+}
+template <int C, bool DILATE>
+__global__ __launch_bounds__(256) void resize_exact_kernel(ResizeK P)
+{
+    const int x = blockIdx.x * STX_RESIZE_TW + (threadIdx.x & 63);
+    const int y = blockIdx.y * STX_RESIZE_TH + (threadIdx.x >> 6);
+    if (x >= P.dw || y >= P.dh) return;
+    resize_exact_pixel<C, DILATE>(P, x, y, P.xt[x], P.yt[y]);
 }
 }  // namespace
 
@@ -1878,7 +1884,7 @@ int stx_launch_resize_exact(stx_ctx* ctx, const stx_buf* src, stx_buf* dst, cons
     K.dst = dst->ptr; K.dstride = (long long)dst->stride; K.dw = dst->w; K.dh = dst->h;
     K.xt = (const int2*)d_xt; K.yt = (const int2*)d_yt;
     K.andmask = andmask ? andmask->ptr : nullptr; K.amstride = andmask ? (long long)andmask->stride : 0;
-    const dim3 grid((dst->w + 63) / 64, (dst->h + 3) / 4);
+    const dim3 grid((dst->w + STX_RESIZE_TW - 1) / STX_RESIZE_TW, (dst->h + STX_RESIZE_TH - 1) / STX_RESIZE_TH);
     StxProfScope prof(ctx, dilate ? "seam_mask_resize" : "resize_linear_exact", (double)src->w * src->h * src->c + (double)dst->w * dst->h * dst->c * (andmask ? 2 : 1));
     // dword access to the destination and to the final mask: 4-byte aligned rows (every stx_buf_new image; views may not be),
     // and the mask rows must be readable up to the next multiple of 4 columns
@@ -1897,6 +1903,46 @@ int stx_launch_resize_exact(stx_ctx* ctx, const stx_buf* src, stx_buf* dst, cons
     else if (src->c == 3) hipLaunchKernelGGL((resize_exact_kernel<3, false>), grid, dim3(256), 0, ctx->stream, K);
     else return stx_fail(STX_ERR_UNSUPPORTED, "resize: 1 or 3 channels");
     return check_launch("resize_linear_exact");
+}
+
+// ---------------------------------------------------------------------------------------------
+// cv::resize(INTER_LINEAR_EXACT) of n images of unequal sizes as ONE launch (the LOW pass of Images.resize: 64 frames -> 0.1 Mpx is 64
+// launches, table uploads and allocations of a kernel that runs a few microseconds).  The grid is the flat list of the destination
+// tiles of all images, image after image: a workgroup finds its image by bisecting the descriptors' first-tile numbers (uniform over
+// the workgroup: scalar loads), so no workgroup exists for an image smaller than the largest.  A tile is the single-image kernel's:
+// 64 adjacent pixels of a row per wavefront (a row segment leaves as 64 or 192 contiguous bytes), 4 rows per workgroup.  Nothing but
+// the descriptors is uploaded: a lane makes its own two coefficients with the IEEE double operations of the host table (seam1_coeff,
+// as the one-launch seam-mask resize does) and hands them to the single-image kernel's pixel body.
+// ---------------------------------------------------------------------------------------------
+namespace {
+__global__ __launch_bounds__(256) void resize_exact_batch_kernel(const StxResizeItem* __restrict__ items, int n)
+{
+    const int tile = blockIdx.x;
+    int lo = 0, hi = n - 1;  // the last image whose first tile is <= tile (tile0 is ascending, items[0].tile0 = 0)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (items[mid].tile0 <= tile) lo = mid; else hi = mid - 1;
+    }
+    const StxResizeItem& D = items[lo];
+    const int t = tile - D.tile0, tyi = t / D.tiles_x, txi = t - tyi * D.tiles_x;
+    const int x = txi * STX_RESIZE_TW + (threadIdx.x & 63);
+    const int y = tyi * STX_RESIZE_TH + (threadIdx.x >> 6);
+    if (x >= D.dw || y >= D.dh) return;
+    ResizeK P;
+    P.src = D.src; P.sstride = D.sstride; P.sw = D.sw; P.sh = D.sh;
+    P.dst = D.dst; P.dstride = D.dstride; P.dw = D.dw; P.dh = D.dh;
+    P.xt = nullptr; P.yt = nullptr; P.andmask = nullptr; P.amstride = 0;
+    const int2 tx = seam1_coeff(x, D.xscale, D.sw), ty = seam1_coeff(y, D.yscale, D.sh);
+    if (D.c == 3) resize_exact_pixel<3, false>(P, x, y, tx, ty);
+    else resize_exact_pixel<1, false>(P, x, y, tx, ty);
+}
+}  // namespace
+
+int stx_launch_resize_exact_batch(stx_ctx* ctx, const StxResizeItem* d_items, int n, int total_tiles, double algo_bytes)
+{
+    StxProfScope prof(ctx, "resize_linear_exact_batch", algo_bytes);
+    hipLaunchKernelGGL(resize_exact_batch_kernel, dim3(total_tiles), dim3(256), 0, ctx->stream, d_items, n);
+    return check_launch("resize_linear_exact_batch");
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -277,6 +277,15 @@ int stx_launch_seam_level(stx_ctx* ctx, const StxSeamPair* d_pairs, int np, int 
 // cv::resize(INTER_LINEAR_EXACT) u8 (next rows N2 / N3); d_xt / d_yt: device tables of (offset, coeff1 | interior << 16)
 int stx_launch_resize_exact(stx_ctx* ctx, const stx_buf* src, stx_buf* dst, const int* d_xt, const int* d_yt, bool dilate,
                             const stx_buf* andmask);
+// the same for n images in one launch: device descriptors, one per image; the grid is the flat list of their STX_RESIZE_TW x
+// STX_RESIZE_TH destination tiles (tile0: the image's first, ascending; tiles_x: tiles per tile row)
+constexpr int STX_RESIZE_TW = 64, STX_RESIZE_TH = 4;
+struct StxResizeItem {
+    const uint8_t* src; long long sstride; uint8_t* dst; long long dstride;
+    int sw, sh, dw, dh, c, tiles_x, tile0, pad_;
+    double xscale, yscale;  // 1 / (dw / sw), 1 / (dh / sh) in double, as linear_exact_table takes them
+};
+int stx_launch_resize_exact_batch(stx_ctx* ctx, const StxResizeItem* d_items, int n, int total_tiles, double algo_bytes);
 
 int stx_launch_seam_resize_batch(stx_ctx* ctx, int n, const stx_buf* const* seams, const stx_buf* const* masks, stx_buf* const* dsts,
                                  const int* const* d_xt, const int* const* d_yt, uint8_t* const* tmp, const size_t* tstride);

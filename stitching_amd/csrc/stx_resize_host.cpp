@@ -177,6 +177,45 @@ STX_EXPORT int stx_resize_linear_exact(stx_ctx* ctx, const stx_buf* src, int dst
     return resize_impl(ctx, src, dst_w, dst_h, false, nullptr, out);
 }
 
+// Images.resize for a list of images: one descriptor upload through the pinned ring, one launch.  Everything is checked before anything
+// is allocated or launched; a failing call hands nothing out.
+STX_EXPORT int stx_resize_linear_exact_batch(stx_ctx* ctx, int n, const stx_buf* const* srcs, const int* dst_wh, stx_buf** outs)
+{
+    if (!ctx || !srcs || !dst_wh || !outs) return stx_fail(STX_ERR_INVALID, "null argument");
+    if (n <= 0) return stx_fail(STX_ERR_INVALID, "resize of %d images", n);
+    STX_TRY(stx_set_device(ctx));
+    std::vector<StxResizeItem> items((size_t)n);
+    long long tiles = 0;
+    double bytes = 0.0;
+    for (int i = 0; i < n; i++) {
+        const stx_buf* src = srcs[i];
+        if (!src) return stx_fail(STX_ERR_INVALID, "null argument");
+        const int dw = dst_wh[2 * i], dh = dst_wh[2 * i + 1];
+        if (src->elem != STX_U8 || (src->c != 1 && src->c != 3)) return stx_fail(STX_ERR_UNSUPPORTED, "resize needs a u8x1 or u8x3 image");
+        if (dw <= 0 || dh <= 0) return stx_fail(STX_ERR_INVALID, "resize to %dx%d", dw, dh);
+        if (src->ctx->device != ctx->device) return stx_fail(STX_ERR_INVALID, "image lives on another device");
+        StxResizeItem& K = items[i];
+        K = StxResizeItem{};
+        K.src = src->ptr; K.sstride = (long long)src->stride; K.sw = src->w; K.sh = src->h; K.dw = dw; K.dh = dh; K.c = src->c;
+        K.xscale = 1.0 / ((double)dw / (double)src->w); K.yscale = 1.0 / ((double)dh / (double)src->h);
+        K.tiles_x = (dw + STX_RESIZE_TW - 1) / STX_RESIZE_TW;
+        K.tile0 = (int)tiles;
+        tiles += (long long)K.tiles_x * ((dh + STX_RESIZE_TH - 1) / STX_RESIZE_TH);
+        if (tiles > 0x7fffffffLL) return stx_fail(STX_ERR_INVALID, "resize batch of more than 2^31 destination tiles");
+        bytes += (double)dw * dh * src->c * 5.0;  // four taps and the result
+    }
+    std::vector<StxBufRef> dsts((size_t)n);
+    for (int i = 0; i < n; i++) {
+        STX_TRY(stx_buf_new(ctx, items[i].dw, items[i].dh, items[i].c, STX_U8, &dsts[i]));
+        items[i].dst = dsts[i]->ptr; items[i].dstride = (long long)dsts[i]->stride;
+    }
+    StxDevBlock d_items;
+    STX_TRY(upload_small(ctx, items.data(), items.size() * sizeof(StxResizeItem), &d_items));
+    STX_TRY(stx_launch_resize_exact_batch(ctx, (const StxResizeItem*)d_items.get(), n, (int)tiles, bytes));
+    for (int i = 0; i < n; i++) outs[i] = dsts[i].release();
+    return STX_OK;  // the descriptor block goes back here: stream-ordered reuse
+}
+
 STX_EXPORT int stx_seam_mask_resize(stx_ctx* ctx, const stx_buf* seam_mask, const stx_buf* final_mask, stx_buf** out)
 {
     if (!ctx || !seam_mask || !final_mask || !out) return stx_fail(STX_ERR_INVALID, "null argument");

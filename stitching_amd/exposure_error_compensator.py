@@ -52,6 +52,8 @@ class ExposureErrorCompensator:
         self._dev_gains = {}  # (context, image index) -> (DeviceImage of the gain map, STX_GAIN_MAP_BOUNDED flag): uploaded once
         if estimator is not None:
             self.compensator = estimator
+        elif compensator == "no":  # estimates nothing: feed() returns at once, and nothing looks for cv2
+            self.compensator = None
         elif config.exposure_estimator() == "device":
             self.compensator = self._device_estimator(compensator, nr_feeds, block_size)
         else:

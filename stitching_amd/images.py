@@ -25,7 +25,7 @@ import numpy as np
 
 from . import config
 from .device import DeviceImage, get_context, pinned_empty
-from .seam_finder import resize_linear_exact
+from .seam_finder import resize_linear_exact, resize_linear_exact_all
 from .stitching_error import StitchingError
 
 
@@ -153,8 +153,24 @@ class Images:
     def resize(self, resolution, imgs=None):
         """generator, stitching/images.py:72-77: every image at `resolution` (cv.resize INTER_LINEAR_EXACT, on the device)"""
         scaler = self._get_scaler(resolution)
+        if config.device_resident():
+            batch = self._items if imgs is None and not self._from_files else imgs  # loaded images: the list is in hand
+            # one launch needs one context: a list that mixes contexts keeps the per-image path (each image on its own)
+            if isinstance(batch, (list, tuple)) and batch and len({id(i.ctx) for i in batch if isinstance(i, DeviceImage)}) <= 1:
+                yield from self._resize_list(scaler, batch)
+                return
         for k, img in enumerate(self if imgs is None else imgs):
             yield Images.resize_img_by_scaler(scaler, self._dims[k], img)
+
+    def _resize_list(self, scaler, imgs):
+        """device residency, a list in hand: every image that changes size in one launch (stx_resize_linear_exact_batch), made when
+        the first result is asked for"""
+        want = [scaler.get_scaled_img_size(self._dims[k]) for k in range(len(imgs))]
+        todo = [k for k, img in enumerate(imgs) if want[k] != Images.get_image_size(img)]
+        ctx = next((i.ctx for i in imgs if isinstance(i, DeviceImage)), None)
+        done = dict(zip(todo, resize_linear_exact_all([imgs[k] for k in todo], [want[k] for k in todo], ctx=ctx, device_resident=True))) if todo else {}
+        for k, img in enumerate(imgs):
+            yield done[k] if k in done else Images.resize_img_by_scaler(scaler, self._dims[k], img, device_resident=True)
 
     def _note_size(self, k, size):
         """item k is `size` pixels: the first size ever seen fixes the three scales (stitching/images.py:79-83, 190-201)"""

@@ -13,7 +13,12 @@ import numpy as np
 
 from . import _lib, config
 from .blender import Blender
+from .cropper import Cropper
 from .device import as_device, get_context
+from .exposure_error_compensator import ExposureErrorCompensator
+from .images import Images
+from .seam_estimation import SeamEstimator
+from .seam_finder import DEVICE_SEAM_FINDERS, SeamFinder
 from .stitching_error import StitchingError
 from .synthetic import blend_strength_for_bands
 from .warper import Warper
@@ -78,12 +83,31 @@ def view_rects(handle, corners, sizes, boxes, min_gain=0.9):
     return None if all(o is None for o in out) else out
 
 
+def clip_rectangle(rect, width, height):
+    """(x0, x1, y0, y1) of what `Cropper.crop_rectangle(img, rect)` — img[rect.y:rect.y2, rect.x:rect.x2] — keeps of a width x height
+    image: numpy's slice rules (ends clipped to the image, negative indices counted from the far end, never a negative extent)."""
+    x0, x1, _ = slice(rect.x, rect.x2).indices(int(width))
+    y0, y1, _ = slice(rect.y, rect.y2).indices(int(height))
+    return x0, max(x1, x0), y0, max(y1, y0)
+
+
+def _split_cropper(cropper, crop_aspect):
+    """cropper= takes a prepared Cropper (its aspect in crop_aspect=) or the pair (cropper, lir_aspect); a Cropper(False) crops nothing"""
+    if isinstance(cropper, (tuple, list)):
+        cropper, crop_aspect = cropper
+    if cropper is not None and not cropper.do_crop:
+        cropper = None
+    if cropper is not None and not getattr(cropper, "intersection_rectangles", None):
+        raise StitchingError("the cropper is not prepared: Cropper.prepare(imgs, masks, corners, sizes) on the low-resolution warps comes first")
+    return cropper, crop_aspect
+
+
 class StitchJob:
     """Pre-staged inputs of one panorama: device-resident source frames + cameras."""
 
     def __init__(self, frames, cameras, warper_type="spherical", blender_type="multiband", num_bands=None,
                  blend_strength=Blender.DEFAULT_BLEND_STRENGTH, ctx=None, async_upload=False, feed_masks=None, seam_masks=None,
-                 crop_to_masks=True, compensator=None):
+                 crop_to_masks=True, compensator=None, cropper=None, crop_aspect=1, camera_aspect=1):
         """async_upload: numpy frames in page-locked memory (pinned_empty) are only queued for upload; they must stay
         untouched until ctx.sync() (a streaming caller alternates two contexts).
         feed_masks: final-resolution u8 masks fed to the blender instead of the warped masks (seam masks already at the
@@ -96,7 +120,15 @@ class StitchJob:
         are warped, masked and fed — the same panorama bit for bit (`view_rects`).
         compensator: an ExposureErrorCompensator with its gains set (the low-resolution pass made them): applied to the warped
         images between warp and feed (stitching/stitcher.py:123,219-221) — all images in one batched launch; on cropped images the
-        gain maps are laid over the whole warped image (the rectangle's offset travels with it)."""
+        gain maps are laid over the whole warped image (the rectangle's offset travels with it).
+        cropper: a prepared Cropper (Cropper.prepare on the low-resolution warps) with crop_aspect= its lir_aspect, or the pair (cropper,
+        lir_aspect): stitching/stitcher.py:119-121,198-208 — only intersection_rectangles[i].times(crop_aspect) of every warped image
+        is warped, clipped as Cropper.crop_rectangle's slice clips it, and the blender is prepared on crop_rois(corners, sizes,
+        crop_aspect): byte for byte "warp whole, Cropper.crop_images, feed".  feed_masks / seam_masks then belong to the CROPPED images,
+        and the block compensators' gain maps lie over the cropped image (apply on a cropped image, as in the reference) — a seam-cell
+        crop inside it carries its offset in the cropped image.
+        camera_aspect: the frames are camera_aspect times the size the cameras were estimated on (Warper's `aspect`)."""
+        cropper, crop_aspect = _split_cropper(cropper, crop_aspect)
         if len(frames) != len(cameras) or not frames:
             raise StitchingError("need one camera per frame and at least one frame")
         self.ctx = ctx or get_context()
@@ -110,7 +142,10 @@ class StitchJob:
         self.num_bands = num_bands
         self.blend_strength = blend_strength
         self.corners = self.warped_sizes = None
-        self._cam_arrays = self.warper.camera_arrays(self.cameras)  # K, R as the batched entry points take them: built once
+        self.cropper, self.crop_aspect, self.camera_aspect = cropper, crop_aspect, camera_aspect
+        if cropper is not None and len(cropper.intersection_rectangles) != len(self.frames):
+            raise StitchingError(f"the cropper was prepared on {len(cropper.intersection_rectangles)} images, the job has {len(self.frames)}")
+        self._cam_arrays = self.warper.camera_arrays(self.cameras, camera_aspect)  # K, R as the batched entry points take them: built once
         # per mask the columns [a, b) and rows [c, d) that hold a non-zero value, and the mask's size (host arrays only: no
         # read-back here)
         self._mask_cols = None
@@ -127,7 +162,7 @@ class StitchJob:
 
     def plan(self):
         """Eager ROI pass (stitching/stitcher.py:188 warp_rois is eager too); one device sync."""
-        self._adopt(*self.warper.warp_rois(self.sizes, self.cameras, camera_arrays=self._cam_arrays))
+        self._adopt(*self.warper.warp_rois(self.sizes, self.cameras, self.camera_aspect, camera_arrays=self._cam_arrays))
         return self.corners, self.warped_sizes
 
     def _adopt(self, corners, warped_sizes):
@@ -140,11 +175,11 @@ class StitchJob:
             roi = Blender.result_roi(self.corners, self.warped_sizes)
             self.blend_strength = blend_strength_for_bands(self.num_bands, roi[2], roi[3])
 
-    def _crop_rects(self, handle):
+    def _crop_rects(self, handle, corners, sizes):
         """see view_rects"""
-        key = (tuple(self.corners), tuple(self.warped_sizes), self.blend_strength)
+        key = (tuple(corners), tuple(sizes), self.blend_strength)
         if self._crop_cache is None or self._crop_cache[0] != key:
-            self._crop_cache = (key, view_rects(handle, self.corners, self.warped_sizes, self._mask_cols))
+            self._crop_cache = (key, view_rects(handle, corners, sizes, self._mask_cols))
         return self._crop_cache[1]
 
     def run(self):
@@ -156,10 +191,12 @@ class StitchJob:
         prev = config.device_resident()
         config.set_device_resident(True)
         try:
+            if self.cropper is not None:
+                return self._run_cropped()
             warped = None
             if self._mask_cols is None:
-                warped = self.warper.warp_images_and_masks(self.frames, self.cameras, compensator=self.compensator, with_rois=True,
-                                                           camera_arrays=self._cam_arrays)
+                warped = self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect, compensator=self.compensator,
+                                                           with_rois=True, camera_arrays=self._cam_arrays)
                 self._adopt([r[0:2] for r in warped[2]], [r[2:4] for r in warped[2]])
             else:
                 self.plan()
@@ -167,28 +204,24 @@ class StitchJob:
             blender.prepare(self.corners, self.warped_sizes)
             crop = None
             if self._mask_cols is not None and blender.blender.kind == _lib.BLEND_MULTIBAND:
-                crop = self._crop_rects(blender.blender)
+                crop = self._crop_rects(blender.blender, self.corners, self.warped_sizes)
             if crop is not None:
                 box = [c if c is not None else (0, w, 0, h) for c, (w, h) in zip(crop, self.warped_sizes)]
                 rects = [(cx + x0, cy + y0, x1 - x0, y1 - y0) for (x0, x1, y0, y1), (cx, cy) in zip(box, self.corners)]
-                imgs, masks, rois = self.warper.warp_images_and_masks(self.frames, self.cameras, rects=rects, compensator=self.compensator,
-                                                                      camera_arrays=self._cam_arrays)
+                imgs, masks, rois = self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect, rects=rects,
+                                                                      compensator=self.compensator, camera_arrays=self._cam_arrays)
                 if self.feed_masks is not None:
                     masks = [m[y0:y1, x0:x1] for m, (x0, x1, y0, y1) in zip(self.feed_masks, box)]
                 else:
-                    from .seam_finder import SeamFinder
-
                     masks = SeamFinder.resize_all(self.seam_masks, masks,
                                                   sub=[(w, h, x0, y0) for (x0, x1, y0, y1), (w, h) in zip(box, self.warped_sizes)])
                 corners = [(r[0], r[1]) for r in rects]
             else:
-                imgs, masks, rois = warped or self.warper.warp_images_and_masks(self.frames, self.cameras, compensator=self.compensator,
-                                                                                camera_arrays=self._cam_arrays)
+                imgs, masks, rois = warped or self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect,
+                                                                                compensator=self.compensator, camera_arrays=self._cam_arrays)
                 if self.feed_masks is not None:
                     masks = self.feed_masks
                 elif self.seam_masks is not None:
-                    from .seam_finder import SeamFinder
-
                     masks = SeamFinder.resize_all(self.seam_masks, masks)
                 corners = self.corners
                 for roi, corner in zip(rois, self.corners):
@@ -203,9 +236,51 @@ class StitchJob:
             config.set_device_resident(prev)
         return pano, pmask
 
+    def _run_cropped(self):
+        """run() with a cropper (device residency is on): the ROI pass first, then only the cropper's rectangle of every image — and
+        inside it, with host seam masks and the multi-band blender, only what the seam cell can reach (view_rects)."""
+        self.plan()
+        cuts = [clip_rectangle(r.times(self.crop_aspect), w, h) for r, (w, h) in zip(self.cropper.intersection_rectangles, self.warped_sizes)]
+        cut_sizes = [(x1 - x0, y1 - y0) for x0, x1, y0, y1 in cuts]
+        if any(w <= 0 or h <= 0 for w, h in cut_sizes):
+            raise StitchingError(f"the cropper leaves nothing of a warped image (sizes {cut_sizes}): it was prepared for another panorama")
+        # what the reference prepares its blender on (crop_rois); the images it feeds are the slices above, which rounding may leave a
+        # pixel larger or smaller
+        corners, sizes = self.cropper.crop_rois(self.corners, self.warped_sizes, self.crop_aspect)
+        corners, sizes = [tuple(c) for c in corners], [tuple(z) for z in sizes]
+        roi = Blender.result_roi(corners, sizes)
+        if self.num_bands is not None:
+            self.blend_strength = blend_strength_for_bands(self.num_bands, roi[2], roi[3])
+        # the reference's order: warp, then Blender.prepare (stitching/stitcher.py:118-126).  What the seam-cell crops need of the
+        # blender beforehand is its geometry alone: a blender without a device (view_rects)
+        crop = None
+        kind, bands, _ = Blender.plan(self.blender_type, self.blend_strength, roi)
+        if self._mask_cols is not None and kind == _lib.BLEND_MULTIBAND and cut_sizes == sizes:
+            from .distributed import make_shard_blender
+
+            crop = self._crop_rects(make_shard_blender(None, roi, bands), corners, sizes)
+        box = [c if crop is not None and c is not None else (0, w, 0, h) for c, (w, h) in zip(crop or [None] * len(cuts), cut_sizes)]
+        rects = [(cx + c[0] + x0, cy + c[2] + y0, x1 - x0, y1 - y0) for (x0, x1, y0, y1), c, (cx, cy) in zip(box, cuts, self.corners)]
+        imgs, masks, _ = self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect, rects=rects,
+                                                           camera_arrays=self._cam_arrays)
+        sub = None if crop is None else [(w, h, x0, y0) for (x0, x1, y0, y1), (w, h) in zip(box, cut_sizes)]
+        if self.compensator is not None:  # over the CROPPED image (apply on a crop); a seam-cell rectangle carries its offset in it
+            imgs = self.compensator.apply_all(corners, imgs, None, sub=sub, ctx=self.ctx)
+        if self.feed_masks is not None:
+            masks = [m if b == (0, m.width, 0, m.height) else m[b[2]:b[3], b[0]:b[1]] for m, b in zip(self.feed_masks, box)]
+        elif self.seam_masks is not None:
+            masks = SeamFinder.resize_all(self.seam_masks, masks, sub=sub)
+        self.last_crop = crop
+        blender = Blender(self.blender_type, self.blend_strength, ctx=self.ctx)
+        blender.prepare(corners, sizes)
+        for img, mask, (cx, cy), b in zip(imgs, masks, corners, box):
+            blender.feed(img, mask, (cx + b[0], cy + b[2]))
+        self.last_num_bands = blender.blender.num_bands()
+        return blender.blend()
+
 
 def compose(frames, cameras, warper_type="spherical", blender_type="multiband", blend_strength=Blender.DEFAULT_BLEND_STRENGTH,
-            compensator=None, seam_masks=None, ctx=None):
+            compensator=None, seam_masks=None, ctx=None, cropper=None, crop_aspect=1, camera_aspect=1):
     """The final-resolution half of Stitcher.stitch (stitching/stitcher.py:117-128) with every intermediate in HBM:
 
         warp_final_resolution_imgs / masks   (:119-121, Warper)            -> one batched warp
@@ -215,23 +290,32 @@ def compose(frames, cameras, warper_type="spherical", blender_type="multiband", 
 
     `compensator`: an ExposureErrorCompensator with set_gains() done, or None; `seam_masks`: low-resolution seam
     masks (one per image, e.g. from cv2's seam finder), or None for the full warped masks.
+    `cropper`: a prepared Cropper with `crop_aspect` its lir_aspect (or the pair of both): crop_final_resolution (:119-121) — only the
+    cropper's rectangles are warped (StitchJob); compensator gains and seam masks then belong to the cropped images.
+    `camera_aspect`: the size of the frames relative to the images the cameras were estimated on.
     Returns device-resident (panorama u8x3, mask u8)."""
     ctx = ctx or get_context()
+    cropper, crop_aspect = _split_cropper(cropper, crop_aspect)
+    if cropper is not None:
+        if seam_masks is not None and blender_type == "multiband":
+            seam_masks = [np.asarray(m.get() if hasattr(m, "get") else m) for m in seam_masks]
+        return StitchJob(frames, cameras, warper_type=warper_type, blender_type=blender_type, blend_strength=blend_strength, ctx=ctx,
+                         seam_masks=seam_masks, compensator=compensator, cropper=cropper, crop_aspect=crop_aspect,
+                         camera_aspect=camera_aspect).run()
     if seam_masks is not None and blender_type == "multiband":
         # nothing between the warp and the blender needs whole images (the gain of a pixel depends on its position alone): warp,
         # compensate and feed only what the seam cells can reach
         return StitchJob(frames, cameras, warper_type=warper_type, blender_type=blender_type, blend_strength=blend_strength, ctx=ctx,
-                         seam_masks=[np.asarray(m.get() if hasattr(m, "get") else m) for m in seam_masks], compensator=compensator).run()
+                         seam_masks=[np.asarray(m.get() if hasattr(m, "get") else m) for m in seam_masks], compensator=compensator,
+                         camera_aspect=camera_aspect).run()
     prev = config.device_resident()
     config.set_device_resident(True)
     try:
         warper = Warper(warper_type, ctx=ctx)
         warper.set_scale(cameras)
-        imgs, masks, rois = warper.warp_images_and_masks([as_device(f, ctx) for f in frames], cameras, compensator=compensator)
+        imgs, masks, rois = warper.warp_images_and_masks([as_device(f, ctx) for f in frames], cameras, camera_aspect, compensator=compensator)
         corners, sizes = [r[0:2] for r in rois], [r[2:4] for r in rois]
         if seam_masks is not None:
-            from .seam_finder import SeamFinder
-
             masks = SeamFinder.resize_all(seam_masks, masks)
         blender = Blender(blender_type, blend_strength, ctx=ctx)
         blender.prepare(corners, sizes)
@@ -240,6 +324,134 @@ def compose(frames, cameras, warper_type="spherical", blender_type="multiband", 
         return blender.blend()
     finally:
         config.set_device_resident(prev)
+
+
+class ComposePlan:
+    """What the low-resolution half of a composition leaves (Composer.prepare), device-resident: the prepared cropper, the compensator
+    with its gains, the low-resolution seam masks and the scales.  Valid for every set of frames of the same rig (same sizes, same
+    cameras): Composer.run(plan, images=new_frames)."""
+
+    def __init__(self, images, frames, cameras, warper_scale, cropper, compensator, seam_masks, seam_masks_host, low_corners, low_sizes):
+        self.images, self.frames, self.cameras, self.warper_scale = images, frames, list(cameras), warper_scale
+        self.cropper, self.compensator, self.seam_masks, self.seam_masks_host = cropper, compensator, seam_masks, seam_masks_host
+        self.low_corners, self.low_sizes = low_corners, low_sizes
+        self.frame_sizes = images.sizes
+        R = Images.Resolution
+        self.camera_aspect = images.get_ratio(R.MEDIUM, R.FINAL)
+        self.lir_aspect = images.get_ratio(R.LOW, R.FINAL)
+
+    def check_frames(self, frames):
+        got = [Images.get_image_size(f) for f in frames]
+        if got != [tuple(z) for z in self.frame_sizes]:
+            raise StitchingError(f"the plan was prepared for frames of sizes {self.frame_sizes}, got {got}: same rig, same sizes")
+
+
+class Composer:
+    """Cameras in, panorama out: both halves of Stitcher.stitch after estimate_scale (stitching/stitcher.py:106-128) with every
+    intermediate in HBM.  `prepare` is the low-resolution half (:108-115: resize to LOW, warp, Cropper.prepare and crop,
+    ExposureErrorCompensator.feed, SeamFinder.find), `run` the final one (:117-128, a StitchJob), `compose` both.  The keywords are the
+    reference's Stitcher.DEFAULT_SETTINGS where they apply; `cameras` are at MEDIUM scale, as the reference's registration leaves them.
+    Exposure gains and the "voronoi" / "no" seams are estimated on the device whatever the process-wide estimator settings are (nothing
+    imports cv2); the "dp_*" and "gc_*" finders are cv2's, through SeamFinder.  The subset step (Images.subset) is the caller's: pass
+    the images registration kept."""
+
+    DEFAULT_SETTINGS = {
+        "medium_megapix": Images.Resolution.MEDIUM.value,
+        "warper_type": Warper.DEFAULT_WARP_TYPE,
+        "low_megapix": Images.Resolution.LOW.value,
+        "crop": Cropper.DEFAULT_CROP,
+        "compensator": ExposureErrorCompensator.DEFAULT_COMPENSATOR,
+        "nr_feeds": ExposureErrorCompensator.DEFAULT_NR_FEEDS,
+        "block_size": ExposureErrorCompensator.DEFAULT_BLOCK_SIZE,
+        "finder": SeamFinder.DEFAULT_SEAM_FINDER,
+        "final_megapix": Images.Resolution.FINAL.value,
+        "blender_type": Blender.DEFAULT_BLENDER,
+        "blend_strength": Blender.DEFAULT_BLEND_STRENGTH,
+    }
+
+    def __init__(self, ctx=None, **kwargs):
+        for arg in kwargs:
+            if arg not in self.DEFAULT_SETTINGS:
+                raise StitchingError("Invalid Argument: " + arg)
+        self.settings = dict(self.DEFAULT_SETTINGS, **kwargs)
+        self.ctx = ctx
+        st = self.settings
+        if st["finder"] not in SeamFinder.SEAM_FINDER_CHOICES:
+            raise StitchingError(f"unknown seam finder {st['finder']!r}")
+        if st["compensator"] not in ExposureErrorCompensator.COMPENSATOR_CHOICES:
+            raise StitchingError(f"unknown compensator {st['compensator']!r}")
+        if st["warper_type"] not in Warper.WARP_TYPE_CHOICES:
+            raise StitchingError(f"unknown warper type {st['warper_type']!r}")
+        if st["blender_type"] not in Blender.BLENDER_CHOICES:
+            raise StitchingError(f"unknown blender type {st['blender_type']!r}")
+        if st["medium_megapix"] < st["low_megapix"]:
+            raise StitchingError("Medium resolution megapix need to be greater or equal than low resolution megapix")
+
+    def _ctx(self):
+        return self.ctx or get_context()
+
+    def prepare(self, images, cameras):
+        """The low-resolution half -> ComposePlan.  The host waits for the device where a result decides what is launched next: the ROI
+        pass of the warp, the cropper's rectangle, the gain solve (and the read-back of the seam masks for the multi-band blender's
+        seam-cell crops)."""
+        st, ctx = self.settings, self._ctx()
+        frames, cameras = list(images), list(cameras)
+        if len(frames) != len(cameras):
+            raise StitchingError("need one camera per image")
+        frames = [as_device(f, ctx) for f in frames]  # on THIS context: every later stage follows its images' context
+        imgs_obj = Images.of(frames, st["medium_megapix"], st["low_megapix"], st["final_megapix"])
+        R = Images.Resolution
+        prev = config.device_resident()
+        config.set_device_resident(True)
+        try:
+            medium = list(imgs_obj.resize(R.MEDIUM))
+            low = list(imgs_obj.resize(R.LOW, medium))  # from the MEDIUM images, as stitcher.py:108 does
+            warper = Warper(st["warper_type"], ctx=ctx)
+            warper.set_scale(cameras)
+            aspect = imgs_obj.get_ratio(R.MEDIUM, R.LOW)
+            imgs, masks, rois = warper.warp_images_and_masks(low, cameras, aspect)
+            corners, sizes = [r[0:2] for r in rois], [r[2:4] for r in rois]
+            cropper = Cropper(st["crop"])
+            cropper.prepare(imgs, masks, corners, sizes)
+            masks = list(cropper.crop_images(masks))
+            imgs = list(cropper.crop_images(imgs))
+            corners, sizes = cropper.crop_rois(corners, sizes)
+            estimator = ExposureErrorCompensator._device_estimator(st["compensator"], st["nr_feeds"], st["block_size"])
+            compensator = ExposureErrorCompensator(st["compensator"], st["nr_feeds"], st["block_size"], estimator=estimator)
+            compensator.feed(corners, imgs, masks)
+            device_finder = st["finder"] in DEVICE_SEAM_FINDERS
+            finder = SeamFinder(st["finder"], estimator=SeamEstimator(st["finder"]) if device_finder else None)
+            seam_masks = [as_device(m, ctx) for m in finder.find(imgs, corners, masks)]
+            host = None
+            if st["blender_type"] == "multiband":  # StitchJob's seam-cell crops read the masks' extents on the host
+                host = [m.numpy() for m in seam_masks]
+        finally:
+            config.set_device_resident(prev)
+        return ComposePlan(imgs_obj, frames, cameras, warper.scale, cropper, compensator, seam_masks, host, corners, sizes)
+
+    def run(self, plan, images=None):
+        """The final-resolution half on a plan: `images` None -> the frames the plan was prepared from, else new frames of the same rig
+        (no low-resolution pass).  Returns device-resident (panorama u8x3, mask u8)."""
+        frames = plan.frames if images is None else list(images)
+        plan.check_frames(frames)
+        st, ctx = self.settings, self._ctx()
+        frames = [as_device(f, ctx) for f in frames]
+        prev = config.device_resident()
+        config.set_device_resident(True)
+        try:
+            final = list(plan.images.resize(Images.Resolution.FINAL, frames))
+        finally:
+            config.set_device_resident(prev)
+        job = StitchJob(final, plan.cameras, warper_type=st["warper_type"], blender_type=st["blender_type"],
+                        blend_strength=st["blend_strength"], ctx=ctx,
+                        seam_masks=plan.seam_masks_host if plan.seam_masks_host is not None else plan.seam_masks,
+                        compensator=plan.compensator, cropper=plan.cropper, crop_aspect=plan.lir_aspect, camera_aspect=plan.camera_aspect)
+        return job.run()
+
+    def compose(self, images, cameras):
+        """prepare + run -> the panorama (device-resident u8x3), as Stitcher.stitch returns it"""
+        pano, _ = self.run(self.prepare(images, cameras))
+        return pano
 
 
 def stitch(frames, cameras, **kw):

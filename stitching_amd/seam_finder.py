@@ -31,6 +31,24 @@ def resize_linear_exact(img, size, ctx=None, device_resident=None):
     return r if resident else r.numpy()
 
 
+def resize_linear_exact_all(imgs, sizes, ctx=None, device_resident=None):
+    """[resize_linear_exact(img, size) for img, size in zip(imgs, sizes)] as ONE launch (stx_resize_linear_exact_batch): images of
+    unequal sizes, 1 and 3 channels mixed, device views included; the same bytes as the per-image call."""
+    imgs, sizes = list(imgs), list(sizes)
+    if len(imgs) != len(sizes):
+        raise StitchingError(f"need one size per image, got {len(imgs)} images and {len(sizes)} sizes")
+    ctx = ctx or next((i.ctx for i in imgs if isinstance(i, DeviceImage)), None) or get_context()
+    d = [as_device(img, ctx) for img in imgs]
+    n = len(d)
+    wh = np.ascontiguousarray([[int(s[0]), int(s[1])] for s in sizes], np.int32).reshape(n, 2)
+    outs = (C.c_void_p * max(n, 1))()
+    _lib.check(ctx._lib.stx_resize_linear_exact_batch(ctx.handle, n, (C.c_void_p * max(n, 1))(*[a._h for a in d]),
+                                                      wh.ctypes.data_as(C.POINTER(C.c_int)), outs))
+    res = [DeviceImage(ctx, C.c_void_p(outs[i])) for i in range(n)]
+    resident = config.device_resident() if device_resident is None else device_resident
+    return res if resident else [r.numpy() for r in res]
+
+
 class SeamFinder:
     """https://docs.opencv.org/4.x/d7/d09/classcv_1_1detail_1_1SeamFinder.html"""
 

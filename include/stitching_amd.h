@@ -350,6 +350,19 @@ int stx_seam_find(stx_ctx* ctx, int kind, int n, const int* sizes_wh, const int*
  * an image with it where one's roi meets the other's roi +- STX_SEAM_GAP clipped to that image).  Running the levels in order, pairs
  * of one level in any order, gives the sequential result.  out_pairs NULL: only writes *inout_npairs. */
 int stx_seam_schedule(int n, const int* sizes_wh, const int* corners_xy, int* inout_npairs, int* out_pairs, int* out_levels);
+/* ---- colour-aware seams: the project's OWN finder, not OpenCV's DpSeamFinder ("dp_color" / "dp_colorgrad" stay cv2's) -------------
+ * Pairwise, integer only, one dynamic programme per overlapping pair in PairwiseSeamFinder::run's order: the cost of a pixel both masks
+ * hold is the squared BGR difference of the two images, the seam is the 8-connected path of least cost along the overlap (vertical or
+ * horizontal by the images' centres), and it splits the pixels both masks hold between the two images.  tests/numpy_color_seams.py is the
+ * contract, byte for byte.
+ * images: n u8x3 images of sizes_wh (read only), masks_in: n u8x1 masks of the same sizes (never written), masks_out[i]: new buffers.
+ * Limits, checked before anything is launched (STX_ERR_INVALID): a seam of at most STX_COLOR_SEAM_MAX_LENGTH pixels (u32 accumulators:
+ * 16384 * 3 * 255^2 < 2^32), at most STX_COLOR_SEAM_MAX_CROSS pixels across it (two u32 accumulator rows of that many in LDS: 32 KiB).
+ * The pairs run level by level (stx_seam_schedule), two launches per level.  out_info as stx_seam_find. */
+#define STX_COLOR_SEAM_MAX_LENGTH 16384
+#define STX_COLOR_SEAM_MAX_CROSS 4096
+int stx_color_seam_find(stx_ctx* ctx, int n, const int* sizes_wh, const int* corners_xy, const stx_buf* const* images,
+                        const stx_buf* const* masks_in, stx_buf** masks_out, double out_info[4]);
 /* ---- cropping: Cropper.estimate_largest_interior_rectangle (stitching/cropper.py:91-106) -----------------------------------------
  * mask_u8x1: the panorama mask (views and pitched buffers allowed; nonzero means true), never copied to the host.
  * out_contours = {foreground components (8-connected), holes (4-connected background components of the zero-framed mask that do

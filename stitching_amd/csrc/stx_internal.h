@@ -274,6 +274,17 @@ int stx_lu_device(stx_ctx* ctx, int n, const StxLuEntry* entries, size_t count, 
 // then mask j's)
 struct StxSeamPair { uint8_t* m1; uint8_t* m2; long long s1, s2, off; int w1, h1, w2, h2, ox1, oy1, ox2, oy2, ww, wh, rw, rh; };
 int stx_launch_seam_level(stx_ctx* ctx, const StxSeamPair* d_pairs, int np, int max_rows, int max_cols, uint16_t* d_arena, double algo_bytes);
+// the project's own colour-aware seams (stx_color_seams.hip; host side in stx_seams_host.cpp) ------------------------------------------
+// a pair of one level: images (u8x3) and masks of i (i1, m1) and j (i2, m2), every pointer at the roi's first pixel, strides in bytes;
+// L x W: seam length x cross extent (a vertical seam: roi h x w, a horizontal one: w x h); off_choice / off_seam: byte offsets of the
+// pair's L * W choice bytes and its L int32 cut positions (4-aligned) in the level's arena
+struct StxColorSeamPair {
+    const uint8_t* i1; const uint8_t* i2; uint8_t* m1; uint8_t* m2;
+    long long si1, si2, sm1, sm2, off_choice, off_seam;
+    int L, W, vertical, first_is_i;
+};
+int stx_launch_color_seam_level(stx_ctx* ctx, const StxColorSeamPair* d_pairs, int np, int max_cross, long long max_area, uint8_t* d_arena,
+                                double algo_bytes);
 // cv::resize(INTER_LINEAR_EXACT) u8 (next rows N2 / N3); d_xt / d_yt: device tables of (offset, coeff1 | interior << 16)
 int stx_launch_resize_exact(stx_ctx* ctx, const stx_buf* src, stx_buf* dst, const int* d_xt, const int* d_yt, bool dilate,
                             const stx_buf* andmask);

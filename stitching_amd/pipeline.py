@@ -352,7 +352,8 @@ class Composer:
     ExposureErrorCompensator.feed, SeamFinder.find), `run` the final one (:117-128, a StitchJob), `compose` both.  The keywords are the
     reference's Stitcher.DEFAULT_SETTINGS where they apply; `cameras` are at MEDIUM scale, as the reference's registration leaves them.
     Exposure gains and the "voronoi" / "no" seams are estimated on the device whatever the process-wide estimator settings are (nothing
-    imports cv2); the "dp_*" and "gc_*" finders are cv2's, through SeamFinder.  The subset step (Images.subset) is the caller's: pass
+    imports cv2); the "dp_*" and "gc_*" finders are cv2's, through SeamFinder; a finder object given as seam_estimator= (the project's
+    own colour-aware ColorSeamEstimator, say) takes their place without cv2.  The subset step (Images.subset) is the caller's: pass
     the images registration kept."""
 
     DEFAULT_SETTINGS = {
@@ -369,7 +370,10 @@ class Composer:
         "blend_strength": Blender.DEFAULT_BLEND_STRENGTH,
     }
 
-    def __init__(self, ctx=None, **kwargs):
+    def __init__(self, ctx=None, seam_estimator=None, **kwargs):
+        """seam_estimator (not a setting): a finder object with find(imgs, corners, masks), e.g. a ColorSeamEstimator — `prepare` then finds
+        its seams with it whatever "finder" names, and never looks for cv2."""
+        self.seam_estimator = seam_estimator
         for arg in kwargs:
             if arg not in self.DEFAULT_SETTINGS:
                 raise StitchingError("Invalid Argument: " + arg)
@@ -419,8 +423,11 @@ class Composer:
             estimator = ExposureErrorCompensator._device_estimator(st["compensator"], st["nr_feeds"], st["block_size"])
             compensator = ExposureErrorCompensator(st["compensator"], st["nr_feeds"], st["block_size"], estimator=estimator)
             compensator.feed(corners, imgs, masks)
-            device_finder = st["finder"] in DEVICE_SEAM_FINDERS
-            finder = SeamFinder(st["finder"], estimator=SeamEstimator(st["finder"]) if device_finder else None)
+            if self.seam_estimator is not None:
+                finder = SeamFinder(st["finder"], estimator=self.seam_estimator)
+            else:
+                device_finder = st["finder"] in DEVICE_SEAM_FINDERS
+                finder = SeamFinder(st["finder"], estimator=SeamEstimator(st["finder"]) if device_finder else None)
             seam_masks = [as_device(m, ctx) for m in finder.find(imgs, corners, masks)]
             host = None
             if st["blender_type"] == "multiband":  # StitchJob's seam-cell crops read the masks' extents on the host

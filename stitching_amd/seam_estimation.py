@@ -5,6 +5,9 @@ masks)` on the low-resolution warped images returns the seam masks.  The images 
 PairwiseSeamFinder::run's pairs level by level (host schedule: csrc/stx_seams_host.cpp), two HIP launches per level
 (csrc/stx_seams.hip); "no" returns copies of the masks.  The algorithm restates OpenCV 4.x from recollection; tests/numpy_seams.py is
 the contract and fidelity to real OpenCV is unpinned.
+
+`ColorSeamEstimator` is the project's own colour-aware finder with the same interface (not OpenCV's DpSeamFinder): it reads the images'
+pixels.  tests/numpy_color_seams.py is its contract.
 """
 import ctypes as C
 
@@ -87,6 +90,86 @@ class SeamEstimator:
         info = np.zeros(4, np.float64)
         _lib.check(ctx._lib.stx_seam_find(ctx.handle, _lib.SEAM_KINDS[self.kind], n, ss.ctypes.data_as(ip), cs.ctypes.data_as(ip), ma,
                                           outs, info.ctypes.data_as(C.POINTER(C.c_double))))
+        self.info = {"pairs": int(info[0]), "levels": int(info[1]), "device_ms": float(info[2]), "device_ms_with_copy": float(info[3])}
+        res = [DeviceImage(ctx, C.c_void_p(outs[i])) for i in range(n)]
+        return res if resident else [r.numpy() for r in res]
+
+
+def _color_image(a, i):
+    """u8 HxWx3 (numpy or DeviceImage) from what a caller hands a finder: u8 images, or the float32 images with integer values in
+    0 .. 255 the reference's SeamFinder.find makes of them (stitching/seam_finder.py:33-35)."""
+    if isinstance(a, DeviceImage):
+        if a.dtype != np.uint8 or a.channels != 3:
+            raise StitchingError(f"image {i}: colour seams need u8 images with 3 channels, got {a.dtype} of shape {a.shape}")
+        return (a.width, a.height), a
+    if not isinstance(a, np.ndarray) and hasattr(a, "get"):
+        a = a.get()
+    a = np.asarray(a)
+    if a.ndim != 3 or a.shape[2] != 3 or a.dtype not in (np.uint8, np.float32):
+        raise StitchingError(f"image {i}: colour seams need u8 (or float32 holding 0 .. 255) images of shape HxWx3, got {a.dtype} of "
+                             f"shape {a.shape}")
+    if a.dtype == np.float32:
+        u = a.astype(np.uint8)
+        if a.size and not (a.min() >= 0 and a.max() <= 255 and np.array_equal(u, a)):
+            raise StitchingError(f"image {i}: float32 images must hold integers in 0 .. 255")
+        a = u
+    return (a.shape[1], a.shape[0]), a
+
+
+class ColorSeamEstimator:
+    """The project's own colour-aware seam finder on the device — NOT OpenCV's DpSeamFinder, and not behind the names "dp_color" /
+    "dp_colorgrad" (those stay cv2's).  Pairwise like "voronoi" (the same pairs, order and dependency levels), integer only, one dynamic
+    programme per overlapping pair: the cost of a pixel both masks hold is the squared BGR difference of the two images, the seam is the
+    8-connected path of least cost along the overlap (vertical or horizontal by the images' centres), and it splits the pixels both masks
+    hold between the two images.  tests/numpy_color_seams.py states the algorithm exactly and is the contract, byte for byte; DESIGN.md
+    section 14 has the launch shape (csrc/stx_color_seams.hip).  Construction needs no GPU.
+
+    Plug it in where a finder object goes: SeamFinder(name, estimator=ColorSeamEstimator()) or Composer(seam_estimator=...).
+
+    Limits, refused with a StitchingError before anything is launched: a seam of at most MAX_SEAM_LENGTH pixels (u32 accumulators:
+    16384 * 3 * 255^2 < 2^32) and at most MAX_CROSS_EXTENT pixels across it (two u32 accumulator rows in LDS: 32 KiB)."""
+
+    MAX_SEAM_LENGTH = _lib.COLOR_SEAM_MAX_LENGTH
+    MAX_CROSS_EXTENT = _lib.COLOR_SEAM_MAX_CROSS
+    reads_device_images = True  # SeamFinder.find hands the images over untouched: device images stay in HBM
+
+    def __init__(self):
+        self.info = None  # of the last call: pairs, levels, device ms of the levels, device ms with the copy of the inputs
+
+    def find(self, imgs, corners, masks):
+        """Seam masks for the u8 BGR images `imgs` (numpy arrays, cv.UMat-likes or DeviceImages; float32 arrays of integers in 0 .. 255
+        are cast) at `corners` with u8 masks `masks`; neither is written.  Returns new masks: DeviceImages when any input is a
+        DeviceImage or config.device_resident(), numpy arrays otherwise."""
+        imgs, masks, corners = list(imgs), list(masks), [tuple(int(v) for v in c) for c in corners]
+        if not (len(imgs) == len(masks) == len(corners)):
+            raise StitchingError("find needs as many images, corners and masks")
+        n = len(imgs)
+        if n == 0:
+            self.info = {"pairs": 0, "levels": 0, "device_ms": 0.0, "device_ms_with_copy": 0.0}
+            return []
+        sizes = []
+        for i in range(n):
+            wh, imgs[i] = _color_image(imgs[i], i)
+            mwh, m = _size(masks[i], "mask", i)
+            if isinstance(m, np.ndarray) and (m.ndim != 2 or m.dtype != np.uint8):
+                raise StitchingError(f"mask {i}: seam finding needs u8 masks with one channel, got {m.dtype} of shape {m.shape}")
+            if mwh != wh:
+                raise StitchingError(f"mask {i} is {mwh[0]}x{mwh[1]}, its image {wh[0]}x{wh[1]}")
+            masks[i] = m
+            sizes.append(wh)
+        ctxs = {id(a.ctx): a.ctx for a in imgs + masks if isinstance(a, DeviceImage)}
+        if len(ctxs) > 1:
+            raise StitchingError("device images of more than one context")
+        ctx = next(iter(ctxs.values())) if ctxs else get_context()
+        resident = config.device_resident() or any(isinstance(a, DeviceImage) for a in imgs + masks)
+        d_imgs, d_masks = [as_device(a, ctx) for a in imgs], [as_device(m, ctx) for m in masks]
+        ss = np.ascontiguousarray(np.asarray(sizes, np.int32).reshape(n, 2))
+        cs = np.ascontiguousarray(np.asarray(corners, np.int32).reshape(n, 2))
+        ip = C.POINTER(C.c_int)
+        ia, ma, outs = (C.c_void_p * n)(*[a._h for a in d_imgs]), (C.c_void_p * n)(*[m._h for m in d_masks]), (C.c_void_p * n)()
+        info = np.zeros(4, np.float64)
+        _lib.check(ctx._lib.stx_color_seam_find(ctx.handle, n, ss.ctypes.data_as(ip), cs.ctypes.data_as(ip), ia, ma, outs,
+                                                info.ctypes.data_as(C.POINTER(C.c_double))))
         self.info = {"pairs": int(info[0]), "levels": int(info[1]), "device_ms": float(info[2]), "device_ms_with_copy": float(info[3])}
         res = [DeviceImage(ctx, C.c_void_p(outs[i])) for i in range(n)]
         return res if resident else [r.numpy() for r in res]

@@ -90,7 +90,9 @@ class SeamFinder:
                                      f"estimator covers {' and '.join(repr(f) for f in DEVICE_SEAM_FINDERS)}")
             raise StitchingError("seam estimation needs OpenCV, which is not importable here: pass an estimator= object "
                                  "or give seam masks found elsewhere to SeamFinder.resize")
-        if isinstance(self.finder, SeamEstimator):  # reads the images' sizes only: device images stay on the device
+        # a SeamEstimator reads the images' sizes only, a ColorSeamEstimator (any finder marked reads_device_images) takes device
+        # images as they are: they stay on the device
+        if isinstance(self.finder, SeamEstimator) or getattr(self.finder, "reads_device_images", False) is True:
             return self.finder.find(list(imgs), list(corners), list(masks))
         host = lambda a: np.asarray(a.get() if hasattr(a, "get") else a)  # noqa: E731
         imgs_float = [host(img).astype(np.float32) for img in imgs]

@@ -1,7 +1,8 @@
 """The project's own colour-aware seam finder on the MI355X (stitching_amd.ColorSeamEstimator, csrc/stx_color_seams.hip) against its
 contract tests/numpy_color_seams.py, byte for byte, on seeded random u8 images: cross extents around the wavefront, the workgroup and the
 stride loop, seam lengths from 1, both orientations, ragged masks, several dependency levels, residency, the limits, and Composer with
-seam_estimator= (also in a child process without cv2)."""
+seam_estimator= (also in a child process without cv2).
+Inputs built to reach the walk-back window's edge, accumulators above 2^31 and mixed launches: tests/test_gpu_constructed_inputs.py."""
 import hashlib
 import json
 import os

@@ -1,7 +1,8 @@
 """The largest interior rectangle on the MI355X (stx_crop_lir / stitching_amd.Cropper) against the restatement tests/numpy_lir.py:
 seeded random and tie-heavy masks, views and pitched buffers, the low-resolution panorama masks of BASELINE configs 2-5 and config 2's
 full-resolution one, the Cropper API, and Stitcher.stitch's order end to end (crop, gain_blocks, voronoi seams, final crop, blend)
-against the oracle chain."""
+against the oracle chain.
+Staircase histograms across many lanes' chunks, the global-scratch path and long label chains: tests/test_gpu_constructed_inputs.py."""
 import numpy as np
 import pytest
 

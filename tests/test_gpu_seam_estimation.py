@@ -1,6 +1,7 @@
 """Seam finding on the MI355X (stitching_amd.SeamEstimator) against the restatement tests/numpy_seams.py, byte for byte: named cases from
 one image to config 4's 64-frame grid and a full-resolution ring, numpy / device / view inputs, residency, and the reference's order end
-to end (low-resolution seams, final-resolution resize + compose) against the oracle chain."""
+to end (low-resolution seams, final-resolution resize + compose) against the oracle chain.
+Ragged masks, far sources, rows without a source and ties (constructed, not warped): tests/test_gpu_constructed_inputs.py."""
 import numpy as np
 import pytest
 

@@ -373,6 +373,32 @@ int stx_color_seam_find(stx_ctx* ctx, int n, const int* sizes_wh, const int* cor
  * tests/numpy_lir.py is the contract.  Six launches, one synchronisation at the end.  At most 2^31 - 2 pixels.
  * out_info (or NULL): {device ms of the launches} (HIP events). */
 int stx_crop_lir(stx_ctx* ctx, const stx_buf* mask_u8x1, int out_xywh[4], int out_contours[2], double out_info[1]);
+/* ---- feature detection: the project's OWN detector, not cv.ORB (FeatureDetector's "orb" / "sift" stay cv2's) ---------------------
+ * Corner keypoints and 256-bit binary descriptors in the family of oriented FAST + rotated BRIEF, integer only: grey pyramid,
+ * 9-of-16 segment-test score with 3 x 3 non-maximum suppression, a Harris-like integer response, the best quotas[l] corners of every
+ * level by (response descending, y, x), orientation in 36 bins from the intensity centroid of a radius-15 disc, 256 comparisons of a
+ * 5 x 5 binomial blur under the rotated pattern.  tests/numpy_features.py is the contract, byte for byte.
+ * images: n u8x3 images of unequal sizes (read only; views allowed); masks: NULL, or n entries of which any may be NULL, else a u8x1
+ * mask of its image's size (nonzero: keypoints allowed; never written).
+ * The caller computes, in double precision as the contract states them, and hands in per image i: level_counts[i] <= nlevels kept
+ * levels, their sizes level_wh[(i * STX_FEATURES_MAX_LEVELS + l) * 2] = {w, h} (level 0: the image's own; every side in 33 .. the
+ * image's) and the quotas[i * STX_FEATURES_MAX_LEVELS + l] >= 0 (their sum at most nfeatures); once per process cxcy = {CX[36],
+ * CY[36]} and patterns[36][256] = {px, py, qx, qy} (the rotated comparison pairs, every coordinate within +-13).
+ * Results per image i, k = out_counts[i] <= nfeatures keypoints by level, then by that order: out_lxyb[(i * nfeatures + j) * 4] =
+ * {level, x, y, bin}, out_R[i * nfeatures + j], out_desc[(i * nfeatures + j) * 32].  out_info (or NULL): {levels, candidates,
+ * keypoints, 0} of the call.
+ * The pyramid levels are stx_resize_linear_exact_batch's, one launch per level; the host waits once for the candidate counts.  The
+ * candidate arena holds the most a level can produce (one per 2 x 2 cell of its interior): nothing is dropped, and the result does
+ * not depend on scheduling.
+ * Refused with STX_ERR_INVALID before anything is launched: an image side above STX_FEATURES_MAX_SIDE ((response, y, x) is one 64-bit
+ * key), nlevels > STX_FEATURES_MAX_LEVELS, nfeatures > STX_FEATURES_MAX_FEATURES, a mask of another size, an image that is not u8x3. */
+#define STX_FEATURES_MAX_SIDE 32767
+#define STX_FEATURES_MAX_LEVELS 16
+#define STX_FEATURES_MAX_FEATURES 65536
+int stx_features_detect(stx_ctx* ctx, int n, const stx_buf* const* images, const stx_buf* const* masks, int nfeatures, int nlevels,
+                        int fast_threshold, const int* level_counts, const int* level_wh, const int* quotas, const int* cxcy,
+                        const signed char* patterns, int* out_counts, int* out_lxyb, long long* out_R, unsigned char* out_desc,
+                        double out_info[4]);
 /* stx_resize_linear_exact <- stitching/images.py:122-124 cv.resize(img, size, interpolation=cv.INTER_LINEAR_EXACT) (u8x1 / u8x3:
  *                            the final-resolution resize of Images.resize, next row N3)
  * stx_seam_mask_resize    <- stitching/seam_finder.py:37-43 SeamFinder.resize: cv.dilate(seam_mask, None), cv.resize(...,

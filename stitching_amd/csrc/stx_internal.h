@@ -285,6 +285,32 @@ struct StxColorSeamPair {
 };
 int stx_launch_color_seam_level(stx_ctx* ctx, const StxColorSeamPair* d_pairs, int np, int max_cross, long long max_area, uint8_t* d_arena,
                                 double algo_bytes);
+// feature detection (stx_features.hip; host side in stx_features_host.cpp) ----------------------------------------------------------
+// the grids are flat lists of tiles, image after image / level after level, as the batched resize's (tile0 ascending, first 0)
+constexpr int STX_FEAT_GREY_TW = 64, STX_FEAT_GREY_TH = 4;    // grey: one pixel per lane
+constexpr int STX_FEAT_BLUR_TW = 64, STX_FEAT_BLUR_TH = 8;    // blur: halo of 2 in LDS
+constexpr int STX_FEAT_SCORE_TW = 32, STX_FEAT_SCORE_TH = 8;  // score + suppression + response: halo of 4 in LDS
+constexpr int STX_FEAT_BORDER = 16;                           // keypoints lie in [16, w - 17] x [16, h - 17]
+struct StxFeatImage { const uint8_t* img; long long istride; uint8_t* grey; long long gstride; int w, h, tiles_x, tile0; };
+// one level of one image: grey level g, its blur, the image's level-0 mask (or null) of size w0 x h0; cand_off / cand_cap: the level's
+// keys in the candidate arena (cap = one per 2 x 2 cell of the interior: strict 3 x 3 maxima cannot be denser)
+struct StxFeatLevel {
+    const uint8_t* g; long long gstride; uint8_t* blur; long long bstride; const uint8_t* mask; long long mstride;
+    long long cand_off, cand_cap;
+    int w, h, w0, h0, btiles_x, btile0, stiles_x, stile0;
+};
+// selection of one level: `count` candidates at cand_off, the first `keep` of them in key order go to out_off .. of the flat output
+struct StxFeatSel { long long cand_off; int count, keep, out_off, pad_; };
+// (response, y, x) as one ascending 64-bit key: (2^33 - R) << 30 | y << 15 | x, |R| < 2^33, x, y < 2^15
+constexpr long long STX_FEAT_R_BIAS = 1ll << 33;
+int stx_launch_feat_grey(stx_ctx* ctx, const StxFeatImage* d_imgs, int n, int tiles, double algo_bytes);
+int stx_launch_feat_blur(stx_ctx* ctx, const StxFeatLevel* d_levels, int n, int tiles, double algo_bytes);
+int stx_launch_feat_score(stx_ctx* ctx, const StxFeatLevel* d_levels, int n, int tiles, int threshold, unsigned long long* d_cand,
+                          int* d_counts, double algo_bytes);
+int stx_launch_feat_select(stx_ctx* ctx, const StxFeatSel* d_sel, int n, const unsigned long long* d_cand, unsigned long long* d_tmp,
+                           unsigned long long* d_keys, int* d_item);
+int stx_launch_feat_describe(stx_ctx* ctx, const StxFeatLevel* d_levels, int nl, const unsigned long long* d_keys, const int* d_item, int total,
+                             const int* d_cxcy, const signed char* d_patterns, int* d_bins, uint8_t* d_desc);
 // cv::resize(INTER_LINEAR_EXACT) u8 (next rows N2 / N3); d_xt / d_yt: device tables of (offset, coeff1 | interior << 16)
 int stx_launch_resize_exact(stx_ctx* ctx, const stx_buf* src, stx_buf* dst, const int* d_xt, const int* d_yt, bool dilate,
                             const stx_buf* andmask);

@@ -138,6 +138,7 @@ int stx_get_pyrdown_mode(int* out_lanes);
 typedef struct stx_ctx stx_ctx;
 typedef struct stx_buf stx_buf;
 typedef struct stx_blender stx_blender;
+typedef struct stx_mb_weights stx_mb_weights;
 
 /* ---- library / context ------------------------------------------------------------ */
 int stx_version(void);
@@ -251,6 +252,27 @@ int stx_blend_finish(stx_blender* b, stx_buf** out_pano_u8, stx_buf** out_mask_u
  * before convertScaleAbs (stitching/blender.py:46); any out pointer may be NULL */
 int stx_blend_finish_ex(stx_blender* b, stx_buf** out_pano_u8, stx_buf** out_mask_u8, stx_buf** out_pano_s16);
 int stx_blend_destroy(stx_blender* b);
+/* Weight pyramids that outlive their blender: the panoramas of one rig ("video: same rig, new frames").  W_1..W_B of a fed image, their
+ * occupancy maps included, depend on its mask and on the geometry of the feed — never on the pixels — so a second panorama with the
+ * same masks at the same places need not build them again.
+ * stx_blend_keep_weights: on a multi-band blender, after its feeds and before stx_blend_finish.  After a finish that succeeded the handle owns the
+ *   wt[1..B] allocations and the occupancy arena of every image fed (they no longer die with the blender), holds a reference to every
+ *   mask buffer and records per image: mask buffer, 0/255 flag and the half-precision W_1 flag, size, corner, feed rectangle, border
+ *   offsets, and the blender's band count and pyrDown mode.  Needs: only images fed on this blender (no received strips), u8 images,
+ *   the batched pyramid kernels (STX_PYRDOWN_SCALAR), occupancy recording on, >= 1 band, weights of its own (not adopted ones).  Where
+ *   that does not hold *out is NULL, the call returns STX_OK and the blender builds as ever.  A handle whose blender never finished
+ *   stays empty and is never adopted.
+ * stx_blend_use_weights: on a fresh blender after its feeds (no feed may follow).  *out_adopted = 1: every fed image matches the handle's
+ *   record field for field (same order, same mask buffer, same geometry, bands, mode), the blender has taken the handle's weight and
+ *   occupancy pointers in place of its own allocations and builds its pyramids without their weight half (no mask read, no weight
+ *   read / sum / write, no occupancy note: the "mb_down0" / "mb_down" profiler entries carry the bytes of what then moves).
+ *   *out_adopted = 0: nothing was adopted — all images or none — and everything is built as ever.  The masks must hold what they held
+ *   at the keep: the caller owns that promise.  Handle and blender live on ONE context, whose stream order makes the weights ready
+ *   before their first reuse; a blender of another context is refused with STX_ERR_INVALID.
+ * stx_mb_weights_free: gives the allocations back (stream-ordered: blenders that adopted the handle may still be in flight). */
+int stx_blend_keep_weights(stx_blender* b, stx_mb_weights** out);
+int stx_blend_use_weights(stx_blender* b, stx_mb_weights* w, int* out_adopted);
+int stx_mb_weights_free(stx_mb_weights* w);
 
 /* ---- "next" rows either side of the path -----------------------------------------------------
  * stx_gain_apply      <- stitching/exposure_error_compensator.py:43-45 compensator.apply(idx, corner, img, mask) for the

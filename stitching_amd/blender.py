@@ -15,6 +15,26 @@ from .device import DeviceImage, as_device, get_context
 from .stitching_error import StitchingError
 
 
+class MbWeights:
+    """Owns one stx_mb_weights: the weight pyramids and occupancy maps a multi-band blender built, kept past its blend() for the next
+    panoramas of the same rig (include/stitching_amd.h: stx_blend_keep_weights).  Device memory of about 0.8 bytes per fed pixel."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self._h = ctx, handle
+
+    def free(self):
+        if self._h is not None:
+            if getattr(self.ctx, "handle", None):
+                self.ctx._lib.stx_mb_weights_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class _BlenderHandle:
     """Owns one stx_blender (the object the reference keeps in `Blender.blender`)."""
 
@@ -33,6 +53,22 @@ class _BlenderHandle:
 
     def feed(self, img, mask, corner):
         _lib.check(self.ctx._lib.stx_blend_feed(self._h, img._h, mask._h, int(corner[0]), int(corner[1])))
+
+    def keep_weights(self):
+        """Before blend(), on a multi-band blender: -> the MbWeights that will own this blender's weight pyramids once it has blended, or
+        None where the blender does not qualify (stx_blend_keep_weights: received strips, int16 images, another pyrDown mode, ...)."""
+        h = C.c_void_p()
+        _lib.check(self.ctx._lib.stx_blend_keep_weights(self._h, C.byref(h)))
+        return MbWeights(self.ctx, h) if h.value else None
+
+    def use_weights(self, weights):
+        """After the feeds of a fresh blender: True when every fed image matched the record of `weights` and the blender took its
+        weight pyramids instead of building them; False: nothing was adopted, everything is built as ever."""
+        if weights is None or weights._h is None:
+            return False
+        got = C.c_int()
+        _lib.check(self.ctx._lib.stx_blend_use_weights(self._h, weights._h, C.byref(got)))
+        return bool(got.value)
 
     def blend(self, want_s16=False):
         pano, mask, p16 = C.c_void_p(), C.c_void_p(), C.c_void_p()

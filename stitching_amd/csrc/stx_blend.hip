@@ -795,8 +795,10 @@ inline dim3 grid64x4(int w, int h) { return dim3((w + 63) / 64, (h + 3) / 4); }
 // the 36 us of the three launches it replaces on config 2 (84 against ~60 on config 4's share; commit history: "fused pyramid tail").
 // 1.7 x redundant halo work, 62 KB of LDS = 2 workgroups per CU = three rounds of a workgroup whose own dependent chain is longer than
 // a whole small launch.  One launch per level stays.)
+// weights = false (every image's W_1..W_B and occupancy maps were taken from a stx_mb_weights handle): the batched LDS kernels build
+// the G planes alone; a level they do not take (degenerate sizes) goes through the generic kernel, which writes the same weights again.
 int stx_launch_mb_pyramids(stx_ctx* ctx, const StxMbImage* d_images, const StxMbImage* h_images, int n, int num_bands, int pyr_mode,
-                           int pyr_lanes)
+                           int pyr_lanes, bool weights)
 {
     for (int lv = 0; lv < num_bands; lv++) {
         double bytes = 0.0;
@@ -804,15 +806,16 @@ int stx_launch_mb_pyramids(stx_ctx* ctx, const StxMbImage* d_images, const StxMb
         for (int i = 0; i < n; i++) {
             const StxMbImage& im = h_images[i];
             const double ip = (double)(im.fw >> lv) * (im.fh >> lv), op = ip / 4.0;
-            const double gw = (im.g_u8 ? 3.0 : 6.0) + 4.0;  // bytes per pyramid sample: 3 Gaussian planes (bytes / int16) + the fp32 weight
-            const double gw1 = gw - (im.w1_f16 ? 2.0 : 0.0);  // ... of level 1: its weight may be a half (StxMbImage::w1_f16)
-            if (lv == 0) bytes += ((im.img0_is_s16 ? 6.0 : 3.0) + 1.0) * im.iw * im.ih + gw1 * op;
+            const double wb = weights ? 4.0 : 0.0;  // the fp32 weight of a sample: neither read nor written by the weightless variants
+            const double gw = (im.g_u8 ? 3.0 : 6.0) + wb;  // bytes per pyramid sample: 3 Gaussian planes (bytes / int16) + the weight
+            const double gw1 = gw - ((weights && im.w1_f16) ? 2.0 : 0.0);  // ... of level 1: its weight may be a half (StxMbImage::w1_f16)
+            if (lv == 0) bytes += ((im.img0_is_s16 ? 6.0 : 3.0) + (weights ? 1.0 : 0.0)) * im.iw * im.ih + gw1 * op;
             else bytes += (lv == 1 ? gw1 : gw) * ip + gw * op;
             any_s16 = any_s16 || im.img0_is_s16;
         }
         StxProfScope prof(ctx, lv == 0 ? "mb_down0" : "mb_down", bytes);
         // the LDS kernels sum the weights in the scalar order; every other order goes through the generic kernels
-        const bool batched = pyr_mode == STX_PYRDOWN_SCALAR && stx_fast_mb_down_batch(ctx, d_images, h_images, n, lv);
+        const bool batched = pyr_mode == STX_PYRDOWN_SCALAR && stx_fast_mb_down_batch(ctx, d_images, h_images, n, lv, weights);
         for (int i = 0; i < n; i++) {
             const StxMbImage& im = h_images[i];
             if (batched && !(lv == 0 && im.img0_is_s16)) continue;

@@ -422,7 +422,9 @@ struct DnImage0 {
     const uint8_t* img0;
     const uint8_t* mask0;
 };
-template <bool PK, bool NEAR, class IM>
+// WEIGHTS = false (a blender that took its weight pyramids from a stx_mb_weights handle): the image sums alone — the mask is never read,
+// hw never written
+template <bool PK, bool NEAR, bool WEIGHTS, class IM>
 STX_DEV void dn_task_level0(const IM& im, int row, int xo, short* hs0, short* hs1, short* hs2, float* hw)
 {
     const int by = reflect101_near(row, im.fh) - im.top;  // bordered row -> image row
@@ -441,6 +443,7 @@ STX_DEV void dn_task_level0(const IM& im, int row, int xo, short* hs0, short* hs
         dn_pack5_channel<false, 0>(w, hs0);  // packed image sums: the image is u8 in this kernel whatever its mask is
         dn_pack5_channel<false, 1>(w, hs1);
         dn_pack5_channel<false, 2>(w, hs2);
+        if (!WEIGHTS) return;
         // the mask's 11 bytes.  PK (host: every mask of the launch is 0 / 255): packed counts.  Otherwise (round 6) the SAME packed counts
         // whenever every lane of the wavefront reads nothing but 0 and 255 — a resized seam mask (SeamFinder.resize) is grey only along
         // its seams, a strip a dozen pixels wide — and the fp32 form (m / 255, row sums in pyrDown's order) for the wavefronts on a seam:
@@ -488,22 +491,25 @@ STX_DEV void dn_task_level0(const IM& im, int row, int xo, short* hs0, short* hs
             dn_pack5_channel<true, 0>(w, hs0);
             dn_pack5_channel<true, 1>(w, hs1);
             dn_pack5_channel<true, 2>(w, hs2);
-            *reinterpret_cast<float4*>(hw) = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (WEIGHTS) *reinterpret_cast<float4*>(hw) = make_float4(0.f, 0.f, 0.f, 0.f);
             return;
         }
     }
     {
         // an 11-pixel run that meets a border: every load unconditional and from a position inside the image (so that all 44 of them
         // are in flight together), the CONSTANT-0 border of the weight as a select afterwards
-        const STX_GAS uint8_t* mrow = gp(im.mask0) + (uint32_t)min(max(by, 0), im.ih - 1) * (uint32_t)im.mask0_stride;
+        const STX_GAS uint8_t* mrow = nullptr;
+        if (WEIGHTS) mrow = gp(im.mask0) + (uint32_t)min(max(by, 0), im.ih - 1) * (uint32_t)im.mask0_stride;
 #pragma unroll
         for (int j = 0; j < 11; j++) {
             const int bx = reflect101_near(c0 + j, im.fw) - im.left;
             const int sx = NEAR ? reflect_near(bx, im.iw) : reflect(bx, im.iw);
             const STX_GAS uint8_t* p = img + (rowoff + (uint32_t)sx * 3u);
             px[j][0] = p[0]; px[j][1] = p[1]; px[j][2] = p[2];
-            const float mv = fmul((float)mrow[sx], INV255);
-            f[j] = (yin && (unsigned)bx < (unsigned)im.iw) ? mv : 0.f;
+            if (WEIGHTS) {
+                const float mv = fmul((float)mrow[sx], INV255);
+                f[j] = (yin && (unsigned)bx < (unsigned)im.iw) ? mv : 0.f;
+            }
         }
     }
 #pragma unroll
@@ -511,7 +517,7 @@ STX_DEV void dn_task_level0(const IM& im, int row, int xo, short* hs0, short* hs
         hs0[o] = (short)h5i(px[2 * o][0], px[2 * o + 1][0], px[2 * o + 2][0], px[2 * o + 3][0], px[2 * o + 4][0]);
         hs1[o] = (short)h5i(px[2 * o][1], px[2 * o + 1][1], px[2 * o + 2][1], px[2 * o + 3][1], px[2 * o + 4][1]);
         hs2[o] = (short)h5i(px[2 * o][2], px[2 * o + 1][2], px[2 * o + 2][2], px[2 * o + 3][2], px[2 * o + 4][2]);
-        hw[o] = h5f(f[2 * o], f[2 * o + 1], f[2 * o + 2], f[2 * o + 3], f[2 * o + 4]);
+        if (WEIGHTS) hw[o] = h5f(f[2 * o], f[2 * o + 1], f[2 * o + 2], f[2 * o + 3], f[2 * o + 4]);
     }
 }
 
@@ -537,11 +543,13 @@ STX_DEV void dn_note_occ(uint8_t* __restrict__ occ, uint32_t nzbits, int tid, in
 #define STX_DN0_BATCH 3
 #endif
 // blockIdx.z = image: all fed images are processed by one launch (deferred pyramid build)
-template <bool PK>
+// WEIGHTS = false: G_1 alone — W_1 and its occupancy map are the handle's (stx_blend_use_weights), the mask is not read, there is no
+// s_w array.  Image sums, border handling, tile order and the G_1 stores are those of WEIGHTS = true.
+template <bool PK, bool WEIGHTS>
 __global__ __launch_bounds__(256) void mb_down0_lds_kernel(const StxMbImage* __restrict__ images, StxTileMap M)
 {
     __shared__ __attribute__((aligned(16))) short s_h[3][DN_ROWS][DN_TOW];  // horizontal sums, <= 255*16
-    __shared__ __attribute__((aligned(16))) float s_w[DN_ROWS][DN_TOW];
+    __shared__ __attribute__((aligned(16))) float s_w[WEIGHTS ? DN_ROWS : 1][WEIGHTS ? DN_TOW : 4];
     // (round 6, STX_DN0_REV) The launch walks the images and their tiles in the REVERSE of the order the batched warp wrote them: the
     // warped images of a panorama (317 MB on config 2) are a little more than the 256 MB Infinity Cache holds, so a second pass in the
     // same order finds every line evicted just before it asks for it, while the reverse pass starts on what was written last.
@@ -554,14 +562,14 @@ __global__ __launch_bounds__(256) void mb_down0_lds_kernel(const StxMbImage* __r
     if (!xcd_tile(M, bb, tile_tx, tile_ty)) return;
     const int X0 = tile_tx * DN_TOW, Y0 = tile_ty * DN_TOH;
     if (im.img0_is_s16 || X0 >= ow || Y0 >= oh) return;  // int16 sources take the generic kernel
-    uint8_t* const occ = im.occ[1];
-    const bool w1h = im.w1_f16 != 0;
-    asm volatile("" ::"s"(occ));  // fetched with the other descriptor fields, not at the tail where nothing hides the round trip
+    uint8_t* const occ = WEIGHTS ? im.occ[1] : nullptr;
+    const bool w1h = WEIGHTS && im.w1_f16 != 0;
+    if (WEIGHTS) asm volatile("" ::"s"(occ));  // fetched with the other descriptor fields, not at the tail where nothing hides the round trip
     DnImage0 D;
     {
         int fw = im.fw, fh = im.fh, iw_ = im.iw, ih_ = im.ih, left = im.left, top = im.top;
-        uint32_t is = (uint32_t)im.img0_stride, ms = (uint32_t)im.mask0_stride;
-        unsigned long long ia = (unsigned long long)im.img0, ma = (unsigned long long)im.mask0;
+        uint32_t is = (uint32_t)im.img0_stride, ms = WEIGHTS ? (uint32_t)im.mask0_stride : 0u;
+        unsigned long long ia = (unsigned long long)im.img0, ma = WEIGHTS ? (unsigned long long)im.mask0 : 0ull;
         // (the binary-mask instantiation only: the grey-mask one measured 148 -> 155 us with its fields pinned, three interleaved runs of the
         // reference-default leg, tools/gpu_r6r.sh; the binary one 121.7 -> 120.1)
         if (PK) asm volatile("" : "+s"(fw), "+s"(fh), "+s"(iw_), "+s"(ih_), "+s"(left), "+s"(top), "+s"(is), "+s"(ms), "+s"(ia), "+s"(ma));
@@ -572,9 +580,14 @@ __global__ __launch_bounds__(256) void mb_down0_lds_kernel(const StxMbImage* __r
     uint32_t g1_plane = 0, g1_stride = 0, w1_stride = 0;
     unsigned long long g1_a = 0, w1_a = 0;
     if (PK) {
-        g1_plane = (uint32_t)im.g_plane[1]; g1_stride = (uint32_t)im.g_stride[1]; w1_stride = (uint32_t)im.wt_stride[1];
-        g1_a = (unsigned long long)im.g[1]; w1_a = (unsigned long long)im.wt[1];
-        asm volatile("" : "+s"(g1_plane), "+s"(g1_stride), "+s"(w1_stride), "+s"(g1_a), "+s"(w1_a));
+        g1_plane = (uint32_t)im.g_plane[1]; g1_stride = (uint32_t)im.g_stride[1];
+        g1_a = (unsigned long long)im.g[1];
+        if (WEIGHTS) {
+            w1_stride = (uint32_t)im.wt_stride[1]; w1_a = (unsigned long long)im.wt[1];
+            asm volatile("" : "+s"(g1_plane), "+s"(g1_stride), "+s"(w1_stride), "+s"(g1_a), "+s"(w1_a));
+        } else {
+            asm volatile("" : "+s"(g1_plane), "+s"(g1_stride), "+s"(g1_a));
+        }
     }
     // rows / columns of the tile past the image's last output feed nothing (narrow exchange strips and the right / bottom
     // edge tiles would otherwise run the reflecting slow path for them)
@@ -616,14 +629,16 @@ __global__ __launch_bounds__(256) void mb_down0_lds_kernel(const StxMbImage* __r
                 d0[t] = *reinterpret_cast<const STX_GAS v4u_a4*>(p);
                 d1[t] = *reinterpret_cast<const STX_GAS v4u_a4*>(p + 16);
                 d2[t] = *reinterpret_cast<const STX_GAS v2u_a4*>(p + 32);
-                // the mask's 11 bytes (cleared below for a row outside the image and for a run in the frame: the weight's border is CONSTANT 0)
-                const uint32_t moff = (uint32_t)min(max(by, 0), D.ih - 1) * (uint32_t)D.mask0_stride + (uint32_t)acol;
-                msh[t] = moff & 3u;
+                if (WEIGHTS) {
+                    // the mask's 11 bytes (cleared below for a row outside the image and for a run in the frame: the weight's border is CONSTANT 0)
+                    const uint32_t moff = (uint32_t)min(max(by, 0), D.ih - 1) * (uint32_t)D.mask0_stride + (uint32_t)acol;
+                    msh[t] = moff & 3u;
 #if STX_ABLATE_MASK
-                mq4[t] = v4u{0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};  // timing experiment only
+                    mq4[t] = v4u{0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};  // timing experiment only
 #else
-                mq4[t] = *reinterpret_cast<const STX_GAS v4u_a4*>(gp(D.mask0) + (moff & ~3u));
+                    mq4[t] = *reinterpret_cast<const STX_GAS v4u_a4*>(gp(D.mask0) + (moff & ~3u));
 #endif
+                }
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -649,6 +664,7 @@ __global__ __launch_bounds__(256) void mb_down0_lds_kernel(const StxMbImage* __r
                     dn_pack5_channel<true, 1>(w, &s_h[1][r][4 * q]);
                     dn_pack5_channel<true, 2>(w, &s_h[2][r][4 * q]);
                 }
+                if (!WEIGHTS) continue;
                 const uint32_t keep = (yin[t] && interior) ? 0xffffffffu : 0u;
                 uint32_t mw[3];
                 mw[0] = __builtin_amdgcn_alignbyte(mq4[t].y, mq4[t].x, msh[t]) & keep;
@@ -679,12 +695,13 @@ __global__ __launch_bounds__(256) void mb_down0_lds_kernel(const StxMbImage* __r
     for (int task = tid; task < DN_ROWS * (DN_TOW / 4) && !batched; task += 256) {
         const int r = task / (DN_TOW / 4), q = task % (DN_TOW / 4);
         if (X0 + 4 * q >= ow || r >= r_end) continue;
+        float* const hw = WEIGHTS ? &s_w[r][4 * q] : nullptr;
         if (PK) {  // the pinned copy of the descriptor
-            if (near) dn_task_level0<PK, true>(D, 2 * Y0 - 2 + r, X0 + 4 * q, &s_h[0][r][4 * q], &s_h[1][r][4 * q], &s_h[2][r][4 * q], &s_w[r][4 * q]);
-            else dn_task_level0<PK, false>(D, 2 * Y0 - 2 + r, X0 + 4 * q, &s_h[0][r][4 * q], &s_h[1][r][4 * q], &s_h[2][r][4 * q], &s_w[r][4 * q]);
+            if (near) dn_task_level0<PK, true, WEIGHTS>(D, 2 * Y0 - 2 + r, X0 + 4 * q, &s_h[0][r][4 * q], &s_h[1][r][4 * q], &s_h[2][r][4 * q], hw);
+            else dn_task_level0<PK, false, WEIGHTS>(D, 2 * Y0 - 2 + r, X0 + 4 * q, &s_h[0][r][4 * q], &s_h[1][r][4 * q], &s_h[2][r][4 * q], hw);
         } else {   // the descriptor itself, as rounds 1 - 5 read it
-            if (near) dn_task_level0<PK, true>(im, 2 * Y0 - 2 + r, X0 + 4 * q, &s_h[0][r][4 * q], &s_h[1][r][4 * q], &s_h[2][r][4 * q], &s_w[r][4 * q]);
-            else dn_task_level0<PK, false>(im, 2 * Y0 - 2 + r, X0 + 4 * q, &s_h[0][r][4 * q], &s_h[1][r][4 * q], &s_h[2][r][4 * q], &s_w[r][4 * q]);
+            if (near) dn_task_level0<PK, true, WEIGHTS>(im, 2 * Y0 - 2 + r, X0 + 4 * q, &s_h[0][r][4 * q], &s_h[1][r][4 * q], &s_h[2][r][4 * q], hw);
+            else dn_task_level0<PK, false, WEIGHTS>(im, 2 * Y0 - 2 + r, X0 + 4 * q, &s_h[0][r][4 * q], &s_h[1][r][4 * q], &s_h[2][r][4 * q], hw);
         }
     }
     __syncthreads();
@@ -711,6 +728,7 @@ __global__ __launch_bounds__(256) void mb_down0_lds_kernel(const StxMbImage* __r
             if (two) *reinterpret_cast<STX_GAS uint16_t*>(o) = (uint16_t)b2;
             else o[0] = (uint8_t)b2;
         }
+        if (!WEIGHTS) continue;
         float fa[5], fb[5];
         {
             // Five 8-byte LDS reads (rows 2 yl .. 2 yl + 4, row pitch 256 bytes).  Written as ds_read_b64 by hand: the compiler
@@ -742,7 +760,7 @@ __global__ __launch_bounds__(256) void mb_down0_lds_kernel(const StxMbImage* __r
         }
         nz |= __float_as_uint(wa) | (two ? __float_as_uint(wb) : 0u);
     }
-    dn_note_occ(occ, nz, tid, X0, Y0, ow, oh);
+    if (WEIGHTS) dn_note_occ(occ, nz, tid, X0, Y0, ow, oh);
 }
 
 // level >= 1 of a byte pyramid: the 19 samples p[c0 .. c0 + 18], c0 = 16 t - 2: dword, 16 bytes, dword around them.
@@ -814,10 +832,12 @@ STX_DEV void dn_hsum_store_f(const float (&f)[19], float* row_q)
     *reinterpret_cast<float4*>(row_q + 32) = make_float4(lo.y, lo.w, hi.y, hi.w);
 }
 
+// WEIGHTS = false: G_{lv+1} alone, as in the level-0 kernel
+template <bool WEIGHTS>
 __global__ __launch_bounds__(256) void mb_down_lds_kernel(const StxMbImage* __restrict__ images, int lv, StxTileMap M)
 {
     __shared__ __attribute__((aligned(16))) int s_h[3][DN_ROWS][DN_TOW];
-    __shared__ __attribute__((aligned(16))) float s_w[DN_ROWS][DN_TOW];
+    __shared__ __attribute__((aligned(16))) float s_w[WEIGHTS ? DN_ROWS : 1][WEIGHTS ? DN_TOW : 4];
     const StxMbImage& im = images[blockIdx.z];
     const int tid = threadIdx.x;
     const int iw = im.fw >> lv, ih = im.fh >> lv;
@@ -829,15 +849,16 @@ __global__ __launch_bounds__(256) void mb_down_lds_kernel(const StxMbImage* __re
     const bool g8b = im.g_u8 != 0;  // byte planes (u8 image) or int16 planes: uniform for the workgroup
     // every descriptor field of both phases in ONE batch of scalar loads, pinned (round 6: as in the level-0 kernel — the weight pointer
     // came back inside the task loop, the output pointers behind the barrier, once per row: seven dependent scalar round trips)
-    unsigned long long G_a = (unsigned long long)im.g[lv], W_a = (unsigned long long)im.wt[lv];
-    unsigned long long Go_a = (unsigned long long)im.g[lv + 1], Wo_a = (unsigned long long)im.wt[lv + 1];
-    uint32_t gs = (uint32_t)im.g_stride[lv], gpl = (uint32_t)im.g_plane[lv], wst = (uint32_t)im.wt_stride[lv];
-    uint32_t gos = (uint32_t)im.g_stride[lv + 1], gopl = (uint32_t)im.g_plane[lv + 1], wost = (uint32_t)im.wt_stride[lv + 1];
-    asm volatile("" : "+s"(G_a), "+s"(W_a), "+s"(Go_a), "+s"(Wo_a), "+s"(gs), "+s"(gpl), "+s"(wst), "+s"(gos), "+s"(gopl), "+s"(wost));
+    unsigned long long G_a = (unsigned long long)im.g[lv], W_a = WEIGHTS ? (unsigned long long)im.wt[lv] : 0ull;
+    unsigned long long Go_a = (unsigned long long)im.g[lv + 1], Wo_a = WEIGHTS ? (unsigned long long)im.wt[lv + 1] : 0ull;
+    uint32_t gs = (uint32_t)im.g_stride[lv], gpl = (uint32_t)im.g_plane[lv], wst = WEIGHTS ? (uint32_t)im.wt_stride[lv] : 0u;
+    uint32_t gos = (uint32_t)im.g_stride[lv + 1], gopl = (uint32_t)im.g_plane[lv + 1], wost = WEIGHTS ? (uint32_t)im.wt_stride[lv + 1] : 0u;
+    if (WEIGHTS) asm volatile("" : "+s"(G_a), "+s"(W_a), "+s"(Go_a), "+s"(Wo_a), "+s"(gs), "+s"(gpl), "+s"(wst), "+s"(gos), "+s"(gopl), "+s"(wost));
+    else asm volatile("" : "+s"(G_a), "+s"(Go_a), "+s"(gs), "+s"(gpl), "+s"(gos), "+s"(gopl));
     const short* G = (const short*)G_a;
-    uint8_t* const occ = im.occ[lv + 1];
-    const bool w_half = lv == 1 && im.w1_f16 != 0;
-    asm volatile("" ::"s"(occ));  // as in the level-0 kernel
+    uint8_t* const occ = WEIGHTS ? im.occ[lv + 1] : nullptr;
+    const bool w_half = WEIGHTS && lv == 1 && im.w1_f16 != 0;
+    if (WEIGHTS) asm volatile("" ::"s"(occ));  // as in the level-0 kernel
     const int r_end = 2 * min(DN_TOH, oh - Y0) + 3;  // as in the level-0 kernel
     for (int task = tid; task < DN_ROWS * (DN_TOW / 8); task += 256) {
         const int r = task / (DN_TOW / 8), q = task % (DN_TOW / 8);
@@ -861,7 +882,8 @@ __global__ __launch_bounds__(256) void mb_down_lds_kernel(const StxMbImage* __re
                 rc[c] = *reinterpret_cast<const STX_GAS uint32_t*>(pp + 18);
             }
             float f[19];
-            if (w_half) {  // wave-uniform
+            if (!WEIGHTS) {  // nothing of the weights
+            } else if (w_half) {  // wave-uniform
                 const STX_GAS _Float16* hq = gp(reinterpret_cast<const _Float16*>(W_a)) + (uint32_t)sy * wst;
                 const v2h16 ha = *reinterpret_cast<const STX_GAS v2h16*>(hq + c0);
                 const v8h16 hb = *reinterpret_cast<const STX_GAS v8h16*>(hq + c0 + 2), hc = *reinterpret_cast<const STX_GAS v8h16*>(hq + c0 + 10);
@@ -895,7 +917,7 @@ __global__ __launch_bounds__(256) void mb_down_lds_kernel(const StxMbImage* __re
                 for (int j = 0; j < 19; j++) s[j] = (int)byte_of(w6, j + 2);
                 dn_hsum_store_i(s, &s_h[c][r][4 * q]);
             }
-            dn_hsum_store_f(f, &s_w[r][4 * q]);
+            if (WEIGHTS) dn_hsum_store_f(f, &s_w[r][4 * q]);
             continue;
         }
 #pragma unroll
@@ -910,6 +932,7 @@ __global__ __launch_bounds__(256) void mb_down_lds_kernel(const StxMbImage* __re
             // instruction measured with the natural order.
             dn_hsum_store_i(s, &s_h[c][r][4 * q]);
         }
+        if (!WEIGHTS) continue;
         const STX_GAS float* wq = gp(reinterpret_cast<const float*>(W_a)) + (uint32_t)sy * wst;
         float f[19];
         if (w_half) {  // level 1 as halves (StxMbImage::w1_f16): the same 19 samples from half the bytes
@@ -972,6 +995,7 @@ __global__ __launch_bounds__(256) void mb_down_lds_kernel(const StxMbImage* __re
                 else o[0] = (short)va;
             }
         }
+        if (!WEIGHTS) continue;
         float fa[5], fb[5];
 #pragma unroll
         for (int k = 0; k < 5; k++) {
@@ -986,7 +1010,7 @@ __global__ __launch_bounds__(256) void mb_down_lds_kernel(const StxMbImage* __re
         else o[0] = wa;
         nz |= __float_as_uint(wa) | (two ? __float_as_uint(wb) : 0u);
     }
-    dn_note_occ(occ, nz, tid, X0, Y0, ow, oh);
+    if (WEIGHTS) dn_note_occ(occ, nz, tid, X0, Y0, ow, oh);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2383,7 +2407,8 @@ bool launched_ok() { return hipGetLastError() == hipSuccess; }
 }  // namespace
 
 // One launch per pyramid level for ALL fed images (grid.z = image).  h_images mirrors d_images.
-bool stx_fast_mb_down_batch(stx_ctx* ctx, const StxMbImage* d_images, const StxMbImage* h_images, int n, int level)
+// weights = false: the G planes alone, for all images of the launch (their W and occupancy maps exist already)
+bool stx_fast_mb_down_batch(stx_ctx* ctx, const StxMbImage* d_images, const StxMbImage* h_images, int n, int level, bool weights)
 {
     int mw = 0, mh = 0;
     for (int i = 0; i < n; i++) {
@@ -2407,9 +2432,13 @@ bool stx_fast_mb_down_batch(stx_ctx* ctx, const StxMbImage* d_images, const StxM
     for (int i = 0; i < n; i++) pk_ok = pk_ok && !h_images[i].img0_is_s16 && h_images[i].mask_binary;
     dim3 grid(stx_tile_grid(M), 1, n);
     static const unsigned pad_lds = getenv("STITCHING_AMD_D0_LDS") ? (unsigned)atoi(getenv("STITCHING_AMD_D0_LDS")) : 0u;  // diagnostic, see stx_warp.hip
-    if (level == 0 && pk_ok) hipLaunchKernelGGL(mb_down0_lds_kernel<true>, grid, dim3(256), pad_lds, ctx->stream, d_images, M);
-    else if (level == 0) hipLaunchKernelGGL(mb_down0_lds_kernel<false>, grid, dim3(256), 0, ctx->stream, d_images, M);
-    else hipLaunchKernelGGL(mb_down_lds_kernel, grid, dim3(256), 0, ctx->stream, d_images, level, M);
+    if (!weights) {
+        if (level == 0 && pk_ok) hipLaunchKernelGGL((mb_down0_lds_kernel<true, false>), grid, dim3(256), pad_lds, ctx->stream, d_images, M);
+        else if (level == 0) hipLaunchKernelGGL((mb_down0_lds_kernel<false, false>), grid, dim3(256), 0, ctx->stream, d_images, M);
+        else hipLaunchKernelGGL(mb_down_lds_kernel<false>, grid, dim3(256), 0, ctx->stream, d_images, level, M);
+    } else if (level == 0 && pk_ok) hipLaunchKernelGGL((mb_down0_lds_kernel<true, true>), grid, dim3(256), pad_lds, ctx->stream, d_images, M);
+    else if (level == 0) hipLaunchKernelGGL((mb_down0_lds_kernel<false, true>), grid, dim3(256), 0, ctx->stream, d_images, M);
+    else hipLaunchKernelGGL(mb_down_lds_kernel<true>, grid, dim3(256), 0, ctx->stream, d_images, level, M);
     return launched_ok();
 }
 

@@ -37,6 +37,11 @@ static void blender_release(stx_blender* b)
     b->held.clear();
     for (void* p : b->pyr_allocs) stx_dev_free(b->ctx, p);
     b->pyr_allocs.clear();
+    for (void* p : b->wt_allocs) stx_dev_free(b->ctx, p);
+    b->wt_allocs.clear();
+    stx_mb_weights_release(b->keep);
+    stx_mb_weights_release(b->adopted);
+    b->keep = b->adopted = nullptr;
     b->d_all = nullptr;
     b->images.clear();
     b->built.clear();
@@ -200,7 +205,7 @@ static int mb_feed(stx_blender* b, const stx_buf* img, const stx_buf* mask, int 
         STX_TRY(stx_dev_alloc(ctx, MB_FRONT_PAD + (size_t)gs * lh * 3 * (im.g_u8 ? 1 : sizeof(short)) + 64, &g));
         b->pyr_allocs.push_back(g);
         STX_TRY(stx_dev_alloc(ctx, (size_t)ws * lh * ((i == 1 && im.w1_f16) ? sizeof(uint16_t) : sizeof(float)), &wt));
-        b->pyr_allocs.push_back(wt);
+        b->wt_allocs.push_back(wt);
         im.g[i] = (short*)((uint8_t*)g + MB_FRONT_PAD); im.g_stride[i] = gs; im.g_plane[i] = gs * lh;
         im.wt[i] = (float*)wt; im.wt_stride[i] = ws;
     }
@@ -236,7 +241,8 @@ static int mb_ensure_pyramids(stx_blender* b)
     // the batched LDS kernels, which write them (int16 sources take the generic level-0 kernel).
     static const bool occ_off = getenv("STITCHING_AMD_NO_OCC") != nullptr;  // diagnostic: A/B of the bookkeeping
     const int pyr = b->pyr_mode;  // (the blender's own, fixed at creation) != scalar: the generic kernels build every level, and they keep no occupancy maps
-    if (todo.size() <= 65535 && !occ_off && (pyr & 255) == STX_PYRDOWN_SCALAR) {
+    // (adopted weights: the maps came with them, and todo is every image of the blender — stx_blend_use_weights)
+    if (!b->adopted && todo.size() <= 65535 && !occ_off && (pyr & 255) == STX_PYRDOWN_SCALAR) {
         const int nl = b->num_bands + 1;
         std::vector<size_t> off(todo.size() * (size_t)nl, 0);
         size_t bytes = 0;
@@ -251,7 +257,7 @@ static int mb_ensure_pyramids(stx_blender* b)
         if (bytes > 0) {
             void* arena = nullptr;
             STX_TRY(stx_dev_alloc(b->ctx, bytes + 16, &arena));
-            b->pyr_allocs.push_back(arena);
+            b->wt_allocs.push_back(arena);
             size_t t = 0;
             for (size_t i = 0; i < b->images.size(); i++) {
                 if (!(b->images[i].kind == 0 && !b->built[i])) continue;
@@ -266,7 +272,7 @@ static int mb_ensure_pyramids(stx_blender* b)
     // every image of the blender in this pass (the usual case): blend() reads the very same table — one upload, one copy dispatch fewer
     // between the pyramids and the collapse
     b->d_all = todo.size() == b->images.size() && memcmp(todo.data(), b->images.data(), sizeof(StxMbImage) * todo.size()) == 0 ? d : nullptr;
-    STX_TRY(stx_launch_mb_pyramids(b->ctx, d, todo.data(), (int)todo.size(), b->num_bands, pyr & 255, pyr >> 8));
+    STX_TRY(stx_launch_mb_pyramids(b->ctx, d, todo.data(), (int)todo.size(), b->num_bands, pyr & 255, pyr >> 8, b->adopted == nullptr));
     for (size_t i = 0; i < b->images.size(); i++) b->built[i] = 1;
     return STX_OK;
 }
@@ -299,6 +305,7 @@ STX_EXPORT int stx_blend_feed_ex(stx_blender* b, const stx_buf* img, const stx_b
 {
     if (!b || !img || !mask) return stx_fail(STX_ERR_INVALID, "null argument");
     if (b->finished) return stx_fail(STX_ERR_STATE, "feed after blend()");
+    if (b->adopted) return stx_fail(STX_ERR_STATE, "feed after stx_blend_use_weights adopted weights");
     if (!b->ctx) return stx_fail(STX_ERR_STATE, "geometry-only blender (created without a context)");
     STX_TRY(stx_set_device(b->ctx));
     // CV_Assert(img.type() == CV_16SC3 [|| CV_8UC3]); CV_Assert(mask.type() == CV_8U)
@@ -429,6 +436,109 @@ static int mb_finish(stx_blender* b, stx_buf* pano, stx_buf* pmask, stx_buf* pan
         }
         STX_TRY(stx_launch_mb_level(ctx, K, mb_level_bytes(b, b->images, lv, K.x0, K.x1, false, pano16 != nullptr)));
     }
+    return STX_OK;
+}
+
+// ---- weight pyramids that outlive a blender (include/stitching_amd.h: stx_blend_keep_weights) --------------------
+void stx_mb_weights_release(stx_mb_weights* w)
+{
+    if (!w || --w->refs > 0) return;
+    if (w->ctx) hipSetDevice(w->ctx->device);
+    for (StxMbKept& k : w->images) stx_buf_release(k.mask);
+    for (void* p : w->allocs) stx_dev_free(w->ctx, p);  // stream-ordered, as blender_release
+    delete w;
+}
+
+// what stx_blend_keep_weights asks of a blender; `built`: also of its finished pyramids (the occupancy maps were recorded)
+static bool mb_weights_eligible(const stx_blender* b, bool built)
+{
+    if (b->kind != STX_BLEND_MULTIBAND || !b->ctx || b->num_bands < 1 || b->adopted) return false;
+    if ((b->pyr_mode & 255) != STX_PYRDOWN_SCALAR || getenv("STITCHING_AMD_NO_OCC") != nullptr || b->images.size() > 65535) return false;
+    for (const StxMbImage& im : b->images) {
+        if (im.kind != 0 || im.img0_is_s16) return false;
+        if (built && !im.occ[1]) return false;
+    }
+    return true;
+}
+
+// blend() succeeded: the weights and occupancy maps of a blender marked by stx_blend_keep_weights move to its handle
+static void mb_hand_over_weights(stx_blender* b)
+{
+    stx_mb_weights* w = b->keep;
+    if (!w || b->images.empty() || !mb_weights_eligible(b, true)) return;
+    // held: (img, mask) of image k at 2 k, 2 k + 1 in FEED order; images is sorted by .order — find every mask by its pointer
+    w->num_bands = b->num_bands; w->pyr_mode = b->pyr_mode;
+    w->rx = b->rx; w->ry = b->ry; w->rw = b->rw; w->rh = b->rh;
+    for (const StxMbImage& im : b->images) {
+        StxMbKept k;
+        memset(&k, 0, sizeof(k));
+        for (size_t h = 1; h < b->held.size(); h += 2)
+            if (b->held[h]->ptr == im.mask0 && (long long)b->held[h]->stride == im.mask0_stride) k.mask = b->held[h];
+        if (!k.mask) {  // (cannot happen: every kind-0 image holds its mask)
+            for (StxMbKept& q : w->images) stx_buf_release(q.mask);
+            w->images.clear();
+            return;
+        }
+        stx_buf_retain(k.mask);
+        k.mask0 = im.mask0; k.mask0_stride = im.mask0_stride; k.mask_binary = im.mask_binary; k.w1_f16 = im.w1_f16;
+        k.iw = im.iw; k.ih = im.ih; k.ix = im.ix; k.iy = im.iy; k.fx = im.fx; k.fy = im.fy; k.fw = im.fw; k.fh = im.fh;
+        k.left = im.left; k.top = im.top;
+        for (int i = 1; i <= b->num_bands; i++) { k.wt[i] = im.wt[i]; k.wt_stride[i] = im.wt_stride[i]; k.occ[i] = im.occ[i]; }
+        w->images.push_back(k);
+    }
+    w->allocs.swap(b->wt_allocs);
+}
+
+STX_EXPORT int stx_blend_keep_weights(stx_blender* b, stx_mb_weights** out)
+{
+    if (!b || !out) return stx_fail(STX_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (b->finished) return stx_fail(STX_ERR_STATE, "keep_weights after blend()");
+    if (b->keep) return stx_fail(STX_ERR_STATE, "keep_weights was already called on this blender");
+    if (b->images.empty() || !mb_weights_eligible(b, false)) return STX_OK;  // not eligible: the blender builds and frees as ever
+    stx_mb_weights* w = new stx_mb_weights();
+    w->ctx = b->ctx;
+    w->refs = 2;  // the caller's and the blender's
+    b->keep = w;
+    *out = w;
+    return STX_OK;
+}
+
+STX_EXPORT int stx_blend_use_weights(stx_blender* b, stx_mb_weights* w, int* out_adopted)
+{
+    if (!b || !w || !out_adopted) return stx_fail(STX_ERR_INVALID, "null argument");
+    *out_adopted = 0;
+    if (b->finished) return stx_fail(STX_ERR_STATE, "use_weights after blend()");
+    if (b->ctx != w->ctx) return stx_fail(STX_ERR_INVALID, "use_weights: the handle belongs to another context (no cross-stream use)");
+    if (b->adopted || b->keep || w->images.empty() || w->images.size() != b->images.size() || !mb_weights_eligible(b, false)) return STX_OK;
+    if (b->num_bands != w->num_bands || b->pyr_mode != w->pyr_mode || b->rx != w->rx || b->ry != w->ry || b->rw != w->rw || b->rh != w->rh)
+        return STX_OK;
+    for (size_t i = 0; i < b->images.size(); i++) {
+        const StxMbImage& im = b->images[i];
+        const StxMbKept& k = w->images[i];
+        if (b->built[i]) return STX_OK;
+        if (im.mask0 != k.mask0 || im.mask0_stride != k.mask0_stride || im.mask_binary != k.mask_binary || im.w1_f16 != k.w1_f16 ||
+            im.iw != k.iw || im.ih != k.ih || im.ix != k.ix || im.iy != k.iy || im.fx != k.fx || im.fy != k.fy || im.fw != k.fw ||
+            im.fh != k.fh || im.left != k.left || im.top != k.top)
+            return STX_OK;
+        for (int l = 1; l <= b->num_bands; l++)
+            if (im.wt_stride[l] != k.wt_stride[l]) return STX_OK;
+    }
+    STX_TRY(stx_set_device(b->ctx));
+    for (size_t i = 0; i < b->images.size(); i++)
+        for (int l = 1; l <= b->num_bands; l++) { b->images[i].wt[l] = w->images[i].wt[l]; b->images[i].occ[l] = w->images[i].occ[l]; }
+    for (void* p : b->wt_allocs) stx_dev_free(b->ctx, p);  // the blender's own, untouched
+    b->wt_allocs.clear();
+    b->d_all = nullptr;
+    w->refs++;
+    b->adopted = w;
+    *out_adopted = 1;
+    return STX_OK;
+}
+
+STX_EXPORT int stx_mb_weights_free(stx_mb_weights* w)
+{
+    stx_mb_weights_release(w);
     return STX_OK;
 }
 
@@ -569,6 +679,7 @@ STX_EXPORT int stx_blend_feed_contrib_ex(stx_blender* b, int order, const int re
     if (!b || !rect_xywh || !packed) return stx_fail(STX_ERR_INVALID, "null argument");
     if (b->kind != STX_BLEND_MULTIBAND) return stx_fail(STX_ERR_UNSUPPORTED, "multi-band blender only");
     if (b->finished) return stx_fail(STX_ERR_STATE, "feed after blend()");
+    if (b->adopted) return stx_fail(STX_ERR_STATE, "feed after stx_blend_use_weights adopted weights");
     if (!b->ctx) return stx_fail(STX_ERR_STATE, "geometry-only blender (created without a context)");
     const int nb = b->num_bands, al = (1 << nb) - 1;
     const int x = rect_xywh[0], y = rect_xywh[1], w = rect_xywh[2], h = rect_xywh[3];
@@ -656,6 +767,7 @@ STX_EXPORT int stx_blend_finish_ex(stx_blender* b, stx_buf** out_pano_u8, stx_bu
         if (b->kind == STX_BLEND_NO) return no_finish(b, pano.get(), pmask.get(), p16.get());
         return feather_finish(b, pano.get(), pmask.get(), p16.get());
     }();
+    if (rc == STX_OK) mb_hand_over_weights(b);
     // whatever the outcome, the blender is spent
     b->finished = true;
     blender_release(b);  // stream-ordered: the kernels above were enqueued before any reuse

@@ -65,7 +65,7 @@ struct MbLevelK {
 
 // fast-path launchers (stx_blend_fast.hip); each returns false when its alignment / size
 // preconditions do not hold and the generic kernel must be used instead.
-bool stx_fast_mb_down_batch(stx_ctx* ctx, const StxMbImage* d_images, const StxMbImage* h_images, int n, int level);
+bool stx_fast_mb_down_batch(stx_ctx* ctx, const StxMbImage* d_images, const StxMbImage* h_images, int n, int level, bool weights);
 bool stx_fast_mb_level(stx_ctx* ctx, const MbLevelK& K);
 
 // batched strip export: see stx_blend_fast.hip

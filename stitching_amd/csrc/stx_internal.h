@@ -236,8 +236,9 @@ struct StxMbImage {  // device-visible descriptor of one fed image (all levels)
     uint8_t* occ[STX_MAX_BANDS + 1];
 };
 // pyr_mode / pyr_lanes: STX_PYRDOWN_* (include/stitching_amd.h); anything but SCALAR builds every level with the generic kernels
+// weights = false: the G planes alone (all images of the call; their weights were adopted from a stx_mb_weights handle)
 int stx_launch_mb_pyramids(stx_ctx* ctx, const StxMbImage* d_images, const StxMbImage* h_images, int n, int num_bands, int pyr_mode,
-                           int pyr_lanes);
+                           int pyr_lanes, bool weights);
 struct MbLevelK;
 int stx_launch_mb_level(stx_ctx* ctx, const MbLevelK& K, double algo_bytes);
 int stx_launch_mb_coarse(stx_ctx* ctx, const MbLevelK& K_level_Bm2, double algo_bytes);  // levels B, B-1, B-2 in one launch
@@ -375,6 +376,11 @@ struct stx_blender {
     std::vector<char> built;          // pyramid of images[i] exists (kind 0)
     std::vector<stx_buf*> held;
     std::vector<void*> pyr_allocs;
+    std::vector<void*> wt_allocs;     // the weight pyramids wt[1..B] of the fed images and the occupancy arena: the part of a blender that
+                                      // depends on the masks and the geometry alone; moved to `keep` at blend() when one is set
+    stx_mb_weights* keep = nullptr;   // stx_blend_keep_weights: filled at blend() (one reference held until then)
+    stx_mb_weights* adopted = nullptr;  // stx_blend_use_weights: the handle whose weights the images point to (one reference held);
+                                      // the pyramids are then built without their weight half
     StxMbImage* d_all = nullptr;      // device copy of `images` as the pyramid pass uploaded it, while it still equals `images` (else null)
     int band_x0 = 0, band_x1 = 0;     // columns of the final roi this blender produces (sharded blending)
     int next_order = 0;
@@ -385,6 +391,23 @@ struct stx_blender {
     // feather: deferred gather as well (stx_launch_feather_weights / _gather)
     std::vector<FeatherImg> feather_images;
 };
+// weight pyramids that outlive their blender (stx_blend_keep_weights / stx_blend_use_weights) --------------------------------------
+struct StxMbKept {  // what the weights of one fed image depend on, and the weights
+    stx_buf* mask;  // (one reference held: the memory cannot be handed out again while the record compares pointers with it)
+    const uint8_t* mask0; long long mask0_stride; int mask_binary, w1_f16;
+    int iw, ih, ix, iy, fx, fy, fw, fh, left, top;
+    float* wt[STX_MAX_BANDS + 1]; long long wt_stride[STX_MAX_BANDS + 1];
+    uint8_t* occ[STX_MAX_BANDS + 1];
+};
+struct stx_mb_weights {
+    stx_ctx* ctx = nullptr;
+    std::atomic<int> refs{1};  // (Python finalizers may drop handles from any thread)
+    int num_bands = 0, pyr_mode = 0;
+    int rx = 0, ry = 0, rw = 0, rh = 0;
+    std::vector<StxMbKept> images;  // in feed order; empty until the blender it was taken from has blended
+    std::vector<void*> allocs;
+};
+void stx_mb_weights_release(stx_mb_weights* w);
 // MultiBandBlender::feed geometry: the feed rectangle (tl_new .. br_new) relative to the padded roi
 void mb_feed_rect(const stx_blender* b, int w, int h, int tlx, int tly, int* fx, int* fy, int* fw, int* fh);
 // level-0 column range [sx0, sx1) of the contribution an image fed at [fx, fx + fw) owes the owner of the columns [bx0, bx1)

@@ -102,16 +102,54 @@ def _split_cropper(cropper, crop_aspect):
     return cropper, crop_aspect
 
 
+class _RigGeometry:
+    """What a panorama of a rig needs besides its pixels (StitchJob keeps one between runs): the rectangles to warp, where and with which
+    masks they are fed, what the blender is prepared on — and the blender's weight pyramids, which follow from all of that."""
+
+    __slots__ = ("key", "rects", "prep_corners", "prep_sizes", "feed_corners", "feed_masks", "blend_strength", "crop", "gain_in_warp",
+                 "gain_corners", "gain_sub", "weights", "blender")
+
+    def __init__(self):
+        self.key = self.weights = self.crop = self.gain_corners = self.gain_sub = None
+        self.blender = None  # the pass's own prepared blender, where it needed one before its warps: taken by the run that made it
+        self.gain_in_warp = True
+
+
+def rig_key(cam_bytes, camera_aspect, warper_type, scale, sizes, blender_type, num_bands, blend_strength, modes, cropper, crop_aspect):
+    """Everything the geometry of a rig depends on, as one hashable value: cameras (the K, R arrays as bytes) and their aspect, warper and
+    the scale as it is NOW (Warper.set_scale may follow the constructor), frame sizes, blender and its width (num_bands where given — the
+    strength is then derived from it and the ROIs — else blend_strength), the process-wide trig / remap / pyrDown modes, the cropper's
+    rectangles and aspect.  The compensator is no part of it: gains change pixels, never a rectangle or a mask."""
+    crop = None
+    if cropper is not None:
+        crop = (tuple(tuple(int(v) for v in r) for r in cropper.intersection_rectangles), float(crop_aspect))
+    return (cam_bytes, float(camera_aspect), str(warper_type), None if scale is None else float(scale), tuple((int(w), int(h)) for w, h in sizes),
+            str(blender_type), None if num_bands is None else int(num_bands), float(blend_strength) if num_bands is None else None,
+            tuple(modes), crop)
+
+
+def masks_belong_to_job(feed_masks, seam_masks):
+    """The condition of geometry reuse (and of the seam-cell crops): no mask input, or host arrays — the job uploaded its own copies.  A
+    mask given as a device array may be rewritten by its owner between runs."""
+    given = feed_masks if feed_masks is not None else seam_masks
+    return given is None or all(isinstance(m, np.ndarray) for m in given)
+
+
 class StitchJob:
-    """Pre-staged inputs of one panorama: device-resident source frames + cameras."""
+    """Pre-staged inputs of one panorama — or of the panoramas of one rig: device-resident source frames + cameras.
+
+    Between runs the job keeps what does not depend on the pixels (reuse_geometry=True): the ROIs, the rectangles it warps, the masks it
+    feeds (the warped masks after SeamFinder.resize_all, slicing or cropping) and the weight pyramids of the multi-band blender — device
+    memory of about P_w + 0.8 P_f bytes (P_w: pixels of the warped masks, P_f: pixels of the feed rectangles; roughly 150 MB for eight
+    4000 x 3000 frames at 5 bands) until release_geometry() or the end of the job.  Warped images are never kept."""
 
     def __init__(self, frames, cameras, warper_type="spherical", blender_type="multiband", num_bands=None,
                  blend_strength=Blender.DEFAULT_BLEND_STRENGTH, ctx=None, async_upload=False, feed_masks=None, seam_masks=None,
-                 crop_to_masks=True, compensator=None, cropper=None, crop_aspect=1, camera_aspect=1):
+                 crop_to_masks=True, compensator=None, cropper=None, crop_aspect=1, camera_aspect=1, reuse_geometry=True):
         """async_upload: numpy frames in page-locked memory (pinned_empty) are only queued for upload; they must stay
         untouched until ctx.sync() (a streaming caller alternates two contexts).
         feed_masks: final-resolution u8 masks fed to the blender instead of the warped masks (seam masks already at the
-        warped size); seam_masks: LOW-resolution seam masks, resized on the device every run exactly as the reference
+        warped size); seam_masks: LOW-resolution seam masks, resized on the device exactly as the reference
         does per panorama (SeamFinder.resize, stitching/stitcher.py:124: dilate, INTER_LINEAR_EXACT, AND with the warped
         mask) — its grey edges make the masks non-binary.
         crop_to_masks (multi-band blender, feed_masks / seam_masks given as host arrays): a seam mask keeps one cell of its
@@ -127,7 +165,12 @@ class StitchJob:
         crop_aspect): byte for byte "warp whole, Cropper.crop_images, feed".  feed_masks / seam_masks then belong to the CROPPED images,
         and the block compensators' gain maps lie over the cropped image (apply on a cropped image, as in the reference) — a seam-cell
         crop inside it carries its offset in the cropped image.
-        camera_aspect: the frames are camera_aspect times the size the cameras were estimated on (Warper's `aspect`)."""
+        camera_aspect: the frames are camera_aspect times the size the cameras were estimated on (Warper's `aspect`).
+        reuse_geometry: the first run() makes the geometry of the rig (ROI pass, warped masks, seam-mask resize, weight pyramids) and
+        keeps it under rig_key(...); a later run with an equal key warps the images alone into the kept rectangles, feeds the kept masks
+        and builds its pyramids without their weight half — the same bytes, made once.  A key that differs (Warper.set_scale with other
+        cameras, a process-wide arithmetic mode, ...) drops the kept state, and that run is a first run.  Only where every mask input
+        belongs to the job (masks_belong_to_job); jobs with device-array masks, and reuse_geometry=False, redo everything every run."""
         cropper, crop_aspect = _split_cropper(cropper, crop_aspect)
         if len(frames) != len(cameras) or not frames:
             raise StitchingError("need one camera per frame and at least one frame")
@@ -146,6 +189,7 @@ class StitchJob:
         if cropper is not None and len(cropper.intersection_rectangles) != len(self.frames):
             raise StitchingError(f"the cropper was prepared on {len(cropper.intersection_rectangles)} images, the job has {len(self.frames)}")
         self._cam_arrays = self.warper.camera_arrays(self.cameras, camera_aspect)  # K, R as the batched entry points take them: built once
+        self._cam_bytes = self._cam_arrays[0].tobytes() + self._cam_arrays[1].tobytes()
         # per mask the columns [a, b) and rows [c, d) that hold a non-zero value, and the mask's size (host arrays only: no
         # read-back here)
         self._mask_cols = None
@@ -153,6 +197,9 @@ class StitchJob:
         if crop_to_masks and given is not None and all(isinstance(m, np.ndarray) for m in given):
             self._mask_cols = [mask_box(m) for m in given]
         self._crop_cache = None
+        self.reuse_geometry = bool(reuse_geometry) and masks_belong_to_job(feed_masks, seam_masks)
+        self._geometry = None
+        self.last_reused = self.last_weights_adopted = False  # of the last run: kept geometry used / weight pyramids adopted by its blender
         self.feed_masks = None if feed_masks is None else [as_device(m, self.ctx) for m in feed_masks]
         self.seam_masks = None if seam_masks is None else [as_device(m, self.ctx) for m in seam_masks]
 
@@ -182,63 +229,125 @@ class StitchJob:
             self._crop_cache = (key, view_rects(handle, corners, sizes, self._mask_cols))
         return self._crop_cache[1]
 
-    def run(self):
-        """warp every frame, feed it, blend.  Returns device-resident (panorama u8x3, mask u8)."""
-        # one panorama = one ROI pass (the reference's eager Warper.warp_rois, stitching/stitcher.py:188): it belongs to the pass and
-        # is re-run every time (batched: one device pass, one wait).  It is the ONE point where the host waits for the device and
-        # the device then waits for the host: without seam-cell crops (which need the ROIs before the warps) pass and warps are one
-        # native call, and everything Python does with the ROIs happens behind the warp launch (profiles/r05_latency.md)
+    def set_frames(self, frames):
+        """New frames of the same rig: the same number, the same sizes (ComposePlan.check_frames's rule)."""
+        frames = list(frames)
+        got = [Images.get_image_size(f) for f in frames]
+        if got != [tuple(z) for z in self.sizes]:
+            raise StitchingError(f"the job was made for frames of sizes {self.sizes}, got {got}: same rig, same sizes")
+        self.frames = [as_device(f, self.ctx) for f in frames]
+
+    def release_geometry(self):
+        """Drop what the job keeps between runs (masks, weight pyramids: see the class docstring); the next run is a first run."""
+        g, self._geometry = self._geometry, None
+        if g is not None and g.weights is not None:
+            g.weights.free()
+
+    def geometry_key(self):
+        """rig_key of the job as it stands now"""
+        modes = (config.trig_mode(), config.remap_mode()) + tuple(config.pyrdown_mode())
+        return rig_key(self._cam_bytes, self.camera_aspect, self.warper.warper_type, self.warper.scale, self.sizes, self.blender_type,
+                       self.num_bands, self.blend_strength, modes, self.cropper, self.crop_aspect)
+
+    def run(self, frames=None):
+        """warp every frame, feed it, blend.  Returns device-resident (panorama u8x3, mask u8).
+        frames: new frames of the same sizes — the next panorama of the same rig (set_frames)."""
+        if frames is not None:
+            self.set_frames(frames)
         prev = config.device_resident()
         config.set_device_resident(True)
         try:
-            if self.cropper is not None:
-                return self._run_cropped()
-            warped = None
-            if self._mask_cols is None:
-                warped = self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect, compensator=self.compensator,
-                                                           with_rois=True, camera_arrays=self._cam_arrays)
-                self._adopt([r[0:2] for r in warped[2]], [r[2:4] for r in warped[2]])
+            key = self.geometry_key() if self.reuse_geometry else None
+            g = self._geometry
+            if g is not None and g.key != key:
+                self.release_geometry()
+                g = None
+            self.last_reused, self.last_weights_adopted = g is not None, False
+            if g is None:
+                g, imgs = self._geometry_pass()
+                g.key = key
             else:
-                self.plan()
-            blender = Blender(self.blender_type, self.blend_strength, ctx=self.ctx)
-            blender.prepare(self.corners, self.warped_sizes)
-            crop = None
-            if self._mask_cols is not None and blender.blender.kind == _lib.BLEND_MULTIBAND:
-                crop = self._crop_rects(blender.blender, self.corners, self.warped_sizes)
-            if crop is not None:
-                box = [c if c is not None else (0, w, 0, h) for c, (w, h) in zip(crop, self.warped_sizes)]
-                rects = [(cx + x0, cy + y0, x1 - x0, y1 - y0) for (x0, x1, y0, y1), (cx, cy) in zip(box, self.corners)]
-                imgs, masks, rois = self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect, rects=rects,
-                                                                      compensator=self.compensator, camera_arrays=self._cam_arrays)
-                if self.feed_masks is not None:
-                    masks = [m[y0:y1, x0:x1] for m, (x0, x1, y0, y1) in zip(self.feed_masks, box)]
-                else:
-                    masks = SeamFinder.resize_all(self.seam_masks, masks,
-                                                  sub=[(w, h, x0, y0) for (x0, x1, y0, y1), (w, h) in zip(box, self.warped_sizes)])
-                corners = [(r[0], r[1]) for r in rects]
-            else:
-                imgs, masks, rois = warped or self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect,
-                                                                                compensator=self.compensator, camera_arrays=self._cam_arrays)
-                if self.feed_masks is not None:
-                    masks = self.feed_masks
-                elif self.seam_masks is not None:
-                    masks = SeamFinder.resize_all(self.seam_masks, masks)
-                corners = self.corners
-                for roi, corner in zip(rois, self.corners):
-                    if roi[0:2] != tuple(corner):
-                        raise StitchingError("warp roi changed between plan() and run()")
-            self.last_crop = crop
-            for img, mask, corner in zip(imgs, masks, corners):
+                # a panorama of a known rig: the images alone, into the kept rectangles (no ROI pass, no wait, no mask, no seam_resize)
+                imgs, _, _ = self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect, rects=g.rects,
+                                                               compensator=self.compensator if g.gain_in_warp else None,
+                                                               camera_arrays=self._cam_arrays, masks=False)
+                if self.compensator is not None and not g.gain_in_warp:
+                    imgs = self.compensator.apply_all(g.gain_corners, imgs, None, sub=g.gain_sub, ctx=self.ctx)
+            self.last_crop = g.crop
+            blender, g.blender = g.blender, None
+            if blender is None:
+                blender = Blender(self.blender_type, g.blend_strength, ctx=self.ctx)
+                blender.prepare(g.prep_corners, g.prep_sizes)
+            for img, mask, corner in zip(imgs, g.feed_masks, g.feed_corners):
                 blender.feed(img, mask, corner)
             self.last_num_bands = blender.blender.num_bands()
+            if key is not None and blender.blender.kind == _lib.BLEND_MULTIBAND:
+                if not self.last_reused:
+                    g.weights = blender.blender.keep_weights()  # filled by blend(); None where the blender does not qualify
+                elif g.weights is not None:
+                    # all images or none: a blender that adopts nothing builds as ever
+                    self.last_weights_adopted = blender.blender.use_weights(g.weights)
             pano, pmask = blender.blend()
+            if key is not None:
+                self._geometry = g
         finally:
             config.set_device_resident(prev)
         return pano, pmask
 
-    def _run_cropped(self):
-        """run() with a cropper (device residency is on): the ROI pass first, then only the cropper's rectangle of every image — and
-        inside it, with host seam masks and the multi-band blender, only what the seam cell can reach (view_rects)."""
+    def _geometry_pass(self):
+        """The first run of a rig (every run of a job that keeps nothing): ROI pass, warps WITH masks, the masks' way to the blender.
+        -> (_RigGeometry, warped images).  The one piece of code that decides rectangles, feed corners and feed masks, for the plain path,
+        the seam-cell crops and a cropper alike."""
+        # one ROI pass (the reference's eager Warper.warp_rois, stitching/stitcher.py:188), batched: one device pass, one wait.  It is the
+        # ONE point where the host waits for the device and the device then waits for the host: without seam-cell crops (which need the
+        # ROIs before the warps) pass and warps are one native call, and everything Python does with the ROIs happens behind the warp
+        # launch (profiles/r05_latency.md)
+        g = _RigGeometry()
+        if self.cropper is not None:
+            return self._geometry_pass_cropped(g)
+        warped = None
+        if self._mask_cols is None:
+            warped = self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect, compensator=self.compensator,
+                                                       with_rois=True, camera_arrays=self._cam_arrays)
+            self._adopt([r[0:2] for r in warped[2]], [r[2:4] for r in warped[2]])
+        else:
+            self.plan()
+        g.blender = Blender(self.blender_type, self.blend_strength, ctx=self.ctx)
+        g.blender.prepare(self.corners, self.warped_sizes)
+        crop = None
+        if self._mask_cols is not None and g.blender.blender.kind == _lib.BLEND_MULTIBAND:
+            crop = self._crop_rects(g.blender.blender, self.corners, self.warped_sizes)
+        if crop is not None:
+            box = [c if c is not None else (0, w, 0, h) for c, (w, h) in zip(crop, self.warped_sizes)]
+            rects = [(cx + x0, cy + y0, x1 - x0, y1 - y0) for (x0, x1, y0, y1), (cx, cy) in zip(box, self.corners)]
+            imgs, masks, rois = self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect, rects=rects,
+                                                                  compensator=self.compensator, camera_arrays=self._cam_arrays)
+            if self.feed_masks is not None:
+                masks = [m[y0:y1, x0:x1] for m, (x0, x1, y0, y1) in zip(self.feed_masks, box)]
+            else:
+                masks = SeamFinder.resize_all(self.seam_masks, masks,
+                                              sub=[(w, h, x0, y0) for (x0, x1, y0, y1), (w, h) in zip(box, self.warped_sizes)])
+            corners = [(r[0], r[1]) for r in rects]
+        else:
+            imgs, masks, rois = warped or self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect,
+                                                                            compensator=self.compensator, camera_arrays=self._cam_arrays)
+            if self.feed_masks is not None:
+                masks = self.feed_masks
+            elif self.seam_masks is not None:
+                masks = SeamFinder.resize_all(self.seam_masks, masks)
+            corners = self.corners
+            for roi, corner in zip(rois, self.corners):
+                if roi[0:2] != tuple(corner):
+                    raise StitchingError("warp roi changed between plan() and run()")
+            rects = [(cx, cy, w, h) for (cx, cy), (w, h) in zip(self.corners, self.warped_sizes)]
+        g.rects, g.crop = [tuple(int(v) for v in r) for r in rects], crop
+        g.prep_corners, g.prep_sizes, g.blend_strength = list(self.corners), list(self.warped_sizes), self.blend_strength
+        g.feed_corners, g.feed_masks = list(corners), list(masks)
+        return g, imgs
+
+    def _geometry_pass_cropped(self, g):
+        """_geometry_pass with a cropper (device residency is on): the ROI pass first, then only the cropper's rectangle of every image —
+        and inside it, with host seam masks and the multi-band blender, only what the seam cell can reach (view_rects)."""
         self.plan()
         cuts = [clip_rectangle(r.times(self.crop_aspect), w, h) for r, (w, h) in zip(self.cropper.intersection_rectangles, self.warped_sizes)]
         cut_sizes = [(x1 - x0, y1 - y0) for x0, x1, y0, y1 in cuts]
@@ -270,13 +379,11 @@ class StitchJob:
             masks = [m if b == (0, m.width, 0, m.height) else m[b[2]:b[3], b[0]:b[1]] for m, b in zip(self.feed_masks, box)]
         elif self.seam_masks is not None:
             masks = SeamFinder.resize_all(self.seam_masks, masks, sub=sub)
-        self.last_crop = crop
-        blender = Blender(self.blender_type, self.blend_strength, ctx=self.ctx)
-        blender.prepare(corners, sizes)
-        for img, mask, (cx, cy), b in zip(imgs, masks, corners, box):
-            blender.feed(img, mask, (cx + b[0], cy + b[2]))
-        self.last_num_bands = blender.blender.num_bands()
-        return blender.blend()
+        g.rects, g.crop = [tuple(int(v) for v in r) for r in rects], crop
+        g.gain_in_warp, g.gain_corners, g.gain_sub = False, corners, sub
+        g.prep_corners, g.prep_sizes, g.blend_strength = corners, sizes, self.blend_strength
+        g.feed_corners, g.feed_masks = [(cx + b[0], cy + b[2]) for (cx, cy), b in zip(corners, box)], list(masks)
+        return g, imgs
 
 
 def compose(frames, cameras, warper_type="spherical", blender_type="multiband", blend_strength=Blender.DEFAULT_BLEND_STRENGTH,
@@ -329,13 +436,15 @@ def compose(frames, cameras, warper_type="spherical", blender_type="multiband", 
 class ComposePlan:
     """What the low-resolution half of a composition leaves (Composer.prepare), device-resident: the prepared cropper, the compensator
     with its gains, the low-resolution seam masks and the scales.  Valid for every set of frames of the same rig (same sizes, same
-    cameras): Composer.run(plan, images=new_frames)."""
+    cameras): Composer.run(plan, images=new_frames).  The plan also carries the StitchJob of its final-resolution half, which keeps the
+    rig's masks and weight pyramids between runs (StitchJob's memory note; `plan.job.release_geometry()` gives them back)."""
 
     def __init__(self, images, frames, cameras, warper_scale, cropper, compensator, seam_masks, seam_masks_host, low_corners, low_sizes):
         self.images, self.frames, self.cameras, self.warper_scale = images, frames, list(cameras), warper_scale
         self.cropper, self.compensator, self.seam_masks, self.seam_masks_host = cropper, compensator, seam_masks, seam_masks_host
         self.low_corners, self.low_sizes = low_corners, low_sizes
         self.frame_sizes = images.sizes
+        self.job = self.job_key = None  # Composer.run's StitchJob for this plan: the rig's geometry is made once (StitchJob)
         R = Images.Resolution
         self.camera_aspect = images.get_ratio(R.MEDIUM, R.FINAL)
         self.lir_aspect = images.get_ratio(R.LOW, R.FINAL)
@@ -449,11 +558,17 @@ class Composer:
             final = list(plan.images.resize(Images.Resolution.FINAL, frames))
         finally:
             config.set_device_resident(prev)
-        job = StitchJob(final, plan.cameras, warper_type=st["warper_type"], blender_type=st["blender_type"],
-                        blend_strength=st["blend_strength"], ctx=ctx,
-                        seam_masks=plan.seam_masks_host if plan.seam_masks_host is not None else plan.seam_masks,
-                        compensator=plan.compensator, cropper=plan.cropper, crop_aspect=plan.lir_aspect, camera_aspect=plan.camera_aspect)
-        return job.run()
+        # one job per plan: its second run warps pixels only (same rig, new frames)
+        job_key = (id(ctx), st["warper_type"], st["blender_type"], st["blend_strength"])
+        if plan.job is None or plan.job_key != job_key:
+            plan.job = StitchJob(final, plan.cameras, warper_type=st["warper_type"], blender_type=st["blender_type"],
+                                 blend_strength=st["blend_strength"], ctx=ctx,
+                                 seam_masks=plan.seam_masks_host if plan.seam_masks_host is not None else plan.seam_masks,
+                                 compensator=plan.compensator, cropper=plan.cropper, crop_aspect=plan.lir_aspect,
+                                 camera_aspect=plan.camera_aspect)
+            plan.job_key = job_key
+            return plan.job.run()
+        return plan.job.run(frames=final)
 
     def compose(self, images, cameras):
         """prepare + run -> the panorama (device-resident u8x3), as Stitcher.stitch returns it"""

@@ -154,7 +154,7 @@ class Warper:
                                                     src._h, C.byref(oi), C.byref(om), roi))
         return (self._result(DeviceImage(ctx, oi)), self._result(DeviceImage(ctx, om)), tuple(int(v) for v in roi))
 
-    def warp_images_and_masks(self, imgs, cameras, aspect=1, rects=None, compensator=None, with_rois=False, camera_arrays=None):
+    def warp_images_and_masks(self, imgs, cameras, aspect=1, rects=None, compensator=None, with_rois=False, camera_arrays=None, masks=True):
         """Batched form of warp_images + create_and_warp_masks (stitching/warper.py:39-41, 54-56) for a list of
         images: one ROI pass, one table launch and one remap launch for all of them (stx_warp_batch).
         Returns (warped_images, warped_masks, rois).
@@ -165,7 +165,9 @@ class Warper:
         when it can).  Equal to compensator.apply_all on the plain result, byte for byte.
         with_rois (no rects): the ROI pass is made by this call, on the device, whatever earlier calls have cached, and the warps are
         launched right behind it from native code (stx_warp_batch_with_rois: a panorama's latency, see StitchJob.run).
-        camera_arrays: Warper.camera_arrays(cameras, aspect), for callers that keep it."""
+        camera_arrays: Warper.camera_arrays(cameras, aspect), for callers that keep it.
+        masks=False (with rects): the images alone — no mask is written, None comes back in their place (a caller that kept the masks
+        of an earlier call with the same cameras and rectangles: StitchJob)."""
         ctx = self._ctx()
         srcs = [self._source(img, ctx) for img in imgs]
         cameras = list(cameras)
@@ -175,6 +177,10 @@ class Warper:
         Ks, Rs = camera_arrays if camera_arrays is not None else self.camera_arrays(cameras[:n], aspect)
         h_src = (C.c_void_p * n)(*[s._h for s in srcs[:n]])
         h_img, h_mask = (C.c_void_p * n)(), (C.c_void_p * n)()
+        if not masks:
+            if rects is None:
+                raise StitchingError("masks=False needs rects: the rectangles of the call that made the masks")
+            h_mask = None
         rois = np.zeros((n, 4), np.int32)
         blocks = compensator is not None and compensator.compensator_type in ("gain_blocks", "channel_blocks")
         if blocks and compensator.gains is None:
@@ -213,7 +219,7 @@ class Warper:
             finally:
                 config.set_device_resident(prev)
         imgs_out = [self._result(d) for d in d_imgs]
-        masks_out = [self._result(DeviceImage(ctx, C.c_void_p(h_mask[i]))) for i in range(n)]
+        masks_out = None if h_mask is None else [self._result(DeviceImage(ctx, C.c_void_p(h_mask[i]))) for i in range(n)]
         return imgs_out, masks_out, [tuple(int(v) for v in r) for r in rois]
 
     # ------------------------------------------------------------------ helpers

@@ -888,8 +888,15 @@ __global__ __launch_bounds__(WARP_FW) __attribute__((amdgpu_waves_per_eu(8, 8)))
     if (it >= n_blocks) break;
     const int y0 = (tile_y * WARP_IT + it) * WARP_TH;
     const bool wave_int = (int_blocks >> it) & 1u;
-    const bool full = y0 + WARP_TH <= dh && (long long)xw * 3 + 192 <= dimg_stride && dimg_stride < (1ll << 24) &&
-                      (long long)xw + 64 <= dmask_stride && dmask_stride < (1ll << 24);
+    // Full tile: every lane stores its 12 (4) bytes unpredicated, with the gain fetched behind the tables.  The test asks only about the
+    // outputs this instantiation WRITES — the host leaves the stride of an output nobody asked for at 0, and a term on it sends every
+    // wavefront of an image-only or mask-only launch down the edge path (with a gain: its dependent loads, three times per lane):
+    //   y0 + WARP_TH <= dh        all 4 rows of the block lie inside the image (both outputs);
+    //   xw * 3 + 192 <= stride    (image) the 64 columns' 192 bytes end inside the row pitch; xw + 64 <= stride for the mask's 64 bytes;
+    //   stride < 2^24             the row offset r * stride of that output is a __umul24.
+    bool full = y0 + WARP_TH <= dh;
+    if (IMG) full = full && (long long)xw * 3 + 192 <= dimg_stride && dimg_stride < (1ll << 24);
+    if (MASK) full = full && (long long)xw + 64 <= dmask_stride && dmask_stride < (1ll << 24);
     if (full) {
         if (IMG) {
             const uint32_t* sp = &s_px[wv][4 * it][0] + lane * 3;

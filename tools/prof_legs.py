@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Per-kernel HIP-event table of an operating point other than the bench default (one panorama at a time).
-usage: python tools/prof_legs.py [seams|voronoi|defaults|config4|feather|no|config3] [steps]"""
+usage: python tools/prof_legs.py [seams|voronoi|defaults|config4|feather|no|config3] [steps] [noreuse]
+noreuse (defaults leg): every run is a first run (reuse_geometry=False) - ROI pass, image + mask warp, weight pyramids."""
 import os
 import sys
 
@@ -15,6 +16,7 @@ from stitching_amd.pipeline import StitchJob  # noqa: E402
 def main():
     leg = sys.argv[1] if len(sys.argv) > 1 else "seams"
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    reuse = "noreuse" not in sys.argv[3:]
     ctx = S.get_context()
     W, H = 4000, 3000
     if leg in ("seams", "voronoi", "defaults"):
@@ -36,7 +38,8 @@ def main():
                 gmaps.append((1.0 + 0.12 * np.sin(0.7 * xx + k) * np.cos(0.5 * yy - k) + 0.02 * rng.standard_normal((gh, gw))).astype(np.float32))
             comp = S.ExposureErrorCompensator("gain_blocks")
             comp.set_gains(gmaps)
-            job = StitchJob(base.frames, cams, blend_strength=5, seam_masks=[np.ascontiguousarray(m[::11, ::11]) for m in seams], compensator=comp)
+            job = StitchJob(base.frames, cams, blend_strength=5, seam_masks=[np.ascontiguousarray(m[::11, ::11]) for m in seams], compensator=comp,
+                           reuse_geometry=reuse)
         elif leg == "voronoi":
             job = StitchJob(base.frames, cams, num_bands=5, feed_masks=seams)
         else:

@@ -421,6 +421,25 @@ int stx_features_detect(stx_ctx* ctx, int n, const stx_buf* const* images, const
                         int fast_threshold, const int* level_counts, const int* level_wh, const int* quotas, const int* cxcy,
                         const signed char* patterns, int* out_counts, int* out_lxyb, long long* out_R, unsigned char* out_desc,
                         double out_info[4]);
+/* ---- feature matching: the project's OWN matcher, not cv.detail.BestOf2NearestMatcher ("homography" / "affine" stay cv2's) ---------
+ * Two-nearest-neighbour matching of 256-bit descriptors by Hamming distance with an integer ratio test (1024 d1 < ratio_T d2), the
+ * union of both directions in OpenCV's order, and a homography RANSAC with a counter-based sampler and a division-free closed form in
+ * IEEE fp64 without FMA.  tests/numpy_matches.py is the contract: every integer result and the bits of out_H.
+ * Per image i (host memory, read only): desc[i], desc_shape[3 i] = {rows, columns, bytes per element} as the caller holds them, and
+ * pts[i] = pts_rows[i] x {x, y} doubles, level-0 pixels relative to the image centre.  ratio_T = floor((1 - match_conf) 1024 + 0.5) in
+ * 0 .. 1024; range_width < 0: every pair i < j, else those with j - i <= range_width; threshold_sq = ransac_threshold^2.
+ * Results by pair ordinal k (the processed pairs i < j, row-major) with slot(k) = the sum of rows_i + rows_j over the pairs before it:
+ * out_counts[k] = m matches; out_matches[3 (slot(k) + e)] = {query, train, distance} and out_mask[slot(k) + e] for e < m; out_pick[2 k]
+ * = {inliers of the best hypothesis, its number, or 0 and -1 where m < 6}; out_H[9 k] = that hypothesis's H as computed (zeros where
+ * m < 6).  The refit, the confidence and the mirrored entries are the caller's (float64 on the host).
+ * out_info (or NULL): {pairs, matches, device ms of the four launches, device ms with the copies both ways} (HIP events).
+ * One host wait, at the end.  Refused with STX_ERR_INVALID before anything is launched: more than STX_MATCH_MAX_FEATURES features in an
+ * image, ransac_iters outside 1 .. STX_MATCH_MAX_ITERS, descriptors that are not rows x 32 of one byte, pts_rows[i] != rows. */
+#define STX_MATCH_MAX_FEATURES 65536
+#define STX_MATCH_MAX_ITERS 4096
+int stx_match_features(stx_ctx* ctx, int n, const unsigned char* const* desc, const int* desc_shape, const double* const* pts,
+                       const int* pts_rows, int ratio_T, int range_width, int ransac_iters, double threshold_sq, unsigned seed,
+                       int* out_counts, int* out_matches, unsigned char* out_mask, int* out_pick, double* out_H, double out_info[4]);
 /* stx_resize_linear_exact <- stitching/images.py:122-124 cv.resize(img, size, interpolation=cv.INTER_LINEAR_EXACT) (u8x1 / u8x3:
  *                            the final-resolution resize of Images.resize, next row N3)
  * stx_seam_mask_resize    <- stitching/seam_finder.py:37-43 SeamFinder.resize: cv.dilate(seam_mask, None), cv.resize(...,

@@ -13,6 +13,8 @@ from .exposure_error_compensator import ExposureErrorCompensator
 from .exposure_estimation import ExposureEstimator
 from .feature_detector import FeatureDetector
 from .feature_estimation import FeatureEstimator, ImageFeatures
+from .feature_matcher import FeatureMatcher
+from .match_estimation import MatchEstimator, MatchesInfo
 from .images import Images, MegapixDownscaler, MegapixScaler
 from .pipeline import ComposePlan, Composer
 from .seam_estimation import ColorSeamEstimator, SeamEstimator
@@ -22,7 +24,7 @@ from .timelapser import Timelapser
 from .warper import Warper
 
 __all__ = [
-    "Blender", "CameraParams", "ColorSeamEstimator", "ComposePlan", "Composer", "Context", "Cropper", "Rectangle", "DeviceImage", "ExposureErrorCompensator", "ExposureEstimator", "FeatureDetector", "FeatureEstimator", "ImageFeatures", "Images", "MegapixDownscaler", "MegapixScaler", "StitchingError", "StitchingWarning",
+    "Blender", "CameraParams", "ColorSeamEstimator", "ComposePlan", "Composer", "Context", "Cropper", "Rectangle", "DeviceImage", "ExposureErrorCompensator", "ExposureEstimator", "FeatureDetector", "FeatureEstimator", "FeatureMatcher", "ImageFeatures", "Images", "MatchEstimator", "MatchesInfo", "MegapixDownscaler", "MegapixScaler", "StitchingError", "StitchingWarning",
     "SeamEstimator", "SeamFinder", "Timelapser", "Warper", "resize_linear_exact", "resize_linear_exact_all",
     "as_device", "device_count", "pinned_empty", "device_resident", "get_context", "set_default_device", "set_device_resident", "set_trig_mode", "trig_mode", "set_remap_mode", "remap_mode", "set_pyrdown_mode", "pyrdown_mode",
     "set_exposure_estimator", "exposure_estimator", "set_exposure_solver", "exposure_solver", "set_seam_estimator", "seam_estimator",

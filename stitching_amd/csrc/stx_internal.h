@@ -312,6 +312,25 @@ int stx_launch_feat_select(stx_ctx* ctx, const StxFeatSel* d_sel, int n, const u
                            unsigned long long* d_keys, int* d_item);
 int stx_launch_feat_describe(stx_ctx* ctx, const StxFeatLevel* d_levels, int nl, const unsigned long long* d_keys, const int* d_item, int total,
                              const int* d_cxcy, const signed char* d_patterns, int* d_bins, uint8_t* d_desc);
+// feature matching (stx_matches.hip; host side in stx_matches_host.cpp) ------------------------------------------------------------
+// all images' descriptors (8 dwords each) and centred points (x, y doubles) lie in two flat arrays; an image is its first row there
+constexpr int STX_MATCH_NN_WG = 256;     // match_2nn: queries per workgroup, and train descriptors per LDS tile
+constexpr int STX_MATCH_HYP_PER_WG = 4;  // match_ransac: one wavefront per hypothesis
+constexpr unsigned STX_MATCH_NO_D = 0xffffu;  // "no distance yet": above every Hamming distance of 256 bits
+// one direction of a pair that can match at all (na > 0 queries, nb >= 2 train descriptors): the queries of image a among image b's;
+// block0: the job's first workgroup of the flat grid (ascending, first 0); nn_off: its na results {i1, d1 | d2 << 16}
+struct StxMatchJob { int a_off, b_off, na, nb, block0, pad_; long long nn_off; };
+// a pair i < j: nn_f / nn_b: the results of i -> j / j -> i (-1: that direction has no job); out_off: the pair's first slot of the
+// match arena (ni + nj slots: the union cannot be larger); p = i n + j
+struct StxMatchPair { int i_off, j_off, ni, nj, p, pad_; long long nn_f, nn_b, out_off; };
+int stx_launch_match_2nn(stx_ctx* ctx, const StxMatchJob* d_jobs, int njobs, int blocks, const uint32_t* d_desc, uint2* d_nn,
+                         double compares, bool lds);
+int stx_launch_match_union(stx_ctx* ctx, const StxMatchPair* d_pairs, int np, const uint2* d_nn, const double* d_pts, int ratio_T,
+                           int* d_counts, int* d_matches, double* d_xyuv);
+int stx_launch_match_ransac(stx_ctx* ctx, const StxMatchPair* d_pairs, int np, const int* d_counts, const double* d_xyuv, int iters,
+                            double threshold_sq, uint32_t seed, int* d_hyp);
+int stx_launch_match_pick(stx_ctx* ctx, const StxMatchPair* d_pairs, int np, const int* d_counts, const double* d_xyuv, int iters,
+                          double threshold_sq, uint32_t seed, const int* d_hyp, int* d_pick, double* d_H, uint8_t* d_mask);
 // cv::resize(INTER_LINEAR_EXACT) u8 (next rows N2 / N3); d_xt / d_yt: device tables of (offset, coeff1 | interior << 16)
 int stx_launch_resize_exact(stx_ctx* ctx, const stx_buf* src, stx_buf* dst, const int* d_xt, const int* d_yt, bool dilate,
                             const stx_buf* andmask);

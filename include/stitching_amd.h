@@ -440,6 +440,27 @@ int stx_features_detect(stx_ctx* ctx, int n, const stx_buf* const* images, const
 int stx_match_features(stx_ctx* ctx, int n, const unsigned char* const* desc, const int* desc_shape, const double* const* pts,
                        const int* pts_rows, int ratio_T, int range_width, int ransac_iters, double threshold_sq, unsigned seed,
                        int* out_counts, int* out_matches, unsigned char* out_mask, int* out_pick, double* out_H, double out_info[4]);
+/* ---- ray bundle adjustment: the project's OWN solver, not cv.detail.BundleAdjusterRay ("ray" stays cv2's) ----------------------------
+ * The normal equations of CameraSolver's Levenberg-Marquardt steps.  An edge is a pair of cameras i < j with its inlier matches
+ * (x, y) in image i and (u, v) in image j, level-0 pixels relative to the image centre.  A camera has 9 variants of 10 doubles
+ * {f', H' = Rodrigues(r') diag(1 / f', 1 / f', 1) row-major}: its parameters, then + and - 1e-3 on each of the four (made by the caller).
+ * Per match the residual sqrt(f_i' f_j') (ray_i - ray_j) of the unit rays H' (x, y, 1) / |.| and its 3 x 8 Jacobian by central
+ * differences over the variants; per edge E = sum r.r, g[8] = sum J^T r and the upper triangle B[36] of sum J^T J, row-major.
+ * tests/numpy_cameras.py is the contract, in the bits of all 45 sums: IEEE fp64 without FMA, 256 lanes that stride over the matches,
+ * folded by v[l] += v[l + s] for s = 128 .. 1.
+ * stx_ray_problem_create uploads the edges once: edge_cams[2 e] = {i, j}, offsets[n_edges + 1] ascending from 0, pts[4 offsets[n_edges]].
+ * stx_ray_problem_eval: variants[n_cams * 90] -> out[45 e] = {E, g, B}; one launch, one host wait.  An edge without matches gives 45
+ * zeros.  out_info (or NULL): {edges, matches, device ms of the launch, device ms with the copies both ways} (HIP events).
+ * Refused with STX_ERR_INVALID before anything is allocated or launched: a camera index outside 0 .. STX_RAY_MAX_CAMERAS - 1 or more
+ * than STX_RAY_MAX_CAMERAS cameras, an edge with i >= j, offsets that do not ascend, more than STX_RAY_MAX_MATCHES matches on an edge,
+ * fewer cameras than the edges name, a variant that is not finite.  Free the problem before its context. */
+#define STX_RAY_MAX_CAMERAS 1024
+#define STX_RAY_MAX_MATCHES 131072 /* 2 x STX_MATCH_MAX_FEATURES: the union of both directions */
+typedef struct stx_ray_problem stx_ray_problem;
+int stx_ray_problem_create(stx_ctx* ctx, int n_edges, const int* edge_cams, const long long* offsets, const double* pts,
+                           stx_ray_problem** out);
+int stx_ray_problem_eval(stx_ray_problem* problem, int n_cams, const double* variants, double* out, double out_info[4]);
+int stx_ray_problem_free(stx_ray_problem* problem);
 /* stx_resize_linear_exact <- stitching/images.py:122-124 cv.resize(img, size, interpolation=cv.INTER_LINEAR_EXACT) (u8x1 / u8x3:
  *                            the final-resolution resize of Images.resize, next row N3)
  * stx_seam_mask_resize    <- stitching/seam_finder.py:37-43 SeamFinder.resize: cv.dilate(seam_mask, None), cv.resize(...,

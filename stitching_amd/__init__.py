@@ -4,6 +4,10 @@ hand-written HIP kernels behind the C ABI in include/stitching_amd.h (loaded wit
 PyTorch, no OpenCV, no CPU fallback)."""
 from .blender import Blender
 from .camera import CameraParams
+from .camera_adjuster import CameraAdjuster
+from .camera_estimation import CameraSolver
+from .camera_estimator import CameraEstimator
+from .camera_wave_corrector import WaveCorrector
 from .config import (device_resident, exposure_estimator, exposure_solver, pyrdown_mode, remap_mode, seam_estimator, set_device_resident,
                      set_exposure_estimator, set_exposure_solver, set_pyrdown_mode, set_remap_mode, set_seam_estimator, set_trig_mode,
                      trig_mode)
@@ -20,12 +24,13 @@ from .pipeline import ComposePlan, Composer
 from .seam_estimation import ColorSeamEstimator, SeamEstimator
 from .seam_finder import SeamFinder, resize_linear_exact, resize_linear_exact_all
 from .stitching_error import StitchingError, StitchingWarning
+from .subsetter import Subsetter
 from .timelapser import Timelapser
 from .warper import Warper
 
 __all__ = [
-    "Blender", "CameraParams", "ColorSeamEstimator", "ComposePlan", "Composer", "Context", "Cropper", "Rectangle", "DeviceImage", "ExposureErrorCompensator", "ExposureEstimator", "FeatureDetector", "FeatureEstimator", "FeatureMatcher", "ImageFeatures", "Images", "MatchEstimator", "MatchesInfo", "MegapixDownscaler", "MegapixScaler", "StitchingError", "StitchingWarning",
-    "SeamEstimator", "SeamFinder", "Timelapser", "Warper", "resize_linear_exact", "resize_linear_exact_all",
+    "Blender", "CameraAdjuster", "CameraEstimator", "CameraParams", "CameraSolver", "ColorSeamEstimator", "ComposePlan", "Composer", "Context", "Cropper", "Rectangle", "DeviceImage", "ExposureErrorCompensator", "ExposureEstimator", "FeatureDetector", "FeatureEstimator", "FeatureMatcher", "ImageFeatures", "Images", "MatchEstimator", "MatchesInfo", "MegapixDownscaler", "MegapixScaler", "StitchingError", "StitchingWarning",
+    "SeamEstimator", "SeamFinder", "Subsetter", "Timelapser", "Warper", "WaveCorrector", "resize_linear_exact", "resize_linear_exact_all",
     "as_device", "device_count", "pinned_empty", "device_resident", "get_context", "set_default_device", "set_device_resident", "set_trig_mode", "trig_mode", "set_remap_mode", "remap_mode", "set_pyrdown_mode", "pyrdown_mode",
     "set_exposure_estimator", "exposure_estimator", "set_exposure_solver", "exposure_solver", "set_seam_estimator", "seam_estimator",
 ]

@@ -1,0 +1,533 @@
+"""Camera registration: which images belong to the panorama, their focals and rotations, a ray bundle adjustment on the device, and
+wave correction.
+
+`CameraSolver` is the project's OWN solver, in the way of OpenCV's homography-based estimator, ray adjuster and wave correction.  It is
+NOT cv.detail.HomographyBasedEstimator, BundleAdjusterRay or waveCorrect and answers to none of their names: "homography", "ray" and
+the wave-correction kinds by name stay cv2's (subsetter.Subsetter, camera_estimator.CameraEstimator, camera_adjuster.CameraAdjuster,
+camera_wave_corrector.WaveCorrector take it as solver=).  tests/numpy_cameras.py states it exactly and is the contract.
+
+The work that grows with the matches — per Levenberg-Marquardt step the residuals of every inlier match of every confident pair and
+their Jacobian with respect to both cameras, summed into the normal equations — is one launch per step over matches that stay on the
+device (csrc/stx_cameras.hip), equal to the contract in the bits of all 45 float64 sums of an edge; DESIGN.md section 17 has the kernel
+and the limits.  What is small and wants float64 with a library behind it is numpy on the host: the subset, the focals, the spanning
+tree and its rotations, the 9 variants of every camera, the 4n x 4n solve, the wave correction.
+"""
+import ctypes as C
+import math
+import warnings
+
+import numpy as np
+
+from . import _lib
+from .camera import CameraParams
+from .device import get_context
+from .match_estimation import centred_points
+from .stitching_error import StitchingError, StitchingWarning
+
+STEP = 1e-3  # of the central differences, on every parameter
+WAVE_KINDS = ("horiz", "vert", "no")
+NO_MATCH_MESSAGE = ("No match exceeds the given confidence threshold. Do your images have enough overlap and common features? If yes, "
+                    "you might want to lower the 'confidence_threshold' or try another 'detector'.")
+NOT_ALL_MESSAGE = ("Not all images are included in the final panorama. If this is not intended, use the 'matches_graph_dot_file' "
+                   "parameter to analyze your matches. You might want to lower the 'confidence_threshold' or try another 'detector' to "
+                   "include all your images.")
+_TRI = np.triu_indices(8)
+
+
+# ---- subset ------------------------------------------------------------------------------------------------------------------------------
+def largest_component(conf, conf_thresh):
+    """Ascending indices of the largest group of images joined by pairs i < j with conf[i, j] >= conf_thresh; among groups of equal
+    size the one that holds the smallest index."""
+    n = len(conf)
+    label = np.arange(n)
+    for i in range(n):
+        for j in range(i + 1, n):
+            if conf[i, j] >= conf_thresh and label[i] != label[j]:
+                lo, hi = sorted((int(label[i]), int(label[j])))
+                label[label == hi] = lo  # a group is named by its smallest member
+    names, counts = np.unique(label, return_counts=True)
+    if n == 0:
+        return []
+    return np.flatnonzero(label == names[np.argmax(counts)]).tolist()  # argmax: the first maximum, names ascend
+
+
+def confidences(matches, n):
+    return np.array([[float(matches[i * n + j].confidence) for j in range(n)] for i in range(n)], np.float64).reshape(n, n)
+
+
+# ---- focals ------------------------------------------------------------------------------------------------------------------------------
+def _focal_choice(v1, v2, d1, d2):
+    """the focal of two candidate squares v = numerator / d: the larger one where it alone is positive; where both are, the one with the
+    larger |d| (the better conditioned quotient)"""
+    larger, smaller = ((v2, d2), (v1, d1)) if v1 < v2 else ((v1, d1), (v2, d2))
+    if not larger[0] > 0:
+        return None
+    square = larger[0]
+    if smaller[0] > 0 and not abs(larger[1]) > abs(smaller[1]):
+        square = smaller[0]
+    return float(np.sqrt(square)) if np.isfinite(square) else None
+
+
+def focals_from_homography(H):
+    """The two focal candidates (f0 of the source image, f1 of the destination) of a homography between two views of a rotating camera
+    with the principal point at the origin, each None where its closed form has no positive solution (a pure translation, say)."""
+    a, b, c, d, e, f, g, h, _ = np.asarray(H, np.float64).reshape(9)
+    with np.errstate(all="ignore"):
+        f1 = _focal_choice(-(a * b + d * e) / (g * h), (a * a + d * d - b * b - e * e) / ((h - g) * (h + g)), g * h, (h - g) * (h + g))
+        f0 = _focal_choice(-c * f / (a * d + b * e), (f * f - c * c) / (a * a + b * b - d * d - e * e), a * d + b * e,
+                           a * a + b * b - d * d - e * e)
+    return f0, f1
+
+
+def starting_focal(features, matches):
+    """One focal for all cameras: the median of sqrt(f0 f1) over the pairs i < j whose homography gives both, where there are at least
+    n - 1 of them; else the mean of width + height."""
+    n = len(features)
+    got = []
+    for i in range(n):
+        for j in range(i + 1, n):
+            H = matches[i * n + j].H
+            if H is not None:
+                f0, f1 = focals_from_homography(H)
+                if f0 is not None and f1 is not None:
+                    got.append(math.sqrt(f0 * f1))
+    if len(got) >= n - 1:
+        got.sort()
+        half = len(got) // 2
+        return got[half] if len(got) % 2 else (got[half - 1] + got[half]) * 0.5
+    return sum(f.img_size[0] + f.img_size[1] for f in features) / n
+
+
+# ---- spanning tree and rotations -----------------------------------------------------------------------------------------------------------
+def spanning_tree(matches, n):
+    """(neighbour lists in ascending order, centre) of the maximum spanning tree over the pairs with a homography — Kruskal by
+    num_inliers descending, then (i, j) ascending; the centre is the node of least eccentricity, the smallest index among equals.
+    (None, -1) where those pairs do not connect all n images."""
+    edges = []
+    for i in range(n):
+        for j in range(i + 1, n):
+            e = matches[i * n + j]
+            if e.H is None:
+                e = matches[j * n + i]
+            if e.H is not None:
+                edges.append((-int(e.num_inliers), i, j))
+    edges.sort()
+    group = list(range(n))
+    near = [[] for _ in range(n)]
+    taken = 0
+    for _, i, j in edges:
+        if group[i] != group[j]:
+            old, new = group[i], group[j]
+            group = [new if g == old else g for g in group]
+            near[i].append(j)
+            near[j].append(i)
+            taken += 1
+    if taken != n - 1:
+        return None, -1
+    near = [sorted(a) for a in near]
+    reach = [max(_hops(near, s)) for s in range(n)]
+    return near, int(np.argmin(reach))
+
+
+def _hops(near, start):
+    hops = {start: 0}
+    front = [start]
+    while front:
+        nxt = []
+        for a in front:
+            for b in near[a]:
+                if b not in hops:
+                    hops[b] = hops[a] + 1
+                    nxt.append(b)
+        front = nxt
+    return [hops[k] for k in range(len(near))]
+
+
+def _homography(matches, n, a, b):
+    H = matches[a * n + b].H
+    if H is not None:
+        return np.asarray(H, np.float64)
+    return np.linalg.inv(np.asarray(matches[b * n + a].H, np.float64))
+
+
+def tree_rotations(matches, n, focals):
+    """float64 rotations along the spanning tree from its centre (R = I there): R_to = R_from (K_from^-1 H_from->to^-1 K_to)"""
+    near, centre = spanning_tree(matches, n)
+    if near is None:
+        raise StitchingError("Homography estimation failed.")
+    R = {centre: np.eye(3)}
+    front = [centre]
+    while front:
+        nxt = []
+        for a in front:
+            for b in near[a]:
+                if b not in R:
+                    k_from_inv = np.diag([1.0 / focals[a], 1.0 / focals[a], 1.0])
+                    k_to = np.diag([focals[b], focals[b], 1.0])
+                    R[b] = R[a] @ (k_from_inv @ np.linalg.inv(_homography(matches, n, a, b)) @ k_to)
+                    nxt.append(b)
+        front = nxt
+    return [R[k] for k in range(n)]
+
+
+# ---- Rodrigues -----------------------------------------------------------------------------------------------------------------------------
+def rotation_matrix(r):
+    """Rodrigues vector -> (3, 3) float64: (1 - c) k k^T + c I + s [k]x with (1 - c) k_a multiplied first, as the contract writes it"""
+    r = np.asarray(r, np.float64)
+    th = np.sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2])
+    if not th >= 1e-12:
+        return np.eye(3) if th == th else np.full((3, 3), np.nan)
+    c, s = np.cos(th), np.sin(th)
+    k = r / th
+    sk = s * k
+    return ((1.0 - c) * k)[:, None] * k[None, :] + np.array([[c, -sk[2], sk[1]], [sk[2], c, -sk[0]], [-sk[1], sk[0], c]])
+
+
+def rotation_vector(R):
+    """(3, 3) -> Rodrigues vector of the nearest rotation (SVD; negated where the determinant is negative), through the unit quaternion:
+    its largest component comes from a square root of the trace or of a diagonal element, the others from sums and differences of
+    off-diagonal pairs — no branch of its own for small turns or half turns.  A half turn comes out with either sign of its axis."""
+    u, _, vt = np.linalg.svd(np.asarray(R, np.float64))
+    R = u @ vt
+    if np.linalg.det(R) < 0:
+        R = -R
+    trace = R[0, 0] + R[1, 1] + R[2, 2]
+    lead = int(np.argmax([trace, R[0, 0], R[1, 1], R[2, 2]]))
+    if lead == 0:
+        w = 0.5 * math.sqrt(max(1.0 + trace, 0.0))
+        v = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]]) / (4.0 * w)
+    else:
+        i = lead - 1
+        j, k = (i + 1) % 3, (i + 2) % 3
+        v = np.zeros(3)
+        v[i] = 0.5 * math.sqrt(max(1.0 + R[i, i] - R[j, j] - R[k, k], 0.0))
+        v[j] = (R[j, i] + R[i, j]) / (4.0 * v[i])
+        v[k] = (R[k, i] + R[i, k]) / (4.0 * v[i])
+        w = (R[k, j] - R[j, k]) / (4.0 * v[i])
+    if w < 0:
+        w, v = -w, -v
+    length = math.sqrt(float(v @ v))
+    return v * (2.0 * math.atan2(length, w) / length) if length > 0 else np.zeros(3)
+
+
+def camera_variants(params):
+    """(n, 9, 10) float64 for params (n, 4) rows focal, rx, ry, rz: per camera its parameters, then + and - STEP on each of the four
+    (+ before -); a variant is f' and H' = R(r') diag(1 / f', 1 / f', 1), row-major."""
+    params = np.ascontiguousarray(params, np.float64).reshape(-1, 4)
+    shifts = np.zeros((9, 4), np.float64)
+    for k in range(4):
+        shifts[1 + 2 * k, k], shifts[2 + 2 * k, k] = STEP, -STEP
+    out = np.zeros((len(params), 9, 10), np.float64)
+    with np.errstate(all="ignore"):
+        moved = params[:, None, :] + shifts[None, :, :]
+        out[:, :, 0] = moved[:, :, 0]
+        scale = np.ones((len(params), 9, 3), np.float64)
+        scale[:, :, 0] = scale[:, :, 1] = 1.0 / moved[:, :, 0]
+        for c in range(len(params)):
+            for v in range(9):
+                out[c, v, 1:] = (rotation_matrix(moved[c, v, 1:]) * scale[c, v][None, :]).reshape(9)
+    return out
+
+
+# ---- the ray problem on the device ---------------------------------------------------------------------------------------------------------
+def ray_edges(matches, n, conf_thresh):
+    """the pairs i < j whose confidence is above conf_thresh, ascending"""
+    return [(i, j) for i in range(n) for j in range(i + 1, n) if matches[i * n + j].confidence > conf_thresh]
+
+
+def edge_points(features, matches, edges, pts=None):
+    """offsets (e + 1,) int64 and xyuv (total, 4) float64: per edge its inlier matches in match order, (x, y) of image i and (u, v) of
+    image j in centred level-0 pixels"""
+    n = len(features)
+    if pts is None:
+        pts = [centred_points(f) for f in features]
+    blocks, offsets = [np.zeros((0, 4), np.float64)], np.zeros(len(edges) + 1, np.int64)
+    for k, (i, j) in enumerate(edges):
+        e = matches[i * n + j]
+        keep = np.asarray(e.inliers_mask) != 0
+        mt = np.asarray(e.matches).reshape(-1, 3)[keep]
+        blocks.append(np.concatenate([pts[i][mt[:, 0]].reshape(-1, 2), pts[j][mt[:, 1]].reshape(-1, 2)], axis=1))
+        offsets[k + 1] = offsets[k] + len(mt)
+    return offsets, np.ascontiguousarray(np.concatenate(blocks, axis=0))
+
+
+class RayProblem:
+    """The edges of one adjustment on the device (stx_ray_problem): uploaded once, evaluated once per Levenberg-Marquardt step.  Use it
+    as a context manager: the handle must go before its context does."""
+
+    def __init__(self, edges, offsets, xyuv, ctx=None):
+        self.ctx = ctx or get_context()
+        self.n_edges = len(edges)
+        self._h = C.c_void_p()
+        cams = np.ascontiguousarray(np.asarray(edges, np.int32).reshape(-1, 2))
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        xyuv = np.ascontiguousarray(xyuv, np.float64)
+        _lib.check(self.ctx._lib.stx_ray_problem_create(
+            self.ctx.handle, self.n_edges, cams.ctypes.data_as(C.POINTER(C.c_int)), offsets.ctypes.data_as(C.POINTER(C.c_longlong)),
+            xyuv.ctypes.data_as(C.POINTER(C.c_double)), C.byref(self._h)))
+        self.info = None
+
+    def evaluate(self, variants):
+        """(n, 9, 10) variants -> (e, 45) float64 sums E, g[8], B[36] of every edge; one launch, one wait"""
+        variants = np.ascontiguousarray(variants, np.float64)
+        out, info = np.zeros((self.n_edges, 45), np.float64), np.zeros(4, np.float64)
+        dp = C.POINTER(C.c_double)
+        _lib.check(self.ctx._lib.stx_ray_problem_eval(self._h, int(variants.shape[0]), variants.ctypes.data_as(dp), out.ctypes.data_as(dp),
+                                                      info.ctypes.data_as(dp)))
+        self.info = {"edges": int(info[0]), "matches": int(info[1]), "device_ms": float(info[2]), "device_ms_with_copy": float(info[3])}
+        return out
+
+    def free(self):
+        h, self._h = self._h, C.c_void_p()
+        if h:
+            _lib.check(self.ctx._lib.stx_ray_problem_free(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+
+def assemble_system(n, edges, sums):
+    """E, g (4n,), A (4n, 4n) from the (e, 45) sums of the edges, added in ascending order; each 8 x 8 block mirrored to its lower half"""
+    A, g, E = np.zeros((4 * n, 4 * n), np.float64), np.zeros(4 * n, np.float64), 0.0
+    for (i, j), row in zip(edges, sums):
+        block = np.zeros((8, 8), np.float64)
+        block[_TRI] = row[9:]
+        block.T[_TRI] = row[9:]
+        at = np.r_[4 * i:4 * i + 4, 4 * j:4 * j + 4]
+        A[np.ix_(at, at)] += block
+        g[at] += row[1:9]
+        E = E + row[0]
+    return E, g, A
+
+
+# ---- wave correction -------------------------------------------------------------------------------------------------------------------------
+def wave_corrected(rotations, kind):
+    """float32 rotations with the waviness of a hand-held sweep taken out: one rotation for all cameras whose second row is, for
+    "horiz", the normal of the plane the cameras' x axes lie nearest to, and for "vert" the direction those axes share."""
+    if kind == "no":
+        return [np.asarray(R) for R in rotations]
+    Rs = np.stack([np.asarray(R, np.float64) for R in rotations])
+    xs = Rs[:, :, 0]
+    moment = np.zeros((3, 3))
+    for x in xs:
+        moment = moment + x[:, None] * x[None, :]
+    _, vectors = np.linalg.eigh(moment)
+    up = vectors[:, 0] if kind == "horiz" else vectors[:, 2]
+    forward = np.zeros(3)
+    for R in Rs:
+        forward = forward + R[:, 2]
+    right = np.cross(up, forward)
+    length = np.sqrt((right * right).sum())
+    if not length > 0:
+        return [R.astype(np.float32) for R in Rs]
+    right = right / length
+    ahead = np.cross(right, up)
+    if sum(float(right @ x) for x in xs) < 0:
+        right, up = -right, -up
+    turn = np.stack([right, up, ahead])
+    return [(turn @ R).astype(np.float32) for R in Rs]
+
+
+class CameraSolver:
+    """The project's own camera registration — NOT cv.detail.HomographyBasedEstimator, BundleAdjusterRay or waveCorrect, and not behind
+    their names.  From the ImageFeatures of FeatureEstimator.detect and the n * n MatchesInfo of MatchEstimator.match:
+
+        subset    the largest group of images joined by pairs of confidence >= conf_thresh
+        estimate  one focal from the homographies' closed form, rotations along the maximum spanning tree
+        adjust    Levenberg-Marquardt on focal + Rodrigues vector per camera over the rays of every inlier match of every pair with
+                  confidence > conf_thresh; the normal equations of a step are one launch on the device
+        correct   wave correction "horiz", "vert" or "no"
+        register  all four -> (indices, cameras)
+
+    tests/numpy_cameras.py states it exactly and is the contract; DESIGN.md section 17 has the launch shape.  Construction needs no GPU.
+    Limits, refused with a StitchingError before anything is launched: at most MAX_CAMERAS images, at most MAX_MATCHES inlier matches
+    on a pair, parameters that are finite.  Nothing handed in is written; cameras come back as new CameraParams with a float32 R."""
+
+    MAX_CAMERAS, MAX_MATCHES = _lib.RAY_MAX_CAMERAS, _lib.RAY_MAX_MATCHES
+
+    def __init__(self, conf_thresh=1.0, wave_correct="horiz", max_evals=100):
+        if wave_correct == "auto":
+            raise StitchingError('wave correction "auto" is cv2\'s: the solver takes "horiz", "vert" or "no"')
+        if wave_correct not in WAVE_KINDS:
+            raise StitchingError(f"unknown wave correction {wave_correct!r}: the solver takes {WAVE_KINDS}")
+        if int(max_evals) < 1:
+            raise StitchingError(f"camera adjustment needs at least one evaluation, got max_evals={max_evals}")
+        self.conf_thresh, self.wave_correct, self.max_evals = float(conf_thresh), wave_correct, int(max_evals)
+        self.info = None  # of the last adjust / register / normal_equations
+
+    # -- subset
+    def subset(self, features, matches):
+        n = len(features)
+        keep = largest_component(confidences(matches, n), self.conf_thresh)
+        if len(keep) < 2:
+            raise StitchingError(NO_MATCH_MESSAGE)
+        if len(keep) < n:
+            warnings.warn(NOT_ALL_MESSAGE, StitchingWarning)
+        return keep
+
+    @staticmethod
+    def subset_matches(matches, indices):
+        """the entries of the kept images, row-major"""
+        n = int(math.sqrt(len(matches)))
+        grid = np.empty((n, n), object)
+        for k, e in enumerate(matches):
+            grid[k // n, k % n] = e
+        return list(grid[np.ix_(indices, indices)].reshape(-1))
+
+    # -- estimate
+    def estimate(self, features, matches):
+        features = list(features)
+        n = len(features)
+        self._check_count(n)
+        focal = starting_focal(features, matches)
+        return [self._camera(f, focal, R) for f, R in zip(features, tree_rotations(matches, n, [focal] * n))]
+
+    @staticmethod
+    def _camera(feature, focal, R):
+        w0, h0 = feature.img_size
+        return CameraParams(focal=focal, aspect=1.0, ppx=w0 / 2, ppy=h0 / 2, R=np.asarray(R).astype(np.float32))
+
+    def _check_count(self, n):
+        if n > self.MAX_CAMERAS:
+            raise StitchingError(f"camera registration of {n} images: the solver takes up to {self.MAX_CAMERAS}")
+
+    # -- adjust
+    @staticmethod
+    def _sums(problem, evaluate, params):
+        """(e, 45) sums at params, or None where a variant is not finite (a rejected step, not evaluated) — the device's, or evaluate's"""
+        variants = camera_variants(params)
+        if not np.isfinite(variants).all():
+            return None
+        if evaluate is None:
+            return problem.evaluate(variants)
+        E, g, B = evaluate(params, variants)
+        return np.concatenate([np.asarray(E).reshape(-1, 1), np.asarray(g).reshape(-1, 8), np.asarray(B).reshape(-1, 36)], axis=1)
+
+    def _check_params(self, params, n):
+        params = np.array(params, np.float64).reshape(-1, 4)
+        if len(params) != n:
+            raise StitchingError(f"{len(params)} parameter rows for {n} cameras")
+        if not np.isfinite(params).all():
+            raise StitchingError("camera adjustment needs finite parameters (focal and Rodrigues vector per camera)")
+        return params
+
+    def _problem(self, features, matches, conf_thresh=None):
+        n = len(features)
+        self._check_count(n)
+        edges = ray_edges(matches, n, self.conf_thresh if conf_thresh is None else float(conf_thresh))
+        offsets, xyuv = edge_points(features, matches, edges)
+        counts = np.diff(offsets)
+        if len(counts) and int(counts.max()) > self.MAX_MATCHES:
+            raise StitchingError(f"a pair with {int(counts.max())} inlier matches: the solver takes up to {self.MAX_MATCHES}")
+        return edges, offsets, xyuv
+
+    def normal_equations(self, features, matches, params, ctx=None):
+        """E (e,), g (e, 8) and the upper triangle B (e, 36) of the normal equations of every edge (the pairs i < j with confidence above
+        conf_thresh, ascending) at params (n, 4) rows focal, rx, ry, rz — one launch on the device."""
+        features = list(features)
+        params = self._check_params(params, len(features))
+        edges, offsets, xyuv = self._problem(features, matches)
+        with RayProblem(edges, offsets, xyuv, ctx) as problem:
+            sums = problem.evaluate(camera_variants(params))
+            self.info = dict(problem.info, evaluations=1)
+        return sums[:, 0].copy(), sums[:, 1:9].copy(), sums[:, 9:].copy()
+
+    def adjust(self, features, matches, cameras, ctx=None, conf_thresh=None, evaluate=None):
+        """conf_thresh: in place of the solver's own, for this call.  evaluate(params, variants) -> (E, g, B) per edge: takes the device's place
+        (measurements and tests of the host steps); everything else, the rejection of steps to variants that are not finite included,
+        is as with the device."""
+        features, cameras = list(features), list(cameras)
+        n = len(features)
+        if len(cameras) != n:
+            raise StitchingError(f"{len(cameras)} cameras for {n} images")
+        start = self._check_params([[c.focal] + list(rotation_vector(c.R)) for c in cameras], n)
+        edges, offsets, xyuv = self._problem(features, matches, conf_thresh)
+        if evaluate is not None:
+            params, info = self._levenberg_marquardt(None, evaluate, edges, start)
+        else:
+            with RayProblem(edges, offsets, xyuv, ctx) as problem:
+                params, info = self._levenberg_marquardt(problem, None, edges, start)
+        info["edges"], info["matches"] = len(edges), int(offsets[-1])
+        self.info = info
+        if not np.isfinite(params).all() or (params[:, 0] <= 0).any():
+            raise StitchingError("Camera parameters adjusting failed.")
+        _, centre = spanning_tree(matches, n)
+        if centre < 0:
+            raise StitchingError("Camera parameters adjusting failed.")
+        Rs = [rotation_matrix(p[1:4]) for p in params]
+        back = np.linalg.inv(Rs[centre])
+        return [self._camera(f, float(p[0]), back @ R) for f, p, R in zip(features, params, Rs)]
+
+    def _levenberg_marquardt(self, problem, evaluate_sums, edges, p):
+        n = len(p)
+        info = {"evaluations": 1, "accepted": 0, "device_ms": 0.0, "device_ms_with_copy": 0.0}
+
+        def evaluate(q):
+            sums = self._sums(problem, evaluate_sums, q)
+            if sums is None:
+                return None
+            if problem is not None:
+                info["device_ms"] += problem.info["device_ms"]
+                info["device_ms_with_copy"] += problem.info["device_ms_with_copy"]
+            return assemble_system(n, edges, sums)
+
+        with np.errstate(all="ignore"):
+            first = evaluate(p)
+            if first is None:
+                raise StitchingError("Camera parameters adjusting failed.")
+            E, g, A = first
+            info["first_E"] = float(E)
+            lam = 1e-3
+            while info["evaluations"] < self.max_evals:
+                better = False
+                try:
+                    step = np.linalg.solve(A + lam * np.diag(np.diag(A)), -g)
+                except np.linalg.LinAlgError:
+                    step = None
+                if step is not None:
+                    q = p + step.reshape(n, 4)
+                    moved = evaluate(q)
+                    if moved is not None:
+                        E2, g2, A2 = moved
+                        info["evaluations"] += 1
+                        better = bool(E2 < E)
+                if better:
+                    gain = (E - E2) / E
+                    p, E, g, A = q, E2, g2, A2
+                    lam = max(lam / 10.0, 1e-12)
+                    info["accepted"] += 1
+                    if gain < 1e-10:
+                        break
+                else:
+                    lam *= 10.0
+                    if lam > 1e12:
+                        break
+        info["last_E"], info["parameters"] = float(E), p.copy()
+        return p, info
+
+    # -- wave correction
+    def correct(self, cameras, kind=None):
+        """kind: in place of the solver's own wave_correct, for this call ("horiz", "vert" or "no")"""
+        kind = self.wave_correct if kind is None else kind
+        if kind not in WAVE_KINDS:
+            raise StitchingError(f"unknown wave correction {kind!r}: the solver takes {WAVE_KINDS}")
+        cameras = list(cameras)
+        out = []
+        for cam, R in zip(cameras, wave_corrected([c.R for c in cameras], kind)):
+            out.append(CameraParams(focal=cam.focal, aspect=cam.aspect, ppx=cam.ppx, ppy=cam.ppy, R=R, t=cam.t))
+        return out
+
+    # -- all of it
+    def register(self, features, matches, ctx=None, evaluate=None):
+        """-> (indices of the images kept, their cameras): subset, estimate, adjust, correct.  evaluate: as adjust's, over the edges of
+        the images kept."""
+        features = list(features)
+        self._check_count(len(features))
+        indices = self.subset(features, matches)
+        features = [features[i] for i in indices]
+        matches = self.subset_matches(matches, indices)
+        cameras = self.adjust(features, matches, self.estimate(features, matches), ctx, evaluate=evaluate)
+        return indices, self.correct(cameras)

@@ -1,0 +1,90 @@
+// stx_cameras_host.cpp — host side of CameraSolver's ray bundle adjustment (the project's own solver, not cv.detail.BundleAdjusterRay):
+// a problem handle that keeps the edges and their points on the device, and one evaluation of the normal equations per call
+// (stx_cameras.hip): upload of the variants, one launch, one wait.  tests/numpy_cameras.py is the contract; DESIGN.md section 17.
+#include <algorithm>
+#include <cmath>
+
+#include "stx_internal.h"
+
+STX_EXPORT int stx_ray_problem_create(stx_ctx* ctx, int n_edges, const int* edge_cams, const long long* offsets, const double* pts,
+                                      stx_ray_problem** out)
+{
+    if (!ctx || !out) return stx_fail(STX_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (n_edges < 0 || n_edges > STX_RAY_MAX_CAMERAS * (STX_RAY_MAX_CAMERAS - 1) / 2)
+        return stx_fail(STX_ERR_INVALID, "ray adjustment over %d edges: 0 .. %d", n_edges, STX_RAY_MAX_CAMERAS * (STX_RAY_MAX_CAMERAS - 1) / 2);
+    if (n_edges > 0 && (!edge_cams || !offsets)) return stx_fail(STX_ERR_INVALID, "null argument");
+    // every check before anything is allocated
+    int max_cam = -1;
+    for (int e = 0; e < n_edges; e++) {
+        const int i = edge_cams[2 * e], j = edge_cams[2 * e + 1];
+        if (i < 0 || j >= STX_RAY_MAX_CAMERAS) return stx_fail(STX_ERR_INVALID, "edge %d joins the cameras %d and %d: 0 .. %d", e, i, j, STX_RAY_MAX_CAMERAS - 1);
+        if (i >= j) return stx_fail(STX_ERR_INVALID, "edge %d joins the cameras %d and %d: the first must be the smaller", e, i, j);
+        const long long m = offsets[e + 1] - offsets[e];
+        if (offsets[e] < 0 || m < 0 || (e == 0 && offsets[0] != 0)) return stx_fail(STX_ERR_INVALID, "edge %d: the offsets do not ascend from 0", e);
+        if (m > STX_RAY_MAX_MATCHES) return stx_fail(STX_ERR_INVALID, "edge %d has %lld matches: ray adjustment takes up to %d", e, m, STX_RAY_MAX_MATCHES);
+        max_cam = j > max_cam ? j : max_cam;
+    }
+    const long long total = n_edges > 0 ? offsets[n_edges] : 0;
+    if (total > 0 && !pts) return stx_fail(STX_ERR_INVALID, "null argument");
+    STX_TRY(stx_set_device(ctx));
+    std::unique_ptr<stx_ray_problem> P(new stx_ray_problem);
+    P->ctx = ctx; P->n_edges = n_edges; P->min_cams = max_cam + 1; P->total = total;
+    if (n_edges > 0) {
+        STX_TRY(stx_dev_alloc(ctx, (size_t)n_edges * 2 * sizeof(int), &P->d_edge_cams));
+        STX_TRY(stx_dev_alloc(ctx, ((size_t)n_edges + 1) * sizeof(long long), &P->d_offsets));
+        STX_TRY(stx_dev_alloc(ctx, std::max<size_t>((size_t)total * 4 * sizeof(double), 8), &P->d_pts));
+        STX_TRY(stx_dev_alloc(ctx, (size_t)P->min_cams * 90 * sizeof(double), &P->d_variants));
+        STX_TRY(stx_dev_alloc(ctx, (size_t)n_edges * 45 * sizeof(double), &P->d_out));
+        STX_HIP(hipMemcpyAsync(P->d_edge_cams.get(), edge_cams, (size_t)n_edges * 2 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        STX_HIP(hipMemcpyAsync(P->d_offsets.get(), offsets, ((size_t)n_edges + 1) * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+        if (total > 0) STX_HIP(hipMemcpyAsync(P->d_pts.get(), pts, (size_t)total * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        for (hipEvent_t& ev : P->ev)
+            if (hipEventCreate(&ev) != hipSuccess) return stx_fail(STX_ERR_HIP, "hipEventCreate failed");
+        STX_HIP(hipStreamSynchronize(ctx->stream));  // the caller's arrays are free again
+    }
+    *out = P.release();
+    return STX_OK;
+}
+
+STX_EXPORT int stx_ray_problem_eval(stx_ray_problem* P, int n_cams, const double* variants, double* out, double out_info[4])
+{
+    if (!P) return stx_fail(STX_ERR_INVALID, "problem is null");
+    if (out_info) std::fill(out_info, out_info + 4, 0.0);
+    if (n_cams < P->min_cams || n_cams > STX_RAY_MAX_CAMERAS)
+        return stx_fail(STX_ERR_INVALID, "ray adjustment of %d cameras: the edges name %d, the limit is %d", n_cams, P->min_cams, STX_RAY_MAX_CAMERAS);
+    if (n_cams > 0 && !variants) return stx_fail(STX_ERR_INVALID, "null argument");
+    for (size_t k = 0; k < (size_t)n_cams * 90; k++)
+        if (!std::isfinite(variants[k]))
+            return stx_fail(STX_ERR_INVALID, "camera %zu: variant %zu is not finite", k / 90, (k % 90) / 10);
+    if (out_info) { out_info[0] = P->n_edges; out_info[1] = (double)P->total; }
+    if (P->n_edges == 0) return STX_OK;
+    if (!out) return stx_fail(STX_ERR_INVALID, "null argument");
+    stx_ctx* ctx = P->ctx;
+    STX_TRY(stx_set_device(ctx));
+    STX_HIP(hipEventRecord(P->ev[0], ctx->stream));
+    STX_HIP(hipMemcpyAsync(P->d_variants.get(), variants, (size_t)P->min_cams * 90 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    STX_TRY(stx_launch_ray_normal_equations(ctx, P->n_edges, (const int*)P->d_edge_cams.get(), (const long long*)P->d_offsets.get(),
+                                            (const double*)P->d_pts.get(), (const double*)P->d_variants.get(), (double*)P->d_out.get(),
+                                            P->ev[1], P->ev[2]));
+    STX_HIP(hipMemcpyAsync(out, P->d_out.get(), (size_t)P->n_edges * 45 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    STX_HIP(hipEventRecord(P->ev[3], ctx->stream));
+    STX_HIP(hipStreamSynchronize(ctx->stream));  // the one wait
+    if (out_info) {
+        float a = 0.f, b = 0.f;
+        if (hipEventElapsedTime(&a, P->ev[1], P->ev[2]) != hipSuccess || hipEventElapsedTime(&b, P->ev[0], P->ev[3]) != hipSuccess)
+            return stx_fail(STX_ERR_HIP, "hipEventElapsedTime failed");
+        out_info[2] = a; out_info[3] = b;
+    }
+    return STX_OK;
+}
+
+STX_EXPORT int stx_ray_problem_free(stx_ray_problem* P)
+{
+    if (!P) return STX_OK;
+    if (P->n_edges > 0 && P->ctx) {
+        if (stx_set_device(P->ctx) == STX_OK) hipStreamSynchronize(P->ctx->stream);
+    }
+    delete P;  // the events go; the blocks go back to the context's allocator
+    return STX_OK;
+}

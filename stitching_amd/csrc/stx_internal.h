@@ -331,6 +331,21 @@ int stx_launch_match_ransac(stx_ctx* ctx, const StxMatchPair* d_pairs, int np, c
                             double threshold_sq, uint32_t seed, int* d_hyp);
 int stx_launch_match_pick(stx_ctx* ctx, const StxMatchPair* d_pairs, int np, const int* d_counts, const double* d_xyuv, int iters,
                           double threshold_sq, uint32_t seed, const int* d_hyp, int* d_pick, double* d_H, uint8_t* d_mask);
+// ray bundle adjustment (stx_cameras.hip; host side in stx_cameras_host.cpp) ---------------------------------------------------------
+// the edges of one adjustment, on the device for all its evaluations: cameras (i < j) per edge, the edges' first points (ascending,
+// first 0, n_edges + 1 entries), the points x, y, u, v; variants / out: the blocks every evaluation writes and reads
+constexpr int STX_RAY_LANES = 256;  // lanes of the ordered sum: the workgroup of ray_normal_equations
+struct stx_ray_problem {
+    stx_ctx* ctx = nullptr;
+    int n_edges = 0, min_cams = 0;  // min_cams: the largest camera an edge names, plus one
+    long long total = 0;
+    StxDevBlock d_edge_cams, d_offsets, d_pts, d_variants, d_out;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // start, launch, launch done, copy back queued
+    ~stx_ray_problem() { for (hipEvent_t e : ev) if (e) hipEventDestroy(e); }
+};
+// E, g[8], B upper triangle[36] of every edge -> d_out[45 n_edges]; start / stop (or null): recorded around the launch
+int stx_launch_ray_normal_equations(stx_ctx* ctx, int n_edges, const int* d_edge_cams, const long long* d_offsets, const double* d_pts,
+                                    const double* d_variants, double* d_out, hipEvent_t start, hipEvent_t stop);
 // cv::resize(INTER_LINEAR_EXACT) u8 (next rows N2 / N3); d_xt / d_yt: device tables of (offset, coeff1 | interior << 16)
 int stx_launch_resize_exact(stx_ctx* ctx, const stx_buf* src, stx_buf* dst, const int* d_xt, const int* d_yt, bool dilate,
                             const stx_buf* andmask);

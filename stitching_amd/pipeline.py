@@ -463,7 +463,8 @@ class Composer:
     Exposure gains and the "voronoi" / "no" seams are estimated on the device whatever the process-wide estimator settings are (nothing
     imports cv2); the "dp_*" and "gc_*" finders are cv2's, through SeamFinder; a finder object given as seam_estimator= (the project's
     own colour-aware ColorSeamEstimator, say) takes their place without cv2.  The subset step (Images.subset) is the caller's: pass
-    the images registration kept."""
+    the images registration kept.  `stitch` starts from the frames alone: it registers them with the project's own estimators
+    (FeatureEstimator, MatchEstimator, CameraSolver) and composes the images those kept."""
 
     DEFAULT_SETTINGS = {
         "medium_megapix": Images.Resolution.MEDIUM.value,
@@ -483,6 +484,7 @@ class Composer:
         """seam_estimator (not a setting): a finder object with find(imgs, corners, masks), e.g. a ColorSeamEstimator — `prepare` then finds
         its seams with it whatever "finder" names, and never looks for cv2."""
         self.seam_estimator = seam_estimator
+        self.registration = None  # of the last stitch(): indices of the images kept, their cameras, the solver's info
         for arg in kwargs:
             if arg not in self.DEFAULT_SETTINGS:
                 raise StitchingError("Invalid Argument: " + arg)
@@ -574,6 +576,35 @@ class Composer:
         """prepare + run -> the panorama (device-resident u8x3), as Stitcher.stitch returns it"""
         pano, _ = self.run(self.prepare(images, cameras))
         return pano
+
+    def stitch(self, images, feature_estimator=None, match_estimator=None, camera_solver=None):
+        """Frames in, panorama out (device-resident u8x3), with no cv2 and no cameras supplied: the registration half of Stitcher.stitch
+        (stitching/stitcher.py:99-105) by the project's own estimators — resize to MEDIUM on the device, FeatureEstimator.detect,
+        MatchEstimator.match, CameraSolver.register — then `compose` on the images registration kept.  The three objects default to
+        their classes' defaults.  `self.registration` keeps the indices of the images kept, their cameras and the solver's info."""
+        from .camera_estimation import CameraSolver
+        from .feature_estimation import FeatureEstimator
+        from .match_estimation import MatchEstimator
+
+        st, ctx = self.settings, self._ctx()
+        frames = [as_device(f, ctx) for f in images]
+        if len(frames) < 2:
+            raise StitchingError("stitching needs at least two images")
+        feature_estimator = feature_estimator or FeatureEstimator()
+        match_estimator = match_estimator or MatchEstimator()
+        camera_solver = camera_solver or CameraSolver()
+        imgs_obj = Images.of(frames, st["medium_megapix"], st["low_megapix"], st["final_megapix"])
+        prev = config.device_resident()
+        config.set_device_resident(True)
+        try:
+            medium = list(imgs_obj.resize(Images.Resolution.MEDIUM))
+        finally:
+            config.set_device_resident(prev)
+        features = feature_estimator.detect(medium)
+        matches = match_estimator.match(features, ctx=ctx)
+        indices, cameras = camera_solver.register(features, matches, ctx=ctx)
+        self.registration = {"indices": list(indices), "cameras": cameras, "info": camera_solver.info}
+        return self.compose([frames[i] for i in indices], cameras)
 
 
 def stitch(frames, cameras, **kw):

@@ -525,13 +525,8 @@ STX_DEV void co_normalise(const int (&acc)[3], float ws, int (&v)[3])
 
 // 7 wavefronts per SIMD (72 registers; the unconstrained build takes 78 -> 6): config 2's 1 680 workgroups are one resident set on
 // 256 CUs x 7, and a second round of a latency-bound kernel doubles its time
-#ifndef STX_COARSE_WAVES
-#define STX_COARSE_WAVES 7
-#endif
-#ifndef STX_COARSE_FAST
-#define STX_COARSE_FAST 1
-#endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(STX_COARSE_WAVES, 8))) void mb_coarse_kernel(MbCoarseK P)
+constexpr int COARSE_WAVES = 7;
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COARSE_WAVES, 8))) void mb_coarse_kernel(MbCoarseK P)
 {
     __shared__ short s0[3][CO_H0 * CO_W0];  // finished level B
     __shared__ short s1[3][CO_H1 * CO_W1];  // finished level B-1
@@ -551,7 +546,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(STX_COARSE_
     const int bx0 = max((ax0 >> 1) - 1, 0), bx1 = min((ax1 >> 1) + 1, pw0 - 1);
     const int by0 = max((ay0 >> 1) - 1, 0), by1 = min((ay1 >> 1) + 1, ph0 - 1);
     const int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1;
-#if STX_COARSE_FAST
     // the images that reach any of the three windows, in feed order, their three levels' descriptors in LDS; s_cnt = -1: the general path
     if (tid < 64) {
         int cnt = 0;
@@ -697,7 +691,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(STX_COARSE_
         }
         return;
     }
-#endif
+    // the general path
     for (int i = tid; i < bw * bh; i += 256) {  // level B: L_B = G_B, nothing above it
         const int yy = i / bw, xx = i - yy * bw;
         int v[3];
@@ -1711,11 +1705,7 @@ int stx_launch_seam_resize_batch(stx_ctx* ctx, int n, const stx_buf* const* seam
 // Same integers as resize_exact_kernel<1, true> (the tests compare both with the CPU checker).
 // ---------------------------------------------------------------------------------------------
 namespace {
-// rows per lane: -DSTX_SEAM1_ROWS=4 / 6 / 16 / 32 build the variants of the A/B (tools/gpu_r6g.sh)
-#ifndef STX_SEAM1_ROWS
-#define STX_SEAM1_ROWS 8
-#endif
-constexpr int SEAM1_COLS = 8, SEAM1_ROWS = STX_SEAM1_ROWS;
+constexpr int SEAM1_COLS = 8, SEAM1_ROWS = 8;  // pixels and rows per lane (the A/B of 4 / 6 / 8 / 16 / 32 rows is quoted above)
 constexpr int SEAM1_TW = 64 * SEAM1_COLS, SEAM1_TH = 4 * SEAM1_ROWS;
 struct Seam1K {
     const uint8_t* src; long long sstride; int sw, sh;  // the low-resolution seam mask as the seam finder made it

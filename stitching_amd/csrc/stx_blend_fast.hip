@@ -24,25 +24,14 @@ namespace {
 
 // waves per SIMD the level-0 gather is compiled for: 5 = 95 VGPRs without spills (A/B on one box: 218 us at 4, 206 us at 5,
 // 283 us at 6: 80 VGPRs spill in the collapse)
-#ifndef STX_L0_WAVES
-#define STX_L0_WAVES 5
-#endif
-// STX_L0_FULL = 1 (round 6, shipped): the level-0 gather issues EVERY load of an image in one batch — both pixel rows (a row outside the
-// image from the clamped row, its mask cleared), the pyrUp windows of the three planes — with the batched image search and the epilogue's
-// windows ahead in every instantiation: 92 registers = 5 wavefronts per SIMD instead of 80 = 6, and still 159.2 -> 147.9 us on config 2
-// (four interleaved runs, tools/gpu_r6w.sh), 176.7 -> 167.0 on the reference-default leg.  Each of the three alone, at 88-92 registers,
-// had measured slower than the plane-by-plane form at 80 (profiles/r06_round_trips.md): it is the whole chain that pays for the wavefront.
-// normalisation of the level-0 gather on integer counts (binary masks): bit 0 the packed shift form for counts <= 2, bit 1 the
-// one-multiplication form for counts < 16 (level0_epilogue_pk); 0 builds the shared-reciprocal IEEE division for every count above 1
-#ifndef STX_L0_NORM
-#define STX_L0_NORM 3
-#endif
-#ifndef STX_ABLATE_MASK
-#define STX_ABLATE_MASK 0
-#endif
-#ifndef STX_L0_FULL
-#define STX_L0_FULL 1
-#endif
+constexpr int L0_WAVES = 5;
+// (Round 6) the level-0 gather issues EVERY load of an image in one batch — both pixel rows (a row outside the image from the clamped
+// row, its mask cleared), the pyrUp windows of the three planes — with the batched image search and the epilogue's windows ahead in
+// every instantiation: 92 registers = 5 wavefronts per SIMD instead of 80 = 6, and still 159.2 -> 147.9 us on config 2 (four
+// interleaved runs), 176.7 -> 167.0 on the reference-default leg.  Each of the three alone, at 88-92 registers, had measured slower than
+// the plane-by-plane form at 80 (profiles/r06_round_trips.md): it is the whole chain that pays for the wavefront.
+// The level-0 gather normalises on integer counts (binary masks): the packed shift form for counts <= 2, the one-multiplication form
+// for counts < 16, the shared-reciprocal IEEE division above that (level0_epilogue_pk).
 constexpr float WEIGHT_EPS = 1e-5f;
 constexpr float INV255 = 0.0039215688593685627f;  // (float)(1./255.)
 constexpr float INV256 = 0.00390625f;
@@ -287,10 +276,6 @@ STX_DEV void load_px8_u8(const uint8_t* img0, uint32_t img0_stride, const uint8_
     pw[3] = __builtin_amdgcn_alignbyte(d1.x, d0.w, s);
     pw[4] = __builtin_amdgcn_alignbyte(d1.y, d1.x, s);
     pw[5] = __builtin_amdgcn_alignbyte(d1.z, d1.y, s);
-#if STX_ABLATE_MASK
-    mw[0] = vm0; mw[1] = vm1;  // timing experiment only: every mask byte taken as 255
-    return;
-#endif
     const uint32_t moff = (uint32_t)ly * mask0_stride + (uint32_t)(lx0 + 64);
     const STX_GAS uint8_t* mq = gp(mask0) - 64 + (moff & ~3u);
     const uint32_t ms = moff & 3u;
@@ -329,24 +314,16 @@ STX_DEV int h5i(int s0, int s1, int s2, int s3, int s4) { return s2 * 6 + (s1 + 
 constexpr int DN_TOW = 64, DN_TOH = 14, DN_ROWS = 2 * DN_TOH + 3;
 // tile rows (of 14 output rows) per XCD band of the level-0 pyrDown.  Round 4, interleaved: 1: 127.8 / 127.0 us, 2: 131.9 / 132.1, 4: 144.2 / 142.2;
 // the plain row-major order 129.2 / 126.8 at 1.6 x the fetched bytes
-#ifndef STX_DN_BAND
-#define STX_DN_BAND 1
-#endif
-constexpr int DN_BAND = STX_DN_BAND;
+constexpr int DN_BAND = 1;
 // The gather kernels of the levels: a wavefront owns 512 x 2 samples and shares nothing with its siblings (no LDS, no barrier), so a
 // workgroup is LV_WAVES independent wavefronts and the tile 512 x LV_TH.  One wavefront per workgroup: a wavefront that finishes frees
 // its slot at once instead of waiting for three siblings (level 0 of config 2: 176.5 / 176.4 us against 180.7 / 181.0 with four, 178.9 /
 // 178.3 with two; interleaved A/B on one box, round 4).
-#ifndef STX_LV_WG_WAVES
-#define STX_LV_WG_WAVES 1
-#endif
-constexpr int LV_WAVES = STX_LV_WG_WAVES, LV_TH = 2 * LV_WAVES, LV_THREADS = 64 * LV_WAVES;
+constexpr int LV_WAVES = 1, LV_TH = 2 * LV_WAVES, LV_THREADS = 64 * LV_WAVES;
 // sample rows per XCD band of the gather kernels.  Measured with one-wavefront workgroups (round 4, interleaved, level 0 of config 2):
 // 64: 181.1 / 180.7 us, 32: 175.9 / 175.9, 16: 172.4 / 174.5, 8: 170.4 / 173.1, 4: 171.0 / 173.1
-#ifndef STX_LV_BAND_ROWS
-#define STX_LV_BAND_ROWS 8
-#endif
-constexpr int LV_BAND = STX_LV_BAND_ROWS / LV_TH;  // tile rows per XCD band
+constexpr int LV_BAND_ROWS = 8;
+constexpr int LV_BAND = LV_BAND_ROWS / LV_TH;  // tile rows per XCD band
 
 // 36 bytes of an image row from byte offset `off` on (any alignment) as a little-endian byte stream w[0..8]
 STX_DEV void dn_load36(const STX_GAS uint8_t* img, uint32_t off, uint32_t (&w)[9])
@@ -385,27 +362,16 @@ STX_DEV void dn_pack5_channel(const uint32_t* w, short* hs)
 }
 
 // The four 1-4-6-4-1 row sums (stride 2) of 11 mask bits held as bytes 0 / 1 in mb[0..2] (byte 11 may hold anything); sums <= 16: exact
-// as floats.  STX_DN0_DOT4 = 1 (round 6, visit ab): bytes are what v_dot4_u32_u8 multiplies — 8 dot products against constant weight
-// dwords where the packed 16-bit form takes 9 v_perm + 10 v_pk_*; measured SLOWER (mb_down0 108.1 / 109.7 / 110.1 -> 110.5 / 111.3 /
-// 113.7 us, three interleaved runs of config 2): the dot product does not issue at the rate of the packed instructions.  Default 0.
-#ifndef STX_DN0_DOT4
-#define STX_DN0_DOT4 0
-#endif
+// as floats.  The packed 16-bit form takes 9 v_perm + 10 v_pk_*; 8 v_dot4_u32_u8 against constant weight dwords measured SLOWER
+// (round 6: mb_down0 108.1 / 109.7 / 110.1 -> 110.5 / 111.3 / 113.7 us, three interleaved runs of config 2): the dot product does not
+// issue at the rate of the packed instructions.
 STX_DEV float4 dn_mask_sums4(const uint32_t (&mb)[3])
 {
-#if STX_DN0_DOT4
-    const uint32_t o0 = __builtin_amdgcn_udot4(mb[0], 0x04060401u, mb[1] & 1u, false);                                      // bytes 0 .. 4
-    const uint32_t o1 = __builtin_amdgcn_udot4(mb[1], 0x00010406u, __builtin_amdgcn_udot4(mb[0], 0x04010000u, 0u, false), false);  // 2 .. 6
-    const uint32_t o2 = __builtin_amdgcn_udot4(mb[1], 0x04060401u, mb[2] & 1u, false);                                      // 4 .. 8
-    const uint32_t o3 = __builtin_amdgcn_udot4(mb[2], 0x00010406u, __builtin_amdgcn_udot4(mb[1], 0x04010000u, 0u, false), false);  // 6 .. 10
-    return make_float4((float)o0, (float)o1, (float)o2, (float)o3);
-#else
     const pk16 o01 = pk(pair_u8<0, 2>(mb)) + pk(pair_u8<4, 6>(mb)) + pk(pair_u8<2, 4>(mb)) * pk_splat(6) +
                      (pk(pair_u8<1, 3>(mb)) + pk(pair_u8<3, 5>(mb))) * pk_splat(4);
     const pk16 o23 = pk(pair_u8<4, 6>(mb)) + pk(pair_u8<8, 10>(mb)) + pk(pair_u8<6, 8>(mb)) * pk_splat(6) +
                      (pk(pair_u8<5, 7>(mb)) + pk(pair_u8<7, 9>(mb))) * pk_splat(4);
     return make_float4((float)(unpk(o01) & 0xffffu), (float)(unpk(o01) >> 16), (float)(unpk(o23) & 0xffffu), (float)(unpk(o23) >> 16));
-#endif
 }
 
 // level 0 (u8 BGR + u8 mask): 4 outputs from 11 input pixels
@@ -535,13 +501,6 @@ STX_DEV void dn_note_occ(uint8_t* __restrict__ occ, uint32_t nzbits, int tid, in
     occ[(long long)((Y0 >> 1) + rg) * occ_pitch(ow) + (X0 >> 6)] = half != 0u ? 1 : 0;
 }
 
-#ifndef STX_DN0_REV
-#define STX_DN0_REV 1
-#endif
-// bit 0: the binary-mask instantiation, bit 1: the grey-mask one
-#ifndef STX_DN0_BATCH
-#define STX_DN0_BATCH 3
-#endif
 // blockIdx.z = image: all fed images are processed by one launch (deferred pyramid build)
 // WEIGHTS = false: G_1 alone — W_1 and its occupancy map are the handle's (stx_blend_use_weights), the mask is not read, there is no
 // s_w array.  Image sums, border handling, tile order and the G_1 stores are those of WEIGHTS = true.
@@ -550,11 +509,11 @@ __global__ __launch_bounds__(256) void mb_down0_lds_kernel(const StxMbImage* __r
 {
     __shared__ __attribute__((aligned(16))) short s_h[3][DN_ROWS][DN_TOW];  // horizontal sums, <= 255*16
     __shared__ __attribute__((aligned(16))) float s_w[WEIGHTS ? DN_ROWS : 1][WEIGHTS ? DN_TOW : 4];
-    // (round 6, STX_DN0_REV) The launch walks the images and their tiles in the REVERSE of the order the batched warp wrote them: the
+    // (round 6) The launch walks the images and their tiles in the REVERSE of the order the batched warp wrote them: the
     // warped images of a panorama (317 MB on config 2) are a little more than the 256 MB Infinity Cache holds, so a second pass in the
     // same order finds every line evicted just before it asks for it, while the reverse pass starts on what was written last.
     // (gridDim.x - 1 - b keeps b mod 8: the tiles of a band still meet on one XCD.)
-    const uint32_t zz = STX_DN0_REV ? gridDim.z - 1u - blockIdx.z : blockIdx.z, bb = STX_DN0_REV ? gridDim.x - 1u - blockIdx.x : blockIdx.x;
+    const uint32_t zz = gridDim.z - 1u - blockIdx.z, bb = gridDim.x - 1u - blockIdx.x;
     const StxMbImage& im = images[zz];
     const int tid = threadIdx.x;
     const int ow = im.fw >> 1, oh = im.fh >> 1;
@@ -571,7 +530,7 @@ __global__ __launch_bounds__(256) void mb_down0_lds_kernel(const StxMbImage* __r
         uint32_t is = (uint32_t)im.img0_stride, ms = WEIGHTS ? (uint32_t)im.mask0_stride : 0u;
         unsigned long long ia = (unsigned long long)im.img0, ma = WEIGHTS ? (unsigned long long)im.mask0 : 0ull;
         // (the binary-mask instantiation only: the grey-mask one measured 148 -> 155 us with its fields pinned, three interleaved runs of the
-        // reference-default leg, tools/gpu_r6r.sh; the binary one 121.7 -> 120.1)
+        // reference-default leg; the binary one 121.7 -> 120.1)
         if (PK) asm volatile("" : "+s"(fw), "+s"(fh), "+s"(iw_), "+s"(ih_), "+s"(left), "+s"(top), "+s"(is), "+s"(ms), "+s"(ia), "+s"(ma));
         D.fw = fw; D.fh = fh; D.iw = iw_; D.ih = ih_; D.left = left; D.top = top; D.img0_stride = is; D.mask0_stride = ms;
         D.img0 = (const uint8_t*)ia; D.mask0 = (const uint8_t*)ma;
@@ -600,7 +559,7 @@ __global__ __launch_bounds__(256) void mb_down0_lds_kernel(const StxMbImage* __r
     // take their six image loads and two mask loads in ONE batch.  The task loop below makes four dependent memory round trips of them
     // (image, then the mask behind its row test; twice) in front of the workgroup's barrier.
     bool batched = false;
-    if ((STX_DN0_BATCH & (PK ? 1 : 2)) && near) {
+    if (near) {
         const int q = tid & 15, rA = tid >> 4;
         const int xo = X0 + 4 * q, c0 = 2 * xo - 2, a0 = c0 - D.left;
         const bool col_ok = xo < ow;
@@ -633,11 +592,7 @@ __global__ __launch_bounds__(256) void mb_down0_lds_kernel(const StxMbImage* __r
                     // the mask's 11 bytes (cleared below for a row outside the image and for a run in the frame: the weight's border is CONSTANT 0)
                     const uint32_t moff = (uint32_t)min(max(by, 0), D.ih - 1) * (uint32_t)D.mask0_stride + (uint32_t)acol;
                     msh[t] = moff & 3u;
-#if STX_ABLATE_MASK
-                    mq4[t] = v4u{0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};  // timing experiment only
-#else
                     mq4[t] = *reinterpret_cast<const STX_GAS v4u_a4*>(gp(D.mask0) + (moff & ~3u));
-#endif
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -1192,7 +1147,7 @@ STX_DEV bool occ_hit(const StxMbImage& im, int lv, int tile_x, int Y0)
     return occ_hit_f<L0>(im.occ[L0 ? 1 : lv], im.fx, im.fy, im.fw, im.fh, lv, tile_x, Y0);
 }
 
-template <bool WF, bool AHEAD = true>
+template <bool WF>
 STX_DEV void level0_epilogue_pk(const MbLevelK& P, int X0, int Y0, uint32_t (&acc)[2][3][4], uint32_t (&cnt)[2][4], const float (*ws)[8]);
 
 // CONTRIB: the image table may hold received contribution strips (kind 1); EMIT: write un-normalised sums.
@@ -1644,8 +1599,7 @@ STX_DEV uint32_t bgr_dword(const uint32_t (&U)[3][4])
 
 // WF: the weight sums are fp32 values `ws` (grey masks somewhere under the wavefront): every pixel takes the division, and `cnt` holds
 // 1 / 0 per pixel for "weight sum > WEIGHT_EPS" (only the final mask and the zeroing look at it)
-// AHEAD: the pyrUp windows of the finished level 1 are loaded ahead of their use (see below); costs registers
-template <bool WF, bool AHEAD>
+template <bool WF>
 STX_DEV void level0_epilogue_pk(const MbLevelK& P, int X0, int Y0, uint32_t (&acc)[2][3][4], uint32_t (&cnt)[2][4], const float (*ws)[8])
 {
     // The constants (1, 1) and (-1, -1) as values the compiler cannot see through: against literal constants LLVM rewrites
@@ -1670,7 +1624,7 @@ STX_DEV void level0_epilogue_pk(const MbLevelK& P, int X0, int Y0, uint32_t (&ac
                     const pk16s a = pks(acc[r][c][q]);
                     v[r][c][q] = unpks(a - __builtin_elementwise_min(__builtin_elementwise_max(a, pks(k_m1)), pks(k_p1)));  // a - sign(a)
                 }
-    } else if (!WF && (STX_L0_NORM & 1) && (cnt3 & 0xfffcfffcu) == 0u) {
+    } else if (!WF && (cnt3 & 0xfffcfffcu) == 0u) {
         // (round 6) at most TWO images over every pixel of the lane — all an un-pitched ring ever has.  For an integer count n <= 16 and
         // |a| <= 32768, (int)(a / (n + 1e-5f)) = trunc((a - sign(a)) / n): the quotient falls short of a / n by a * 1e-5 / n^2 < 1 / n,
         // 40+ ulps when a / n is an integer (tests/test_host_logic.py checks every a and n against IEEE division).  For n = 1, 2 that
@@ -1689,9 +1643,11 @@ STX_DEV void level0_epilogue_pk(const MbLevelK& P, int X0, int Y0, uint32_t (&ac
                 }
             }
     } else {
-        // (round 6) integer counts below 16: the same quotients from ONE multiplication by v_rcp_f32's reciprocal (1 ulp) — the distance
-        // of a / (n + 1e-5f) to the next integer is 1000 x the error of the product (checked for every a, n <= 30 and reciprocals 2 ulps off)
-        const bool small = !WF && (STX_L0_NORM & 2) && (anyc & 0xfff0fff0u) == 0u;
+        // (round 6) integer counts below 16: the same quotients from ONE multiplication by v_rcp_f32's reciprocal (1 ulp).  Where a / n
+        // is an integer, a / (n + 1e-5f) falls short of it by the relative gap 1e-5 / n, and the product must not close that gap: at
+        // n = 15 it is 6.7e-7 against the 1.8e-7 of reciprocal + multiplication, a margin of 3 - 4 x (checked for every a, n <= 30 and
+        // reciprocals 2 ulps off).  n < 16 is a HARD limit: the margin shrinks as 1 / n, so the test below must not be widened.
+        const bool small = !WF && (anyc & 0xfff0fff0u) == 0u;
 #pragma unroll
         for (int r = 0; r < 2; r++)
 #pragma unroll
@@ -1719,28 +1675,22 @@ STX_DEV void level0_epilogue_pk(const MbLevelK& P, int X0, int Y0, uint32_t (&ac
     }
     // ---- + pyrUp(finished level 1), saturating
     if (P.up) {
-        // (round 6) AHEAD: the windows of the planes of the finished level 1 are loaded ahead of their use — planes 0 and 1 together,
-        // plane 2 while plane 0 is worked on: two memory round trips at the end of every wavefront where a branch between the planes
-        // made three.  It costs 12 registers: free for the instantiations that hold 88 anyway (grey-mask deferral, contribution strips:
-        // the reference-default leg's level 0 193 -> 179 us together with the batched image search), one wavefront per SIMD less for the
-        // binary-mask instantiation at 80 (measured: +1.4 us) — which therefore keeps the plane-by-plane form.
+        // (round 6) the windows of the planes of the finished level 1 are loaded ahead of their use — planes 0 and 1 together, plane 2
+        // while plane 0 is worked on: two memory round trips at the end of every wavefront where a branch between the planes made
+        // three.  It costs 12 registers: the reference-default leg's level 0 193 -> 179 us together with the batched image search.
+        // (Alone it cost the binary-mask instantiation of mb_level0_pk_kernel, then at 80 registers, a wavefront per SIMD and +1.4 us;
+        // the whole batched chain pays for that wavefront: see the top of the file.)
         v4u uw[3][3];
         const short* const plane0 = P.up - ((long long)P.up_y0 * P.up_stride + P.up_x0);
-        if (AHEAD) {
-            up_patch_pks_load(gp(plane0), (uint32_t)P.up_stride, P.ph >> 1, (uint32_t)(X0 >> 1) * 2u, Y0 >> 1, uw[0]);
-            up_patch_pks_load(gp(plane0 + P.up_plane), (uint32_t)P.up_stride, P.ph >> 1, (uint32_t)(X0 >> 1) * 2u, Y0 >> 1, uw[1]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        up_patch_pks_load(gp(plane0), (uint32_t)P.up_stride, P.ph >> 1, (uint32_t)(X0 >> 1) * 2u, Y0 >> 1, uw[0]);
+        up_patch_pks_load(gp(plane0 + P.up_plane), (uint32_t)P.up_stride, P.ph >> 1, (uint32_t)(X0 >> 1) * 2u, Y0 >> 1, uw[1]);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             const short* plane = P.up + c * P.up_plane - ((long long)P.up_y0 * P.up_stride + P.up_x0);
-            if (AHEAD) {
-                if (c == 0) {
-                    up_patch_pks_load(gp(plane0 + 2 * P.up_plane), (uint32_t)P.up_stride, P.ph >> 1, (uint32_t)(X0 >> 1) * 2u, Y0 >> 1, uw[2]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            } else {
-                up_patch_pks_load(gp(plane), (uint32_t)P.up_stride, P.ph >> 1, (uint32_t)(X0 >> 1) * 2u, Y0 >> 1, uw[c]);
+            if (c == 0) {
+                up_patch_pks_load(gp(plane0 + 2 * P.up_plane), (uint32_t)P.up_stride, P.ph >> 1, (uint32_t)(X0 >> 1) * 2u, Y0 >> 1, uw[2]);
+                __builtin_amdgcn_sched_barrier(0);
             }
             pk16s up[2][4];
             if (!up_patch_pks_math(uw[c], up_sel(X0 == 0, (X0 >> 1) + 4 >= (P.pw >> 1)), up)) {
@@ -1812,7 +1762,7 @@ STX_DEV void level0_epilogue_pk(const MbLevelK& P, int X0, int Y0, uint32_t (&ac
 // storing.  A resized seam mask is grey along the seams only: 1 - 2 % of the lanes (round 3 switched the WHOLE wavefront to fp32 sums at
 // its first grey byte: 40 % of the wavefronts of the default pipeline).
 template <bool CONTRIB, bool DEFER = false>
-__global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(STX_L0_WAVES, 8))) void mb_level0_pk_kernel(MbLevelK P)
+__global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(L0_WAVES, 8))) void mb_level0_pk_kernel(MbLevelK P)
 {
     const int tid = threadIdx.x;
     int tile_tx, tile_ty;
@@ -1836,26 +1786,17 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(STX_
         bool hit = false;
         {
             const int kk = base + (tid & 63);
-            // (round 6) size and corner of the lane's image as ONE 16-byte load and tests without short circuits: `&&` had become three
-            // dependent loads, each behind its own branch (see mb_level_pk_kernel)
             // (round 6) size and corner of the lane's image as ONE 16-byte load and tests without short circuits (`&&` had become three
-            // dependent loads, each behind its own branch: see mb_level_pk_kernel) — where its 8 registers are free (see level0_epilogue_pk)
-            if (DEFER || CONTRIB || STX_L0_FULL) {
-                const StxMbImage& im = P.images[min(kk, P.n_images - 1)];
-                const v4u f = *reinterpret_cast<const v4u_a4*>(&im.iw);  // iw, ih, ix, iy
-                const v4u ff = *reinterpret_cast<const v4u_a4*>(&im.fx);  // fx, fy, fw, fh
-                const uint8_t* const occp = im.occ[1];
-                const int kind = CONTRIB ? im.kind : 0;
-                int rx = (int)f.z, ry = (int)f.w, rw = (int)f.x, rh = (int)f.y;
-                if (CONTRIB && kind == 1) { rx = (int)ff.x; ry = (int)ff.y; rw = (int)ff.z; rh = (int)ff.w; }
-                hit = (kk < P.n_images) & (rx < tile_x + 512) & (rx + rw > tile_x) & (ry < Y0 + 2) & (ry + rh > Y0);
-                if (hit) hit = occ_hit_f<true>(occp, (int)ff.x, (int)ff.y, (int)ff.z, (int)ff.w, 0, tile_x, Y0);
-            } else if (kk < P.n_images) {
-                const StxMbImage& im = P.images[kk];
-                const int rx = im.ix, ry = im.iy, rw = im.iw, rh = im.ih;
-                hit = rx < tile_x + 512 && rx + rw > tile_x && ry < Y0 + 2 && ry + rh > Y0;
-                if (hit) hit = occ_hit<true>(im, 0, tile_x, Y0);
-            }
+            // dependent loads, each behind its own branch: see mb_level_pk_kernel)
+            const StxMbImage& im = P.images[min(kk, P.n_images - 1)];
+            const v4u f = *reinterpret_cast<const v4u_a4*>(&im.iw);  // iw, ih, ix, iy
+            const v4u ff = *reinterpret_cast<const v4u_a4*>(&im.fx);  // fx, fy, fw, fh
+            const uint8_t* const occp = im.occ[1];
+            const int kind = CONTRIB ? im.kind : 0;
+            int rx = (int)f.z, ry = (int)f.w, rw = (int)f.x, rh = (int)f.y;
+            if (CONTRIB && kind == 1) { rx = (int)ff.x; ry = (int)ff.y; rw = (int)ff.z; rh = (int)ff.w; }
+            hit = (kk < P.n_images) & (rx < tile_x + 512) & (rx + rw > tile_x) & (ry < Y0 + 2) & (ry + rh > Y0);
+            if (hit) hit = occ_hit_f<true>(occp, (int)ff.x, (int)ff.y, (int)ff.z, (int)ff.w, 0, tile_x, Y0);
         }
         unsigned long long todo = __ballot(hit);
         while (todo) {
@@ -1898,9 +1839,8 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(STX_
             if (lx0 + 8 <= 0 || lx0 >= i_iw || ly0 + 2 <= 0 || ly0 >= i_ih) continue;
             // lanes partly left / right of the image take the same aligned loads (load_px8_u8): no per-pixel path
             uint32_t pw_[2][6], mw[2][2];
-#if STX_L0_FULL
             // every load of the image in one batch: both pixel rows (clamped row, mask cleared when outside) and the pyrUp windows of the planes
-            const uint32_t g1_boff_f = (uint32_t)((X0 - i_fx) >> 1);
+            const uint32_t g1_boff = (uint32_t)((X0 - i_fx) >> 1);  // this lane's samples of G_1 (bytes): offset in a row
             v3u win[3][3];
 #pragma unroll
             for (int r = 0; r < 2; r++) {
@@ -1910,19 +1850,8 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(STX_
             }
 #pragma unroll
             for (int c = 0; c < 3; c++)
-                up_patch_pk_load(gp(reinterpret_cast<const uint8_t*>(G1_a)) + (uint32_t)c * g1p, g1s, i_fh >> 1, g1_boff_f, (Y0 - i_fy) >> 1, win[c]);
+                up_patch_pk_load(gp(reinterpret_cast<const uint8_t*>(G1_a)) + (uint32_t)c * g1p, g1s, i_fh >> 1, g1_boff, (Y0 - i_fy) >> 1, win[c]);
             __builtin_amdgcn_sched_barrier(0);
-#else
-#pragma unroll
-            for (int r = 0; r < 2; r++) {
-                const int ly = ly0 + r;
-#pragma unroll
-                for (int q = 0; q < 6; q++) pw_[r][q] = 0;
-                mw[r][0] = mw[r][1] = 0;
-                if ((unsigned)ly >= (unsigned)i_ih) continue;
-                load_px8_u8((const uint8_t*)I_a, ist, (const uint8_t*)M_a, mst, lx0, ly, 0xffffffffu, 0xffffffffu, pw_[r], mw[r]);
-            }
-#endif
             {   // mask bytes of the pixels outside the image: cleared (after the loads: two registers less while they are in flight)
                 uint32_t vm0, vm1;
                 lane_valid_bytes(lx0, i_iw, vm0, vm1);
@@ -1938,7 +1867,6 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(STX_
                     }
             }
             // (no early-out on an all-zero mask: it would put the G_1 loads behind the mask loads' round trip)
-            const uint32_t g1_boff = (uint32_t)((X0 - i_fx) >> 1);  // this lane's samples of G_1 (bytes): offset in a row
             const UpSel g1_sel = up_sel_u8(X0 == i_fx, ((X0 - i_fx) >> 1) + 4 >= (i_fw >> 1));
             uint32_t M[2][4];
 #pragma unroll
@@ -1956,11 +1884,7 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(STX_
 #pragma unroll
             for (int c = 0; c < 3; c++) {
                 pk16 up[2][4];
-#if STX_L0_FULL
                 up_patch_pk_math(win[c], g1_sel, up);
-#else
-                up_patch_pk(gp(reinterpret_cast<const uint8_t*>(G1_a)) + (uint32_t)c * g1p, g1s, i_fh >> 1, g1_boff, (Y0 - i_fy) >> 1, g1_sel, up);
-#endif
 #pragma unroll
                 for (int r = 0; r < 2; r++) {
                     uint32_t px[4];
@@ -2010,7 +1934,7 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(STX_
         cnt[r][2] = pair_u8<1, 3>(cntb[r]);
         cnt[r][3] = pair_u8<5, 7>(cntb[r]);
     }
-    level0_epilogue_pk<false, DEFER || CONTRIB || STX_L0_FULL>(P, X0, Y0, acc, cnt, nullptr);
+    level0_epilogue_pk<false>(P, X0, Y0, acc, cnt, nullptr);
 }
 
 
@@ -2121,20 +2045,13 @@ STX_DEV uint32_t min3u(uint32_t a, uint32_t b, uint32_t c) { return min(min(a, b
 STX_DEV uint32_t max3u(uint32_t a, uint32_t b, uint32_t c) { return max(max(a, b), c); }
 
 // at least 3 wavefronts per SIMD (168 registers): the batched loads of round 6 would otherwise take 174 and leave two.
-// Measured forms (one box, interleaved, tools/gpu_r6o.sh / gpu_r6p.sh; mb_level of config 2 = levels 1 + 2 / the four launches of the
-// reference-default leg / of config 4's share):  HEAD (loads plane by plane, 103 registers, 4 per SIMD): 84.8 / 128.0 / 332.4 us;
-// STX_LVPK_LOOP = 1 (all loads of an image in one batch, 3 per SIMD: shipped): 79.1 / 116.3 / 308.7;  STX_LVPK_LOOP = 0 with the batched
-// image search and the windows of the epilogue ahead, held to 4 per SIMD (128 registers, 19 spill instructions): 89.5 / 146.5 / 376.6.
-#ifndef STX_LVPK_WAVES
-#define STX_LVPK_WAVES 3
-#endif
-#ifndef STX_LVPK_EPI
-#define STX_LVPK_EPI 3
-#endif
-#ifndef STX_LVPK_LOOP
-#define STX_LVPK_LOOP 1
-#endif
-__global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(STX_LVPK_WAVES, 8))) void mb_level_pk_kernel(MbLevelK P)
+// Measured forms (round 6, one box, interleaved; mb_level of config 2 = levels 1 + 2 / the four launches of the reference-default leg /
+// of config 4's share):  all loads of an image in one batch and the three windows of the epilogue ahead, 3 per SIMD (this form):
+// 79.1 / 116.3 / 308.7 us;  loads plane by plane, 103 registers, 4 per SIMD: 84.8 / 128.0 / 332.4;  loads plane by plane with the
+// batched image search and the windows of the epilogue ahead, held to 4 per SIMD (128 registers, 19 spill instructions):
+// 89.5 / 146.5 / 376.6.
+constexpr int LVPK_WAVES = 3;
+__global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LVPK_WAVES, 8))) void mb_level_pk_kernel(MbLevelK P)
 {
     const int tid = threadIdx.x;
     const int lv = P.level;
@@ -2213,17 +2130,14 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(STX_
             const UpSel g1_sel = up_sel_u8(lx0 == 0, (lx0 >> 1) + 4 >= (lw >> 1));
             v3u win[3][3];
             v2u grow[3][2];
-#define STX_LVPK_LOAD(c)                                                                                                            \
-    {                                                                                                                              \
-        up_patch_pk_load(gp(reinterpret_cast<const uint8_t*>(G1_a)) + (uint32_t)(c) * g1p, g1s, lh >> 1, g1_boff, ly0 >> 1, win[c]);    \
-        _Pragma("unroll") for (int r = 0; r < 2; r++)                                                                              \
-            grow[c][r] = g8_row_load(gp(reinterpret_cast<const uint8_t*>(G0_a)) + (uint32_t)(c) * g0p, ly0 + r, g0s, (uint32_t)lx0);   \
-    }
-#if STX_LVPK_LOOP
 #pragma unroll
-            for (int c = 0; c < 3; c++) STX_LVPK_LOAD(c)
+            for (int c = 0; c < 3; c++) {
+                up_patch_pk_load(gp(reinterpret_cast<const uint8_t*>(G1_a)) + (uint32_t)c * g1p, g1s, lh >> 1, g1_boff, ly0 >> 1, win[c]);
+#pragma unroll
+                for (int r = 0; r < 2; r++)
+                    grow[c][r] = g8_row_load(gp(reinterpret_cast<const uint8_t*>(G0_a)) + (uint32_t)c * g0p, ly0 + r, g0s, (uint32_t)lx0);
+            }
             __builtin_amdgcn_sched_barrier(0);
-#endif
             bool all1;
             if (w_half) {
                 // "all sixteen are 1" is decided on the half patterns themselves (weights are in [0, 1]: unsigned order = float order;
@@ -2245,9 +2159,6 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(STX_
 #pragma unroll
                 for (int c = 0; c < 3; c++) {
                     pk16 upk[2][4];
-#if !STX_LVPK_LOOP
-                    STX_LVPK_LOAD(c)
-#endif
                     up_patch_pk_math(win[c], g1_sel, upk);
 #pragma unroll
                     for (int r = 0; r < 2; r++) {
@@ -2280,9 +2191,6 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(STX_
 #pragma unroll
             for (int c = 0; c < 3; c++) {
                 pk16 upk[2][4];
-#if !STX_LVPK_LOOP
-                STX_LVPK_LOAD(c)
-#endif
                 up_patch_pk_math(win[c], g1_sel, upk);
 #pragma unroll
                 for (int r = 0; r < 2; r++) {
@@ -2348,26 +2256,12 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(STX_
         // (round 6) the windows of the planes are loaded ahead of their use (they were three round trips: a branch sat between the planes)
         v4u uw[3][3];
         const short* const plane0 = P.up - ((long long)P.up_y0 * P.up_stride + P.up_x0);
-#if STX_LVPK_EPI == 3
 #pragma unroll
         for (int c = 0; c < 3; c++) up_patch_pks_load(gp(plane0 + c * P.up_plane), (uint32_t)P.up_stride, P.ph >> 1, (uint32_t)(X0 >> 1) * 2u, Y0 >> 1, uw[c]);
         __builtin_amdgcn_sched_barrier(0);
-#elif STX_LVPK_EPI == 2
-        up_patch_pks_load(gp(plane0), (uint32_t)P.up_stride, P.ph >> 1, (uint32_t)(X0 >> 1) * 2u, Y0 >> 1, uw[0]);
-        up_patch_pks_load(gp(plane0 + P.up_plane), (uint32_t)P.up_stride, P.ph >> 1, (uint32_t)(X0 >> 1) * 2u, Y0 >> 1, uw[1]);
-        __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             const short* plane = P.up + c * P.up_plane - ((long long)P.up_y0 * P.up_stride + P.up_x0);
-#if STX_LVPK_EPI == 2
-            if (c == 0) {
-                up_patch_pks_load(gp(plane0 + 2 * P.up_plane), (uint32_t)P.up_stride, P.ph >> 1, (uint32_t)(X0 >> 1) * 2u, Y0 >> 1, uw[2]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#elif STX_LVPK_EPI < 2
-            up_patch_pks_load(gp(plane), (uint32_t)P.up_stride, P.ph >> 1, (uint32_t)(X0 >> 1) * 2u, Y0 >> 1, uw[c]);
-#endif
             pk16s up[2][4];
             if (!up_patch_pks_math(uw[c], usel, up)) {
                 int u32[2][8];
@@ -2420,14 +2314,12 @@ bool stx_fast_mb_down_batch(stx_ctx* ctx, const StxMbImage* d_images, const StxM
     // kernel time and equal end-to-end throughput (A/B on one box, two panoramas in flight: 116.1 / 116.9 against
     // 116.5 / 116.9 Gpix/s) — kept for the HBM traffic they leave to the co-running kernels.
     StxTileMap M = stx_tile_map((mw + DN_TOW - 1) / DN_TOW, (mh + DN_TOH - 1) / DN_TOH, DN_BAND);
-    // Levels 1 and 2 in XCD bands too (round 6, visits af / ag).  Round 4 had measured the bands 15 % SLOWER on level 1 -> 2 (103 against
+    // Levels 1 and 2 in XCD bands too (round 6).  Round 4 had measured the bands 15 % SLOWER on level 1 -> 2 (103 against
     // 88 us) and kept the plain row-major order from level 1 on, at 1.8 x the algorithmic bytes fetched; on the batched-load kernel of round 6
     // the bands win: mb_down x 4 88.7 -> 80 us, value +1.0 %, latency 0.683 -> 0.66 ms (three interleaved runs; bands on the levels >= 3 as well
-    // change nothing more).  STX_DN_PLAIN_FROM = first level in plain order.
-#ifndef STX_DN_PLAIN_FROM
-#define STX_DN_PLAIN_FROM 3
-#endif
-    M.plain = level >= STX_DN_PLAIN_FROM;
+    // change nothing more).
+    constexpr int DN_PLAIN_FROM = 3;  // first level in plain order
+    M.plain = level >= DN_PLAIN_FROM;
     bool pk_ok = true;  // packed 16-bit row sums need u8 images with 0 / 255 masks
     for (int i = 0; i < n; i++) pk_ok = pk_ok && !h_images[i].img0_is_s16 && h_images[i].mask_binary;
     dim3 grid(stx_tile_grid(M), 1, n);

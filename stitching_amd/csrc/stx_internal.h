@@ -5,6 +5,7 @@
 
 #include <atomic>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <map>
@@ -235,6 +236,13 @@ struct StxMbImage {  // device-visible descriptor of one fed image (all levels)
     // seam masks, exchange strips) a wavefront at a time.
     uint8_t* occ[STX_MAX_BANDS + 1];
 };
+// the gather kernels fetch (iw, ih, ix, iy) and (fx, fy, fw, fh) as ONE 16-byte load each, from &im.iw and &im.fx, on 4-byte alignment
+static_assert(offsetof(StxMbImage, ih) == offsetof(StxMbImage, iw) + 4 && offsetof(StxMbImage, ix) == offsetof(StxMbImage, iw) + 8 &&
+                  offsetof(StxMbImage, iy) == offsetof(StxMbImage, iw) + 12 && offsetof(StxMbImage, iw) % 4 == 0,
+              "StxMbImage: iw, ih, ix, iy must be four adjacent ints");
+static_assert(offsetof(StxMbImage, fy) == offsetof(StxMbImage, fx) + 4 && offsetof(StxMbImage, fw) == offsetof(StxMbImage, fx) + 8 &&
+                  offsetof(StxMbImage, fh) == offsetof(StxMbImage, fx) + 12 && offsetof(StxMbImage, fx) % 4 == 0,
+              "StxMbImage: fx, fy, fw, fh must be four adjacent ints");
 // pyr_mode / pyr_lanes: STX_PYRDOWN_* (include/stitching_amd.h); anything but SCALAR builds every level with the generic kernels
 // weights = false: the G planes alone (all images of the call; their weights were adopted from a stx_mb_weights handle)
 int stx_launch_mb_pyramids(stx_ctx* ctx, const StxMbImage* d_images, const StxMbImage* h_images, int n, int num_bands, int pyr_mode,

@@ -34,30 +34,15 @@ constexpr int WARP_TH = 4;    // tile height (4 waves x 1 row)
 // every block: 2 blocks per wavefront 212 us against 180 us with 1 — gfx9 has one vmcnt for loads and stores, so the second block's
 // sample loads could not be waited for without also waiting for the first block's stores.  Round 4 samples every block before the first
 // result leaves (the stores follow the loop): 179.4 / 182.8 us with 2 blocks against 177.5 / 178.1 with 1 — the diagnosis was right and
-// the prologue it saves is worth nothing measurable.  1 it stays (-DSTX_WARP_IT=2 builds the other).
-#ifndef STX_WARP_GAIN_EARLY
-#define STX_WARP_GAIN_EARLY 1
-#endif
-#ifndef STX_WARP_IT
-#define STX_WARP_IT 1
-#endif
-constexpr int WARP_IT = STX_WARP_IT;
+// the prologue it saves is worth nothing measurable.  1 it stays (the loops over WARP_IT blocks remain generic in it).
+constexpr int WARP_IT = 1;
 constexpr int WARP_FTH = WARP_TH * WARP_IT;  // tile height of the fast kernel
 // wavefronts per workgroup of the fast kernel (they share nothing: no workgroup barrier, LDS per wavefront): its tile is 64 x this wide.
 // Measured (round 4, one box, interleaved, config 2): 1: 175.8 / 174.2 us, 2: 177.0 / 177.0, 4: 178.4 / 178.8, 8: 193.9 / 191.2 — a
 // wavefront that finishes frees its slot for the next workgroup at once instead of waiting for its three siblings.
-#ifndef STX_WARP_WAVES
-#define STX_WARP_WAVES 1
-#endif
-constexpr int WARP_FW = 64 * STX_WARP_WAVES;
-#ifndef STX_WARP_BAND
-#define STX_WARP_BAND 4
-#endif
-// STX_WARP_ZGRID = 1 (A/B only): the grid of rounds 1-5, (workgroups of the LARGEST image, 1, images) — see WarpBatchK::first_wg
-#ifndef STX_WARP_ZGRID
-#define STX_WARP_ZGRID 0
-#endif
-constexpr int WARP_BAND = STX_WARP_BAND;  // tile rows per XCD band (fast kernel); measured 1: 548, 2: 424, 4: 360, 8: 327, 16: 311 MB fetched
+constexpr int WARP_WAVES = 1;
+constexpr int WARP_FW = 64 * WARP_WAVES;
+constexpr int WARP_BAND = 4;  // tile rows per XCD band (fast kernel); measured 1: 548, 2: 424, 4: 360, 8: 327, 16: 311 MB fetched
 constexpr float PI_F = 3.14159274101257324f;  // static_cast<float>(CV_PI)
 
 struct WarpK {
@@ -427,67 +412,29 @@ STX_DEV uint32_t sample_border(const STX_GAS uint8_t* src, uint32_t stride, int 
 // bit 16 (weights scaled by 64: <= 2048, sums < 2^25); the byte is stored as it is (ds_write_b8_d16_hi).
 // Issue costs on gfx950 (tools/ubench/valu_rate2.hip, inline asm, profiles/r04_valu_issue_cycles.txt): a wave64 instruction takes ~4.5 cycles
 // of its SIMD for almost everything this kernel uses (v_perm, v_alignbyte, v_dot2, v_pk_*_u16, v_bfe, v_mad_u32_u24, v_lshl_add, v_min3,
-// v_pk_fma_f32 — 5.0 for its two elements), ~2.8 for v_fma_f32 / v_mul_f32 / v_add_u32 / v_and_b32 and 8.4 for v_rcp_f32.  Measured A/Bs of
-// round 4 (one box, interleaved):
-//   STX_WARP_MUL = 1: 3 ix = (ix << 1) + ix, (fy, fy) = fy << 16 | fy, the horizontal weight pair by shifts instead of 24-bit multiplies
-//                     — 185.4 / 186.8 us against 185.6 / 185.6: the multiplies cost what the shifts cost.  Default 0 (the round-3 code).
-//   STX_WARP_UNALIGNED = 1: the 6-byte groups as byte-exact 8-byte loads (HSA unaligned-access mode) instead of aligned 12-byte windows +
-//                     v_alignbyte: 268 us against 185 — the texture-address path splits every unaligned lane access.  Default 0.
-#ifndef STX_WARP_MUL
-#define STX_WARP_MUL 0
-#endif
-#ifndef STX_WARP_UNALIGNED
-#define STX_WARP_UNALIGNED 0
-#endif
-
-STX_DEV uint32_t lshl_add_u32(uint32_t a, uint32_t b)  // (a << 1) + b, as ONE v_lshl_add_u32 (LLVM folds (x << 1) + x back into a multiply)
-{
-    uint32_t d;
-    asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-STX_DEV uint32_t lshl16_or_u32(uint32_t a, uint32_t b)  // (a << 16) | b
-{
-    uint32_t d;
-    asm("v_lshl_or_b32 %0, %1, 16, %2" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-
-// STX_WARP_NOAND = 1 (round 5): v_alignbyte_b32 reads bits 1:0 of its shift operand only (gfx9 ISA), so the `a & 3` in front of it is a
-//                     VALU instruction per pixel that LLVM cannot drop (the builtin's operand is a plain i32): 121 -> 117 per 4 pixels.
-#ifndef STX_WARP_NOAND
-#define STX_WARP_NOAND 1
-#endif
+// v_pk_fma_f32 — 5.0 for its two elements), ~2.8 for v_fma_f32 / v_mul_f32 / v_add_u32 / v_and_b32 and 8.4 for v_rcp_f32.  Decided by
+// A/Bs on one box, interleaved:
+//   * 3 ix, (fy, fy) and the horizontal weight pair are 24-bit multiplies: building them from shifts (v_lshl_add_u32, v_lshl_or_b32)
+//     measured 185.4 / 186.8 us against 185.6 / 185.6 (round 4) — the multiplies cost what the shifts cost;
+//   * the 6-byte groups are read as aligned 12-byte windows + v_alignbyte: byte-exact 8-byte loads (HSA unaligned-access mode) measured
+//     268 us against 185 (round 4) — the texture-address path splits every unaligned lane access;
+//   * v_alignbyte_b32 reads bits 1:0 of its shift operand only (gfx9 ISA), so the offset goes in unmasked: an `a & 3` in front of it is a
+//     VALU instruction per pixel that LLVM cannot drop (the builtin's operand is a plain i32): 121 -> 117 per 4 pixels (round 5).
 // The adjacent pixel pair (ix, ix + 1) of rows iy and iy + 1, all four taps inside the source: l = first 4 bytes, h = next 4 of the 6-byte
 // BGRBGR group of either row
 STX_DEV void load_taps(const STX_GAS uint8_t* src, uint32_t stride, uint32_t ix, uint32_t iy, uint32_t& l0, uint32_t& h0, uint32_t& l1,
                        uint32_t& h1)
 {
     // row < 2^15 and stride < 2^24 (fast_ok): 24-bit multiply
-#if STX_WARP_MUL
-    const uint32_t a = __umul24(iy, stride) + lshl_add_u32(ix, ix);
-#else
     const uint32_t a = __umul24(iy, stride) + ix * 3u;
-#endif
     // the lower row through its own scalar base (src + stride: one scalar add per wavefront) and the SAME lane offset — not
     // src + (offset + stride), a vector add per pixel
-#if STX_WARP_UNALIGNED
-    typedef uint32_t u32x2_u __attribute__((ext_vector_type(2), aligned(1)));
-    const u32x2_u r0 = *reinterpret_cast<const STX_GAS u32x2_u*>(src + a);
-    const u32x2_u r1 = *reinterpret_cast<const STX_GAS u32x2_u*>((src + stride) + a);
-    l0 = r0.x; h0 = r0.y; l1 = r1.x; h1 = r1.y;
-#else
     const STX_GAS uint32_t* q0 = reinterpret_cast<const STX_GAS uint32_t*>(src + (a & ~3u));
     const STX_GAS uint32_t* q1 = reinterpret_cast<const STX_GAS uint32_t*>((src + stride) + (a & ~3u));
     const uint32_t d0 = q0[0], d1 = q0[1], d2 = q0[2], e0 = q1[0], e1 = q1[1], e2 = q1[2];
-#if STX_WARP_NOAND
-    const uint32_t sh = a;
-#else
-    const uint32_t sh = a & 3u;
-#endif
-    l0 = __builtin_amdgcn_alignbyte(d1, d0, sh); h0 = __builtin_amdgcn_alignbyte(d2, d1, sh);
-    l1 = __builtin_amdgcn_alignbyte(e1, e0, sh); h1 = __builtin_amdgcn_alignbyte(e2, e1, sh);
-#endif
+    // v_alignbyte_b32 reads bits 1:0 of a only
+    l0 = __builtin_amdgcn_alignbyte(d1, d0, a); h0 = __builtin_amdgcn_alignbyte(d2, d1, a);
+    l1 = __builtin_amdgcn_alignbyte(e1, e0, a); h1 = __builtin_amdgcn_alignbyte(e2, e1, a);
 }
 
 STX_DEV void blend_pair_to_lds(const STX_GAS uint8_t* src, uint32_t stride, uint32_t ix, uint32_t iy, uint32_t fx, uint32_t fy,
@@ -495,14 +442,8 @@ STX_DEV void blend_pair_to_lds(const STX_GAS uint8_t* src, uint32_t stride, uint
 {
     uint32_t l0, h0, l1, h1;
     load_taps(src, stride, ix, iy, l0, h0, l1, h1);
-#if STX_WARP_MUL
-    const uint32_t wy1 = lshl16_or_u32(fy, fy), wy0 = 0x200020u - wy1;  // (fy, fy), (32 - fy, 32 - fy)
-    const uint32_t g = fx << 6;
-    const uint32_t wx = lshl16_or_u32(g, 2048u - g);              // (64 (32 - fx), 64 fx)
-#else
     const uint32_t wy1 = fy * 0x10001u, wy0 = 0x200020u - wy1;  // (fy, fy), (32 - fy, 32 - fy)
     const uint32_t wx = __umul24(fx, 0x3fffc0u) + 2048u;        // (64 (32 - fx), 64 fx)
-#endif
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         // (left tap, right tap) of channel c as two u16: bytes c and c + 3 of the 6-byte BGRBGR group
@@ -643,8 +584,8 @@ __global__ __launch_bounds__(WARP_FW) __attribute__((amdgpu_waves_per_eu(8, 8)))
     // row constants are wave-uniform.  The 3-byte results go through LDS to leave as whole dwords: 768 + 256 bytes per
     // wavefront, written bytewise, read back as the 192 + 64 dwords of the wavefront's 4 rows.  Only the wavefront
     // itself reads what it wrote (LDS operations of one wavefront execute in order): no workgroup barrier.
-    __shared__ uint32_t s_px[STX_WARP_WAVES][WARP_FTH][48];  // [wavefront][row][dword]: 64 px x 3 B
-    __shared__ uint32_t s_mk[STX_WARP_WAVES][WARP_FTH][16];  // [wavefront][row][dword]: 64 px x 1 B
+    __shared__ uint32_t s_px[WARP_WAVES][WARP_FTH][48];  // [wavefront][row][dword]: 64 px x 3 B
+    __shared__ uint32_t s_mk[WARP_WAVES][WARP_FTH][16];  // [wavefront][row][dword]: 64 px x 1 B
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform, and known to be
     const int xw = tile_x * WARP_FW + wv * 64;  // first column of this wavefront
     // columns beyond the image are computed on the clamped table entry, rows beyond it on the repeated last row
@@ -660,10 +601,10 @@ __global__ __launch_bounds__(WARP_FW) __attribute__((amdgpu_waves_per_eu(8, 8)))
     // GAIN (round 6): the two gain rows of the position this lane STORES in the epilogue (row y0 + (lane >> 4), columns xw + 4 (lane & 15) ..)
     // are fetched here, behind the tables, and wait under the projector and the gathers.  Fetched in the epilogue — row table entry, then
     // the two rows it names — they were two more dependent memory round trips at the end of every wavefront: the fused gain cost +58 us
-    // on a 170 us kernel for arithmetic worth a fifth of that (STX_WARP_GAIN_EARLY=0 builds that form).
+    // on a 170 us kernel for arithmetic worth a fifth of that.  (With WARP_IT > 1 a lane stores several rows and the epilogue fetches them itself.)
     float4 g_u = make_float4(0.f, 0.f, 0.f, 0.f), g_v = g_u;
     float g_b1 = 0.f;
-    if (GAIN && WARP_IT == 1 && STX_WARP_GAIN_EARLY) {
+    if (GAIN && WARP_IT == 1) {
         const int er = lane >> 4, ec = lane & 15;
         const int2 ty = P.g_yt[min(tile_y * WARP_TH + er, dh - 1)];
         g_b1 = __int_as_float(ty.y);
@@ -907,7 +848,7 @@ __global__ __launch_bounds__(WARP_FW) __attribute__((amdgpu_waves_per_eu(8, 8)))
                 // this lane's 4 pixels: columns xw + 4 c .. + 3 of row y0 + r.  g = H[r0][x] b0 + H[r1][x] b1 as cv::resize(INTER_LINEAR) rounds it
                 float4 u, v;
                 float b1;
-                if (WARP_IT == 1 && STX_WARP_GAIN_EARLY) {  // fetched behind the tables (see there)
+                if (WARP_IT == 1) {  // fetched behind the tables (see there)
                     u = g_u; v = g_v; b1 = g_b1;
                 } else {
                     const int2 ty = P.g_yt[y0 + r];
@@ -1313,7 +1254,7 @@ int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, cons
             //              more dependent scalar load before its per-image block.
             // Measured (round 6, one box, profiles/r06_warp_split.md): config 2 (equal ROIs) 180-181 us z against 183-188 flat; a column
             // of config 3 235 z against 223 flat; config 4's 8 frames 1190 z against 1129 flat.  The flat grid is taken when the z grid
-            // would launch more than 5 % empty workgroups (STX_WARP_ZGRID=1 builds a library that never does: the A/B).
+            // would launch more than 5 % empty workgroups.
             unsigned long long wgs = 0, wg_max = 0;
             for (int i = 0; i < WARP_BATCH; i++) B.first_wg[i] = 0xffffffffu;
             for (int i = 0; i < m; i++) {
@@ -1325,7 +1266,7 @@ int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, cons
                 wg_max = std::max(wg_max, own);
             }
             if (wgs >= (1ull << 31)) return stx_fail(STX_ERR_UNSUPPORTED, "warp batch of %llu tiles exceeds the grid", wgs);
-            const bool flat = !STX_WARP_ZGRID && !dbg && (double)wgs < 0.95 * (double)(wg_max * (unsigned long long)m);
+            const bool flat = !dbg && (double)wgs < 0.95 * (double)(wg_max * (unsigned long long)m);
             const dim3 gf(flat ? (unsigned)wgs : (unsigned)wg_max, 1, flat ? 1 : m);
             // STITCHING_AMD_WARP_LDS (diagnostic): bytes of dynamic LDS requested on top of the kernel's own — an occupancy limit
             // (160 KB per CU / request = workgroups per CU) for co-residency experiments with the other panorama's kernels

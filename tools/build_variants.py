@@ -7,9 +7,9 @@ How the per-file scheduler flags of stitching_amd/csrc/Makefile were found (prof
 
 with `=` for "what the Makefile ships for this file" and an empty field for "no extra flags".  Example (spec.txt):
 
-    base  | = | = | =
-    ilp   | = | = | -mllvm -amdgpu-use-amdgpu-trackers -mllvm -amdgpu-sched-strategy=max-ilp
-    w6    | = | = | = -DSTX_L0_WAVES=6
+    base   | = | = | =
+    ilp    | = | = | -mllvm -amdgpu-use-amdgpu-trackers -mllvm -amdgpu-sched-strategy=max-ilp
+    clause | = | = | = -mllvm -amdgpu-sched-strategy=max-memory-clause
 
     python tools/build_variants.py spec.txt           # builds stitching_amd/libv_<label>.so, prints the gpurun command
     gpurun -- 'bash tools/gpu_ab_lib.sh <tag> 2 "base|stitching_amd/libv_base.so|| " ...'

@@ -27,6 +27,11 @@ int stx_debug_warp_maps(stx_ctx* ctx, int type, float scale, const float K[9], c
  * halo of its strips by it (stitching_amd/distributed.py: FEATHER_DIST_CAP); tests/test_host_logic.py ties the two together. */
 int stx_debug_feather_dist_cap(void);
 
+/* How many gather launches of the LAST blend() on this context took their images from the cover table of an adopted stx_mb_weights
+ * handle instead of searching for them (stx_blend_use_weights; levels 0 .. bands - 3 of a multi-band blender with at most 64 images
+ * whose regions are the ones the table was recorded over): 0 when the blender searched.  tests/test_gpu_cover_replay.py. */
+int stx_debug_blend_replayed(stx_ctx* ctx, int* out_launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,7 +55,7 @@ EXPORTS = (
     "stx_blend_destroy stx_blend_keep_weights stx_blend_use_weights stx_mb_weights_free stx_blend_set_band stx_blend_feed_ex stx_blend_contrib_rect stx_blend_export_contrib stx_blend_export_contribs "
     "stx_blend_build stx_blend_feed_contrib stx_blend_feed_contrib_ex stx_buf_flags stx_strip_rect stx_view_rect stx_strip_pack stx_strip_pack_batch stx_strip_pack_batch_ex stx_strip_bytes stx_strip_unpack stx_blend_feed_strips stx_comm_unique_id stx_comm_create stx_comm_exchange stx_comm_exchange_begin stx_comm_exchange_end stx_comm_exchange_begin_on stx_comm_exchange_end_on stx_comm_info stx_comm_destroy stx_prof_enable stx_prof_reset stx_prof_count stx_prof_get stx_mark stx_mark_elapsed_ms "
     "stx_exposure_feed stx_exposure_stats stx_exposure_solve stx_set_exposure_solver stx_get_exposure_solver stx_exposure_feed_ex stx_exposure_solve_device stx_lu_solve_device stx_seam_find stx_seam_schedule stx_color_seam_find stx_crop_lir stx_features_detect stx_match_features stx_ray_problem_create stx_ray_problem_eval stx_ray_problem_free "
-    "stx_debug_warp_maps stx_debug_feather_dist_cap"  # include/stitching_amd_debug.h: test hooks, never called by the package's classes
+    "stx_debug_warp_maps stx_debug_feather_dist_cap stx_debug_blend_replayed"  # include/stitching_amd_debug.h: test hooks, never called by the package's classes
 ).split()
 
 _lib = None
@@ -160,6 +160,7 @@ def lib():
     L.stx_prof_count.argtypes = [vp, ip]
     L.stx_prof_get.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                C.POINTER(C.c_double)]
+    L.stx_debug_blend_replayed.argtypes = [vp, ip]
     L.stx_debug_warp_maps.argtypes = [vp, C.c_int, C.c_float, fp, fp, C.c_int, C.c_int, C.c_int, ip, vpp, vpp, ip]
     llp, dp = C.POINTER(C.c_longlong), C.POINTER(C.c_double)
     L.stx_exposure_feed.argtypes = [vp, C.c_int, C.c_int, vpp, vpp, ip, C.c_int, C.c_int, dp, llp, dp]

@@ -1147,6 +1147,46 @@ STX_DEV bool occ_hit(const StxMbImage& im, int lv, int tile_x, int Y0)
     return occ_hit_f<L0>(im.occ[L0 ? 1 : lv], im.fx, im.fy, im.fw, im.fh, lv, tile_x, Y0);
 }
 
+// The image search of the packed gathers (mb_level0_pk_kernel, mb_level_pk_kernel): does image kk (one lane per image, kk = base + lane)
+// reach the rows Y0, Y0 + 1 of level lv under the 512 columns from tile_x on — rectangle test, then the occupancy map (level 0 reads the
+// level-1 map, see occ_hit_f).  The ballot of it over a wavefront is the set of images the wavefront walks.  It reads nothing but the
+// descriptor table and the occupancy maps, so on a known rig it is a constant of the tile: mb_cover_kernel records the ballot with THIS
+// function and the replay instantiations of the gathers read the record instead of calling it.
+// (round 6) size and corner / feed rectangle of the lane's image as ONE 16-byte load and tests without short circuits: left to `&&` the
+// compiler made three dependent loads of it, each behind its own branch — three memory round trips before a wavefront knew its images;
+// the occupancy pointer in the same batch: the occupancy test then costs one round trip, not two.
+template <bool L0, bool CONTRIB>
+STX_DEV bool mb_tile_hit(const StxMbImage* images, int n_images, int lv, int tile_x, int Y0, int kk)
+{
+    const StxMbImage& im = images[min(kk, n_images - 1)];
+    bool hit;
+    if (L0) {
+        const v4u f = *reinterpret_cast<const v4u_a4*>(&im.iw);  // iw, ih, ix, iy
+        const v4u ff = *reinterpret_cast<const v4u_a4*>(&im.fx);  // fx, fy, fw, fh
+        const uint8_t* const occp = im.occ[1];
+        const int kind = CONTRIB ? im.kind : 0;
+        int rx = (int)f.z, ry = (int)f.w, rw = (int)f.x, rh = (int)f.y;
+        if (CONTRIB && kind == 1) { rx = (int)ff.x; ry = (int)ff.y; rw = (int)ff.z; rh = (int)ff.w; }
+        hit = (kk < n_images) & (rx < tile_x + 512) & (rx + rw > tile_x) & (ry < Y0 + 2) & (ry + rh > Y0);
+        if (hit) hit = occ_hit_f<true>(occp, (int)ff.x, (int)ff.y, (int)ff.z, (int)ff.w, 0, tile_x, Y0);
+    } else {
+        const v4u f = *reinterpret_cast<const v4u_a4*>(&im.fx);  // fx, fy, fw, fh
+        const uint8_t* const occp = im.occ[lv];
+        const int rx = (int)f.x >> lv, ry = (int)f.y >> lv, rw = (int)f.z >> lv, rh = (int)f.w >> lv;
+        hit = (kk < n_images) & (rx < tile_x + 512) & (rx + rw > tile_x) & (ry < Y0 + 2) & (ry + rh > Y0);
+        if (hit) hit = occ_hit_f<false>(occp, (int)f.x, (int)f.y, (int)f.z, (int)f.w, lv, tile_x, Y0);
+    }
+    return hit;
+}
+
+// Replay of the image search (MbLevelK::cover): the recorded ballot of this wavefront's tile, as one wave-uniform (scalar) load
+typedef const unsigned long long __attribute__((address_space(4))) * StxCoverPtr;
+STX_DEV unsigned long long mb_cover_word(const MbLevelK& P, int tile_tx, int Y0)
+{
+    const int idx = __builtin_amdgcn_readfirstlane(((Y0 - P.y0) / LV_TH) * P.tiles.tiles_x + tile_tx);
+    return ((StxCoverPtr)P.cover)[idx];
+}
+
 template <bool WF>
 STX_DEV void level0_epilogue_pk(const MbLevelK& P, int X0, int Y0, uint32_t (&acc)[2][3][4], uint32_t (&cnt)[2][4], const float (*ws)[8]);
 
@@ -1761,7 +1801,9 @@ STX_DEV void level0_epilogue_pk(const MbLevelK& P, int X0, int Y0, uint32_t (&ac
 // byte is 0 / 255 iff it equals its sign bit replicated), and at the end such a lane queues its patch for the fp32-weight pass instead of
 // storing.  A resized seam mask is grey along the seams only: 1 - 2 % of the lanes (round 3 switched the WHOLE wavefront to fp32 sums at
 // its first grey byte: 40 % of the wavefronts of the default pipeline).
-template <bool CONTRIB, bool DEFER = false>
+// REPLAY (MbLevelK::cover, at most 64 images, no contribution strips): the set of images comes from the rig's cover table instead of the
+// search; the loop over it and everything behind are the same code.
+template <bool CONTRIB, bool DEFER = false, bool REPLAY = false>
 __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(L0_WAVES, 8))) void mb_level0_pk_kernel(MbLevelK P)
 {
     const int tid = threadIdx.x;
@@ -1782,23 +1824,10 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(L0_W
     uint32_t grey_seen = 0u;  // DEFER: non-zero once a mask byte under this lane was neither 0 nor 255
 
     // every wavefront finds the images under ITS two rows with one ballot (no LDS list, no barrier)
-    for (int base = 0; base < P.n_images; base += 64) {
-        bool hit = false;
-        {
-            const int kk = base + (tid & 63);
-            // (round 6) size and corner of the lane's image as ONE 16-byte load and tests without short circuits (`&&` had become three
-            // dependent loads, each behind its own branch: see mb_level_pk_kernel)
-            const StxMbImage& im = P.images[min(kk, P.n_images - 1)];
-            const v4u f = *reinterpret_cast<const v4u_a4*>(&im.iw);  // iw, ih, ix, iy
-            const v4u ff = *reinterpret_cast<const v4u_a4*>(&im.fx);  // fx, fy, fw, fh
-            const uint8_t* const occp = im.occ[1];
-            const int kind = CONTRIB ? im.kind : 0;
-            int rx = (int)f.z, ry = (int)f.w, rw = (int)f.x, rh = (int)f.y;
-            if (CONTRIB && kind == 1) { rx = (int)ff.x; ry = (int)ff.y; rw = (int)ff.z; rh = (int)ff.w; }
-            hit = (kk < P.n_images) & (rx < tile_x + 512) & (rx + rw > tile_x) & (ry < Y0 + 2) & (ry + rh > Y0);
-            if (hit) hit = occ_hit_f<true>(occp, (int)ff.x, (int)ff.y, (int)ff.z, (int)ff.w, 0, tile_x, Y0);
-        }
-        unsigned long long todo = __ballot(hit);
+    for (int base = 0; base < (REPLAY ? 1 : P.n_images); base += 64) {
+        unsigned long long todo;
+        if (REPLAY) todo = mb_cover_word(P, tile_tx, Y0);
+        else todo = __ballot(mb_tile_hit<true, CONTRIB>(P.images, P.n_images, 0, tile_x, Y0, base + (tid & 63)));
         while (todo) {
             const int k = base + (int)__builtin_ctzll(todo);
             todo &= todo - 1;
@@ -2051,6 +2080,7 @@ STX_DEV uint32_t max3u(uint32_t a, uint32_t b, uint32_t c) { return max(max(a, b
 // batched image search and the windows of the epilogue ahead, held to 4 per SIMD (128 registers, 19 spill instructions):
 // 89.5 / 146.5 / 376.6.
 constexpr int LVPK_WAVES = 3;
+template <bool REPLAY>  // the images from the rig's cover table instead of the search, as mb_level0_pk_kernel
 __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LVPK_WAVES, 8))) void mb_level_pk_kernel(MbLevelK P)
 {
     const int tid = threadIdx.x;
@@ -2073,20 +2103,10 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LVPK
     uint32_t ones = 0;     // images whose 16 weights here are all 1.f
     uint32_t mixed = 0;    // != 0: some image had a weight here that is neither covered by `ones` nor 0.f
 
-    for (int base = 0; base < P.n_images; base += 64) {
-        // (round 6) the rectangle of the lane's image as ONE 16-byte load, the tests without short circuits: left to `&&` the compiler
-        // made three dependent loads of it, each behind its own branch — three memory round trips before a wavefront knew its images
-        bool hit = false;
-        {
-            const int kk = base + (tid & 63);
-            const StxMbImage& im = P.images[min(kk, P.n_images - 1)];
-            const v4u f = *reinterpret_cast<const v4u_a4*>(&im.fx);  // fx, fy, fw, fh
-            const uint8_t* const occp = im.occ[lv];                  // (in the same batch: the occupancy test then costs one round trip, not two)
-            const int rx = (int)f.x >> lv, ry = (int)f.y >> lv, rw = (int)f.z >> lv, rh = (int)f.w >> lv;
-            hit = (kk < P.n_images) & (rx < tile_x + 512) & (rx + rw > tile_x) & (ry < Y0 + 2) & (ry + rh > Y0);
-            if (hit) hit = occ_hit_f<false>(occp, (int)f.x, (int)f.y, (int)f.z, (int)f.w, lv, tile_x, Y0);
-        }
-        unsigned long long todo = __ballot(hit);
+    for (int base = 0; base < (REPLAY ? 1 : P.n_images); base += 64) {
+        unsigned long long todo;
+        if (REPLAY) todo = mb_cover_word(P, tile_tx, Y0);
+        else todo = __ballot(mb_tile_hit<false, false>(P.images, P.n_images, lv, tile_x, Y0, base + (tid & 63)));
         while (todo) {
             const int k = base + (int)__builtin_ctzll(todo);
             todo &= todo - 1;
@@ -2296,6 +2316,24 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LVPK
     }
 }
 
+// Records the image search of the packed gathers for one level of a rig: one wavefront per gather tile (the tile and row derivation of
+// the gathers), the ballot of mb_tile_hit over the images written by lane 0 to cover[tile row * tiles_x + tile column] — indexed by the
+// tile's position, not by the workgroup that happens to run it.  n_images <= 64 (one word); level 0 is searched as the gathers search it.
+static_assert(LV_WAVES == 1, "a cover word is the search of ONE wavefront: a tile of more wavefronts needs a word per wavefront");
+__global__ __launch_bounds__(LV_THREADS) void mb_cover_kernel(const StxMbImage* images, int n_images, int level, int x0, int y0, StxTileMap tiles,
+                                                              unsigned long long* cover)
+{
+    const int tid = threadIdx.x;
+    int tile_tx, tile_ty;
+    if (!xcd_tile(tiles, blockIdx.x, tile_tx, tile_ty)) return;
+    const int tile_x = x0 + tile_tx * 512, tile_y = y0 + tile_ty * LV_TH;
+    const int Y0 = tile_y + __builtin_amdgcn_readfirstlane(tid >> 6) * 2;
+    const bool hit = level == 0 ? mb_tile_hit<true, false>(images, n_images, 0, tile_x, Y0, tid & 63)
+                                : mb_tile_hit<false, false>(images, n_images, level, tile_x, Y0, tid & 63);
+    const unsigned long long word = __ballot(hit);
+    if ((tid & 63) == 0) cover[((Y0 - y0) / LV_TH) * tiles.tiles_x + tile_tx] = word;
+}
+
 bool launched_ok() { return hipGetLastError() == hipSuccess; }
 
 }  // namespace
@@ -2381,11 +2419,17 @@ bool stx_fast_mb_level(stx_ctx* ctx, const MbLevelK& K)
     if (!fast_level_ok(K, &KT)) return false;
     dim3 grid(stx_tile_grid(KT.tiles), 1);
     hipStream_t st = ctx->stream;
+    // the rig's cover table instead of the image search (MbLevelK::cover, which emit mode reads as out_w): one word holds 64 images, and
+    // the record has no strips
+    const bool replay = !K.emit && K.cover != nullptr && K.n_images <= 64 && !K.has_contrib;
+    bool replayed = false;
     if (K.level == 0 && K.pk_ok && !K.emit && K.num_bands > 0) {
         // STITCHING_AMD_L0_LDS (diagnostic): dynamic LDS as an occupancy limit, see stx_warp.hip
         static const unsigned pad_lds = getenv("STITCHING_AMD_L0_LDS") ? (unsigned)atoi(getenv("STITCHING_AMD_L0_LDS")) : 0u;
         if (K.has_contrib) hipLaunchKernelGGL(mb_level0_pk_kernel<true>, grid, dim3(LV_THREADS), pad_lds, st, KT);
+        else if (replay) hipLaunchKernelGGL((mb_level0_pk_kernel<false, false, true>), grid, dim3(LV_THREADS), pad_lds, st, KT);
         else hipLaunchKernelGGL(mb_level0_pk_kernel<false>, grid, dim3(LV_THREADS), pad_lds, st, KT);
+        replayed = replay && !K.has_contrib;
     } else if (K.level == 0 && K.all_u8 && !K.has_contrib && !K.emit && K.num_bands > 0 && !no_defer()) {
         // u8 images whose masks are not known to be binary (resized seam masks: the reference's default pipeline): the packed kernel
         // with per-lane deferral + the fp32-weight pass over the queued patches.  The queue has room for every patch of the region; it
@@ -2402,7 +2446,9 @@ bool stx_fast_mb_level(stx_ctx* ctx, const MbLevelK& K)
         KT.defer_list = reinterpret_cast<unsigned long long*>(reinterpret_cast<uint8_t*>(q.get()) + counters);
         KT.defer_cap = (unsigned)seg_cap;
         hipMemsetAsync(q.get(), 0, counters, st);
-        hipLaunchKernelGGL((mb_level0_pk_kernel<false, true>), grid, dim3(LV_THREADS), 0, st, KT);
+        if (replay) hipLaunchKernelGGL((mb_level0_pk_kernel<false, true, true>), grid, dim3(LV_THREADS), 0, st, KT);
+        else hipLaunchKernelGGL((mb_level0_pk_kernel<false, true>), grid, dim3(LV_THREADS), 0, st, KT);
+        replayed = replay;
         {
             StxProfScope prof2(ctx, "mb_level0_deferred", 0.0);  // inside the caller's "mb_level0" bracket: that one times both launches
             hipLaunchKernelGGL(mb_level0_deferred_kernel, dim3(1024), dim3(256), 0, st, KT);
@@ -2430,9 +2476,32 @@ bool stx_fast_mb_level(stx_ctx* ctx, const MbLevelK& K)
         // (4 waves per SIMD at 121 registers; forced to 5 it spills 19 of them: 309 against 203 us on the resized-seam-mask leg)
         if (K.level == 0 && K.all_u8 && K.num_bands > 0) hipLaunchKernelGGL((mb_level_fast_kernel<true, false, false, true>), grid, dim3(LV_THREADS), 0, st, KT);
         else if (K.level == 0) hipLaunchKernelGGL((mb_level_fast_kernel<true, false, false, false>), grid, dim3(LV_THREADS), 0, st, KT);
-        else if (K.all_u8 && K.level < K.num_bands && !no_pk_levels) hipLaunchKernelGGL(mb_level_pk_kernel, grid, dim3(LV_THREADS), 0, st, KT);
+        else if (K.all_u8 && K.level < K.num_bands && !no_pk_levels) {
+            if (replay) hipLaunchKernelGGL(mb_level_pk_kernel<true>, grid, dim3(LV_THREADS), 0, st, KT);
+            else hipLaunchKernelGGL(mb_level_pk_kernel<false>, grid, dim3(LV_THREADS), 0, st, KT);
+            replayed = replay;
+        }
         else if (K.all_u8) hipLaunchKernelGGL((mb_level_fast_kernel<false, false, false, true>), grid, dim3(LV_THREADS), 0, st, KT);
         else hipLaunchKernelGGL((mb_level_fast_kernel<false, false, false, false>), grid, dim3(LV_THREADS), 0, st, KT);
     }
+    if (replayed) ctx->blend_replayed++;
+    return launched_ok();
+}
+
+// ---- the image search of a known rig, recorded (stx_mb_weights: cover) ----
+// tile dimensions of the packed gathers over a level's region: what a cover table is indexed by
+void stx_fast_mb_cover_dims(int x0, int x1, int y0, int y1, int* tiles_x, int* tiles_y, int* band_rows)
+{
+    *tiles_x = (x1 - x0 + 511) / 512; *tiles_y = (y1 - y0 + LV_TH - 1) / LV_TH; *band_rows = LV_BAND;
+}
+
+// fills cover[tiles_x * tiles_y] for `level` over [x0, x1) x [y0, y1); n <= 64
+bool stx_fast_mb_cover(stx_ctx* ctx, const StxMbImage* d_images, int n, int level, int x0, int x1, int y0, int y1, unsigned long long* cover)
+{
+    if (n < 1 || n > 64 || x1 <= x0 || y1 <= y0) return false;
+    int tx, ty, br;
+    stx_fast_mb_cover_dims(x0, x1, y0, y1, &tx, &ty, &br);
+    const StxTileMap M = stx_tile_map(tx, ty, br);
+    hipLaunchKernelGGL(mb_cover_kernel, dim3(stx_tile_grid(M), 1), dim3(LV_THREADS), 0, ctx->stream, d_images, n, level, x0, y0, M, cover);
     return launched_ok();
 }

@@ -42,7 +42,7 @@ static void blender_release(stx_blender* b)
     stx_mb_weights_release(b->keep);
     stx_mb_weights_release(b->adopted);
     b->keep = b->adopted = nullptr;
-    b->d_all = nullptr;
+    b->d_all = b->d_gather = nullptr;
     b->images.clear();
     b->built.clear();
     b->no_images.clear();
@@ -378,6 +378,22 @@ static void mb_fill_common(const stx_blender* b, MbLevelK* K, const StxMbImage* 
     K->all_u8 = 1;
 }
 
+// rows [0, y1) of level lv that blend() computes
+static int mb_level_y1(const stx_blender* b, int lv) { return lv == 0 ? b->fh : b->rh >> lv; }
+
+// the adopted handle's cover table for the level K is about to run, or null: the table answers for the region and the tile map it was
+// recorded over and for no other (a band set after adoption, another tile height)
+static const unsigned long long* mb_cover_for(const stx_mb_weights* w, const MbLevelK& K)
+{
+    if (!w || K.level < 0 || K.level > STX_MAX_BANDS || K.n_images > 64 || K.n_images != (int)w->images.size()) return nullptr;
+    const stx_mb_weights::Cover& c = w->cover[K.level];
+    int tx, ty, br;
+    stx_fast_mb_cover_dims(K.x0, K.x1, K.y0, K.y1, &tx, &ty, &br);
+    if (!c.table || c.x0 != K.x0 || c.x1 != K.x1 || c.y0 != K.y0 || c.y1 != K.y1 || c.tiles_x != tx || c.tiles_y != ty || c.band_rows != br)
+        return nullptr;
+    return c.table;
+}
+
 static int mb_finish(stx_blender* b, stx_buf* pano, stx_buf* pmask, stx_buf* pano16)
 {
     stx_ctx* ctx = b->ctx;
@@ -385,6 +401,7 @@ static int mb_finish(stx_blender* b, stx_buf* pano, stx_buf* pmask, stx_buf* pan
     STX_TRY(mb_ensure_pyramids(b));
     StxMbImage* d_images = b->d_all;
     if (!d_images) STX_TRY(mb_upload(b, b->images.data(), n, &d_images));
+    b->d_gather = d_images;
     bool all_u8 = true, has_contrib = false, pk_ok = true;
     for (const StxMbImage& im : b->images) {
         if (im.kind == 0 && im.img0_is_s16) all_u8 = false;
@@ -405,7 +422,8 @@ static int mb_finish(stx_blender* b, stx_buf* pano, stx_buf* pmask, stx_buf* pan
         K.all_u8 = all_u8 ? 1 : 0;
         K.has_contrib = has_contrib ? 1 : 0;
         K.pk_ok = pk_ok ? 1 : 0;
-        K.x0 = xb[lv]; K.x1 = xe[lv]; K.y0 = 0; K.y1 = lv == 0 ? b->fh : b->rh >> lv;
+        K.x0 = xb[lv]; K.x1 = xe[lv]; K.y0 = 0; K.y1 = mb_level_y1(b, lv);
+        if (b->adopted && !has_contrib) K.cover = mb_cover_for(b->adopted, K);
         if (lv < nb) {
             K.up = out[lv + 1]; K.up_stride = ostride[lv + 1]; K.up_plane = oplane[lv + 1];
             K.up_x0 = xb[lv + 1]; K.up_y0 = 0;
@@ -487,6 +505,24 @@ static void mb_hand_over_weights(stx_blender* b)
         w->images.push_back(k);
     }
     w->allocs.swap(b->wt_allocs);
+    // the image search of the packed gathers (levels 0 .. B - 3), recorded while this blender's descriptor table is still alive: rectangles,
+    // occupancy maps, tile positions and feed order are the rig's, and stx_blend_use_weights pins every one of them.  One word per tile
+    // holds 64 images: larger rigs keep no cover and search as ever.
+    if (b->images.size() > 64 || !b->d_gather) return;
+    int xb[STX_MAX_BANDS + 1], xe[STX_MAX_BANDS + 1];
+    mb_level_regions(b, b->band_x0, b->band_x1, xb, xe);
+    for (int lv = 0; lv <= b->num_bands - 3; lv++) {
+        stx_mb_weights::Cover c;
+        c.x0 = xb[lv]; c.x1 = xe[lv]; c.y0 = 0; c.y1 = mb_level_y1(b, lv);
+        if (c.x1 <= c.x0 || c.y1 <= c.y0) continue;
+        stx_fast_mb_cover_dims(c.x0, c.x1, c.y0, c.y1, &c.tiles_x, &c.tiles_y, &c.band_rows);
+        void* t = nullptr;
+        if (stx_dev_alloc(b->ctx, sizeof(unsigned long long) * (size_t)c.tiles_x * (size_t)c.tiles_y, &t) != STX_OK) return;
+        w->allocs.push_back(t);
+        c.table = (unsigned long long*)t;
+        if (!stx_fast_mb_cover(b->ctx, b->d_gather, (int)b->images.size(), lv, c.x0, c.x1, c.y0, c.y1, c.table)) return;
+        w->cover[lv] = c;
+    }
 }
 
 STX_EXPORT int stx_blend_keep_weights(stx_blender* b, stx_mb_weights** out)
@@ -533,6 +569,13 @@ STX_EXPORT int stx_blend_use_weights(stx_blender* b, stx_mb_weights* w, int* out
     w->refs++;
     b->adopted = w;
     *out_adopted = 1;
+    return STX_OK;
+}
+
+STX_EXPORT int stx_debug_blend_replayed(stx_ctx* ctx, int* out_launches)
+{
+    if (!ctx || !out_launches) return stx_fail(STX_ERR_INVALID, "null argument");
+    *out_launches = ctx->blend_replayed;
     return STX_OK;
 }
 
@@ -757,6 +800,7 @@ STX_EXPORT int stx_blend_finish_ex(stx_blender* b, stx_buf** out_pano_u8, stx_bu
     if (!b->ctx) return stx_fail(STX_ERR_STATE, "geometry-only blender (created without a context)");
     STX_TRY(stx_set_device(b->ctx));
     stx_ctx* ctx = b->ctx;
+    ctx->blend_replayed = 0;
     const int ow = b->kind == STX_BLEND_MULTIBAND ? b->band_x1 - b->band_x0 : b->rw, oh = b->kind == STX_BLEND_MULTIBAND ? b->fh : b->rh;
     StxBufRef p16, pmask, pano;  // (what the caller does not take is released in the order pano, pmask, p16)
     const int rc = [&]() {

@@ -38,7 +38,12 @@ struct MbLevelK {
     short* out; long long out_stride, out_plane; int out_x0, out_y0;   // planar int16 level (levels >= 1, or emit)
     const short* up; long long up_stride, up_plane; int up_x0, up_y0;  // finished level+1 (null at the coarsest)
     // emit mode (sharded blending): write the un-normalised sums (short)acc -> out, weight sum -> out_w
-    int emit; float* out_w; long long out_w_stride;
+    // (out_w shares its eight bytes with `cover`, which only launches that do not emit read: the block is 264 bytes without an 8-byte hole,
+    // and a longer one would move the implicit arguments behind it in every kernel that takes it)
+    // cover (null: search): the image search of the packed gathers, recorded for a known rig.  Word (Y0 - y0) / 2 * tiles.tiles_x + tile
+    // column is the ballot a wavefront's search would give for its rows Y0, Y0 + 1 and its 512 columns: bit k = image k of the table.
+    // Written once per rig by mb_cover_kernel into the stx_mb_weights handle; set by mb_finish only for the region and tile map it was made for.
+    int emit; union { float* out_w; const unsigned long long* cover; }; long long out_w_stride;
     // level 0 outputs, origin (pano_x0, pano_y0)
     uint8_t* pano; long long pano_stride;
     uint8_t* pmask; long long pmask_stride;
@@ -67,6 +72,10 @@ struct MbLevelK {
 // preconditions do not hold and the generic kernel must be used instead.
 bool stx_fast_mb_down_batch(stx_ctx* ctx, const StxMbImage* d_images, const StxMbImage* h_images, int n, int level, bool weights);
 bool stx_fast_mb_level(stx_ctx* ctx, const MbLevelK& K);
+// cover tables (MbLevelK::cover): the tile dimensions of the packed gathers over a region, and the launch that fills one table of
+// tiles_x * tiles_y words for at most 64 images (false: nothing was launched)
+void stx_fast_mb_cover_dims(int x0, int x1, int y0, int y1, int* tiles_x, int* tiles_y, int* band_rows);
+bool stx_fast_mb_cover(stx_ctx* ctx, const StxMbImage* d_images, int n, int level, int x0, int x1, int y0, int y1, unsigned long long* cover);
 
 // batched strip export: see stx_blend_fast.hip
 int stx_fast_mb_emit_class(const MbLevelK& K, MbLevelK* KT);

@@ -89,6 +89,8 @@ struct stx_ctx {
     hipEvent_t marks[16] = {};
     // exposure estimation: sqrt(k) for k = 0 .. 3 * 255^2 in fp64, uploaded at the first feed (an allocator block: freed with the context)
     double* exp_sqrt = nullptr;
+    // gather launches of the last blend() that took their images from a cover table (stx_debug_blend_replayed)
+    int blend_replayed = 0;
 };
 
 #define STX_STAGE_SEGS 4
@@ -424,6 +426,7 @@ struct stx_blender {
     stx_mb_weights* adopted = nullptr;  // stx_blend_use_weights: the handle whose weights the images point to (one reference held);
                                       // the pyramids are then built without their weight half
     StxMbImage* d_all = nullptr;      // device copy of `images` as the pyramid pass uploaded it, while it still equals `images` (else null)
+    StxMbImage* d_gather = nullptr;   // the device table the gathers of blend() ran on (one of pyr_allocs; mb_hand_over_weights records the cover from it)
     int band_x0 = 0, band_x1 = 0;     // columns of the final roi this blender produces (sharded blending)
     int next_order = 0;
     int pyr_mode = 0;                 // STX_PYRDOWN_* | lanes << 8, captured at stx_blend_create: one summation order per panorama
@@ -448,6 +451,11 @@ struct stx_mb_weights {
     int rx = 0, ry = 0, rw = 0, rh = 0;
     std::vector<StxMbKept> images;  // in feed order; empty until the blender it was taken from has blended
     std::vector<void*> allocs;
+    // the image search of the packed gathers, recorded once (levels 0 .. num_bands - 3, at most 64 images; table null: none): per level
+    // the region and tile dimensions the table was made for — a blender whose level differs in any of them searches as ever.
+    // 8 bytes per 512 x 2 tile (one of `allocs`)
+    struct Cover { int x0, x1, y0, y1, tiles_x, tiles_y, band_rows; unsigned long long* table; };
+    Cover cover[STX_MAX_BANDS + 1] = {};
 };
 void stx_mb_weights_release(stx_mb_weights* w);
 // MultiBandBlender::feed geometry: the feed rectangle (tl_new .. br_new) relative to the padded roi

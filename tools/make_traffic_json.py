@@ -27,6 +27,7 @@ def kernel_source_hash():
 NAMES = [("warp_fast_kernel<3, true, true", "warp_img_mask"), ("warp_fast_kernel<2, true, true", "warp_img_mask"),
          ("warp_fast_kernel<0, true, true", "warp_img_mask"),
          ("warp_fast_kernel<3, true, true, false, 0, true", "warp_img_mask_gain"),
+         ("warp_fast_kernel<3, true, false", "warp_img"),  # the image-only launch of a known rig: every timed step of the bench
          ("seam_resize4", "seam_mask_resize"), ("dilate3x3", "seam_mask_dilate"), ("mb_level0_deferred", "mb_level0_deferred"),
          ("gain_rows_kernel", "block_gain_rows"), ("mb_level0_pk_kernel", "mb_level0"),
          ("mb_down0_lds_kernel", "mb_down0"), ("mb_down_lds_kernel", "mb_down"), ("warp_tables_kernel", "warp_tables"),

@@ -139,6 +139,7 @@ typedef struct stx_ctx stx_ctx;
 typedef struct stx_buf stx_buf;
 typedef struct stx_blender stx_blender;
 typedef struct stx_mb_weights stx_mb_weights;
+typedef struct stx_warp_tables stx_warp_tables;
 
 /* ---- library / context ------------------------------------------------------------ */
 int stx_version(void);
@@ -216,6 +217,26 @@ int stx_warp_batch_rects(stx_ctx* ctx, int type, float scale, int n, const float
 int stx_warp_batch_gain(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s, const stx_buf* const* srcs,
                         const int* rects_xywh, const stx_buf* const* gain_maps_f32, const int* gain_flags, stx_buf** out_imgs,
                         stx_buf** out_masks, int* out_xywh);
+/* stx_warp_batch_rects / stx_warp_batch_gain for the panoramas of one rig: the per-column / per-row tables of the typed projectors (plane,
+ * affine, cylindrical, spherical, mercator) follow from the cameras, the rectangles, the scale and the trig mode — never from the pixels —
+ * so a handle keeps them between calls.  *tables = NULL on the first call: a handle is made and filled.  A later call with the handle
+ * compares everything the table kernel reads (projector type and family; per image the rectangle, scale, trig mode, t[0..1] and the
+ * products' factors k_rinv[1], [4], [7]) with the handle's record: equal -> no table kernel is launched and no table block allocated, the
+ * warp reads the kept tables; any difference -> the tables are rebuilt into the handle in stream order and the record updated.  The library
+ * decides, never the caller; the bytes are those of the plain calls either way.  The per-pixel projector families use no tables and
+ * leave the handle empty.  rects_xywh is required (stx_warp_batch_with_rois_kept: the ROIs of the call).  A handle belongs to the context that made it: another context's is refused with
+ * STX_ERR_INVALID.  stx_warp_tables_free gives the block back (stream-ordered: warps that read it may still be in flight). */
+int stx_warp_batch_rects_kept(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s, const stx_buf* const* srcs,
+                              const int* rects_xywh, stx_buf** out_imgs, stx_buf** out_masks, stx_warp_tables** tables);
+int stx_warp_batch_gain_kept(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s, const stx_buf* const* srcs,
+                             const int* rects_xywh, const stx_buf* const* gain_maps_f32, const int* gain_flags, stx_buf** out_imgs,
+                             stx_buf** out_masks, stx_warp_tables** tables);
+/* stx_warp_batch_with_rois that fills (or checks) a table handle on its way: the first panorama of a rig, whose ROIs become the
+ * rectangles of the later stx_warp_batch_rects_kept / _gain_kept calls */
+int stx_warp_batch_with_rois_kept(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s, const stx_buf* const* srcs,
+                                  const stx_buf* const* gain_maps_f32_or_null, const int* gain_flags_or_null, stx_buf** out_imgs,
+                                  stx_buf** out_masks, int* out_xywh, stx_warp_tables** tables);
+int stx_warp_tables_free(stx_warp_tables* t);
 /* One panorama's warps, its ROI pass included: stitching/stitcher.py:188 (warp_rois) + :119-123 in ONE call.  The ROIs are computed by this
  * call (never taken from the cache of earlier calls: a panorama pays for its own ROI pass) and returned in out_xywh; the host waits for them
  * once, inside the call, by polling stamps the ROI kernel writes into pinned memory, and launches the warps right behind — the device idles
@@ -249,7 +270,13 @@ int stx_blend_num_bands(const stx_blender* b, int* out_num_bands);
 int stx_blend_feed(stx_blender* b, const stx_buf* img, const stx_buf* mask, int tlx, int tly);
 int stx_blend_finish(stx_blender* b, stx_buf** out_pano_u8, stx_buf** out_mask_u8);
 /* as stx_blend_finish, but also hands out the int16 result that blender.blend() returns
- * before convertScaleAbs (stitching/blender.py:46); any out pointer may be NULL */
+ * before convertScaleAbs (stitching/blender.py:46); any out pointer may be NULL.
+ * THE RETURNED MASK IS READ-ONLY where weights are kept (stx_blend_keep_weights / stx_blend_use_weights below): the mask a blender marked
+ * by stx_blend_keep_weights returns is also held by its handle, and a blender that adopted the handle returns THAT SAME buffer (one more
+ * reference) instead of storing the same bytes again — the panoramas of a known rig may share one mask buffer from run to run.  Whoever
+ * writes into it changes the mask of every later panorama of the rig.  The buffer is reference-counted like every stx_buf: it stays
+ * valid after the handle, the blenders and the context's other users of it are gone, until its last stx_buf_free.  A caller that needs
+ * a mask of its own copies it.  Blenders without a handle return a buffer of their own, as ever. */
 int stx_blend_finish_ex(stx_blender* b, stx_buf** out_pano_u8, stx_buf** out_mask_u8, stx_buf** out_pano_s16);
 int stx_blend_destroy(stx_blender* b);
 /* Weight pyramids that outlive their blender: the panoramas of one rig ("video: same rig, new frames").  W_1..W_B of a fed image, their
@@ -257,7 +284,9 @@ int stx_blend_destroy(stx_blender* b);
  * same masks at the same places need not build them again.
  * stx_blend_keep_weights: on a multi-band blender, after its feeds and before stx_blend_finish.  After a finish that succeeded the handle owns the
  *   wt[1..B] allocations and the occupancy arena of every image fed (they no longer die with the blender), holds a reference to every
- *   mask buffer and records per image: mask buffer, 0/255 flag and the half-precision W_1 flag, size, corner, feed rectangle, border
+ *   mask buffer AND TO THE PANORAMA MASK this finish returns (w x h bytes of the output region: 54 MB for eight 4000 x 3000 frames, next to
+ *   the ~150 MB of weights; see stx_blend_finish_ex: read-only from here on), four small device copies of the blenders' descriptor table
+ *   (stx_blend_use_weights) and records per image: mask buffer, 0/255 flag and the half-precision W_1 flag, size, corner, feed rectangle, border
  *   offsets, and the blender's band count and pyrDown mode.  Needs: only images fed on this blender (no received strips), u8 images,
  *   the batched pyramid kernels (STX_PYRDOWN_SCALAR), occupancy recording on, >= 1 band, weights of its own (not adopted ones).  Where
  *   that does not hold *out is NULL, the call returns STX_OK and the blender builds as ever.  A handle whose blender never finished
@@ -266,6 +295,11 @@ int stx_blend_destroy(stx_blender* b);
  *   record field for field (same order, same mask buffer, same geometry, bands, mode), the blender has taken the handle's weight and
  *   occupancy pointers in place of its own allocations and builds its pyramids without their weight half (no mask read, no weight
  *   read / sum / write, no occupancy note: the "mb_down0" / "mb_down" profiler entries carry the bytes of what then moves).
+ *   Such a blender also (i) finds its descriptor table (per image: geometry and buffer addresses) among the handle's four resident device
+ *   copies when the same addresses come round again — the context's allocator hands out the lowest free block of a size, so they do — and
+ *   then uploads nothing, else overwrites the least recently used copy in stream order; (ii) returns the handle's panorama mask from
+ *   stx_blend_finish[_ex] and stores none, when its output region is the one the mask was recorded over (no stx_blend_set_band in
+ *   between) and its level-0 launch replays the recorded image search; otherwise it stores a mask of its own as ever.
  *   *out_adopted = 0: nothing was adopted — all images or none — and everything is built as ever.  The masks must hold what they held
  *   at the keep: the caller owns that promise.  Handle and blender live on ONE context, whose stream order makes the weights ready
  *   before their first reuse; a blender of another context is refused with STX_ERR_INVALID.

@@ -32,6 +32,19 @@ int stx_debug_feather_dist_cap(void);
  * whose regions are the ones the table was recorded over): 0 when the blender searched.  tests/test_gpu_cover_replay.py. */
 int stx_debug_blend_replayed(stx_ctx* ctx, int* out_launches);
 
+/* How many table kernels (warp_tables_kernel: one per launch batch of the typed projectors) the LAST batched warp call on this context
+ * launched: 0 when every batch read the kept tables of a stx_warp_tables handle.  tests/test_gpu_warp_tables_kept.py. */
+int stx_debug_warp_table_launches(stx_ctx* ctx, int* out_launches);
+
+/* How many descriptor tables (StxMbImage arrays) the LAST blend() on this context copied to the device: 0 when an adopted blender found
+ * its table, byte for byte, among the resident copies of its stx_mb_weights handle.  tests/test_gpu_blend_resident.py. */
+int stx_debug_blend_uploads(stx_ctx* ctx, int* out_uploads);
+
+/* 1 when the level-0 launch of the LAST multi-band blend() on this context stored the panorama mask, 0 when it did not: an adopted
+ * blender over the output region its stx_mb_weights handle recorded the mask for hands out the handle's mask instead (also 0 after a
+ * blend() of another kind).  tests/test_gpu_blend_resident.py. */
+int stx_debug_blend_mask_stored(stx_ctx* ctx, int* out_stored);
+
 #ifdef __cplusplus
 }
 #endif

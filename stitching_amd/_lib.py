@@ -50,12 +50,12 @@ STRIP_MASK_BITS = 2
 EXPORTS = (
     "stx_version stx_last_error stx_set_trig_mode stx_get_trig_mode stx_set_remap_mode stx_get_remap_mode stx_set_pyrdown_mode stx_get_pyrdown_mode stx_device_count stx_ctx_create stx_ctx_destroy stx_ctx_sync "
     "stx_host_alloc stx_host_free stx_buf_from_host stx_buf_from_host_async stx_buf_alloc stx_buf_to_host stx_buf_to_host_async stx_buf_view stx_buf_info stx_buf_device_ptr stx_buf_free "
-    "stx_warp_roi stx_warp_rois stx_warp stx_warp_image_and_mask stx_warp_batch stx_warp_batch_rects stx_warp_batch_gain stx_warp_batch_with_rois stx_warp_mask "
+    "stx_warp_roi stx_warp_rois stx_warp stx_warp_image_and_mask stx_warp_batch stx_warp_batch_rects stx_warp_batch_gain stx_warp_batch_rects_kept stx_warp_batch_gain_kept stx_warp_tables_free stx_warp_batch_with_rois stx_warp_batch_with_rois_kept stx_warp_mask "
     "stx_gain_apply stx_block_gain_apply stx_block_gain_apply_batch stx_resize_linear_exact stx_resize_linear_exact_batch stx_seam_mask_resize stx_seam_mask_resize_batch stx_seam_mask_resize_batch_sub stx_timelapse_frame stx_result_roi stx_blend_create stx_blend_num_bands stx_blend_feed stx_blend_finish stx_blend_finish_ex "
     "stx_blend_destroy stx_blend_keep_weights stx_blend_use_weights stx_mb_weights_free stx_blend_set_band stx_blend_feed_ex stx_blend_contrib_rect stx_blend_export_contrib stx_blend_export_contribs "
     "stx_blend_build stx_blend_feed_contrib stx_blend_feed_contrib_ex stx_buf_flags stx_strip_rect stx_view_rect stx_strip_pack stx_strip_pack_batch stx_strip_pack_batch_ex stx_strip_bytes stx_strip_unpack stx_blend_feed_strips stx_comm_unique_id stx_comm_create stx_comm_exchange stx_comm_exchange_begin stx_comm_exchange_end stx_comm_exchange_begin_on stx_comm_exchange_end_on stx_comm_info stx_comm_destroy stx_prof_enable stx_prof_reset stx_prof_count stx_prof_get stx_mark stx_mark_elapsed_ms "
     "stx_exposure_feed stx_exposure_stats stx_exposure_solve stx_set_exposure_solver stx_get_exposure_solver stx_exposure_feed_ex stx_exposure_solve_device stx_lu_solve_device stx_seam_find stx_seam_schedule stx_color_seam_find stx_crop_lir stx_features_detect stx_match_features stx_ray_problem_create stx_ray_problem_eval stx_ray_problem_free "
-    "stx_debug_warp_maps stx_debug_feather_dist_cap stx_debug_blend_replayed"  # include/stitching_amd_debug.h: test hooks, never called by the package's classes
+    "stx_debug_warp_maps stx_debug_feather_dist_cap stx_debug_blend_replayed stx_debug_warp_table_launches stx_debug_blend_uploads stx_debug_blend_mask_stored"  # include/stitching_amd_debug.h: test hooks, never called by the package's classes
 ).split()
 
 _lib = None
@@ -107,6 +107,10 @@ def lib():
     L.stx_warp_batch.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, fp, vpp, vpp, vpp, ip]
     L.stx_warp_batch_rects.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, fp, vpp, ip, vpp, vpp]
     L.stx_warp_batch_gain.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, fp, vpp, ip, vpp, ip, vpp, vpp, ip]
+    L.stx_warp_batch_rects_kept.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, fp, vpp, ip, vpp, vpp, vpp]
+    L.stx_warp_batch_gain_kept.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, fp, vpp, ip, vpp, ip, vpp, vpp, vpp]
+    L.stx_warp_tables_free.argtypes = [vp]
+    L.stx_warp_batch_with_rois_kept.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, fp, vpp, vpp, ip, vpp, vpp, ip, vpp]
     L.stx_warp_batch_with_rois.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, fp, vpp, vpp, ip, vpp, vpp, ip]
     L.stx_warp_mask.argtypes = [vp, C.c_int, C.c_float, fp, fp, C.c_int, C.c_int, vpp, ip]
     L.stx_gain_apply.argtypes = [vp, vp, fp]
@@ -161,6 +165,9 @@ def lib():
     L.stx_prof_get.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                C.POINTER(C.c_double)]
     L.stx_debug_blend_replayed.argtypes = [vp, ip]
+    L.stx_debug_warp_table_launches.argtypes = [vp, ip]
+    L.stx_debug_blend_uploads.argtypes = [vp, ip]
+    L.stx_debug_blend_mask_stored.argtypes = [vp, ip]
     L.stx_debug_warp_maps.argtypes = [vp, C.c_int, C.c_float, fp, fp, C.c_int, C.c_int, C.c_int, ip, vpp, vpp, ip]
     llp, dp = C.POINTER(C.c_longlong), C.POINTER(C.c_double)
     L.stx_exposure_feed.argtypes = [vp, C.c_int, C.c_int, vpp, vpp, ip, C.c_int, C.c_int, dp, llp, dp]

@@ -848,6 +848,8 @@ int stx_launch_mb_level(stx_ctx* ctx, const MbLevelK& K, double algo_bytes)
     if (K.x1 <= K.x0 || K.y1 <= K.y0) return STX_OK;
     StxProfScope prof(ctx, K.emit ? "mb_contrib" : (K.level == 0 ? "mb_level0" : "mb_level"), algo_bytes);
     if ((K.level > 0 || K.all_u8) && stx_fast_mb_level(ctx, K)) return STX_OK;
+    // (a level-0 block without a mask buffer is for the replaying gathers alone: stx_fast_mb_level0_skips_mask)
+    if (K.level == 0 && !K.emit && !K.pmask) return stx_fail(STX_ERR_HIP, "multi-band level 0: the replaying gather could not be launched");
     const dim3 grid = grid64x4(K.x1 - K.x0, K.y1 - K.y0);
     if (K.level == 0) hipLaunchKernelGGL(mb_level_kernel<true>, grid, dim3(256), 0, ctx->stream, K);
     else hipLaunchKernelGGL(mb_level_kernel<false>, grid, dim3(256), 0, ctx->stream, K);

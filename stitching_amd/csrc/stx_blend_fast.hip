@@ -1024,7 +1024,8 @@ STX_DEV void up_patch(const T* __restrict__ plane, long long stride, int cw, int
 
 // normalizeUsingWeightMap, + pyrUp(finished coarser level) saturating, store (level >= 1: planar int16;
 // level 0: u8 panorama via convertScaleAbs, mask = weight > eps, optional int16 result)
-template <bool L0>
+// MASK_OPT: P.pmask may be null — the panorama mask of a known rig is kept with its weights (stx_mb_weights: pmask) and not stored again
+template <bool L0, bool MASK_OPT = false>
 STX_DEV void level_epilogue(const MbLevelK& P, int X0, int Y0, int (&acc)[2][8][3], float (&ws)[2][8])
 {
     // normalizeUsingWeightMap, then + pyrUp(finished coarser level), saturating
@@ -1088,7 +1089,7 @@ STX_DEV void level_epilogue(const MbLevelK& P, int X0, int Y0, int (&acc)[2][8][
             *reinterpret_cast<uint2*>(po) = make_uint2(ob[0], ob[1]);
             *reinterpret_cast<uint2*>(po + 2) = make_uint2(ob[2], ob[3]);
             *reinterpret_cast<uint2*>(po + 4) = make_uint2(ob[4], ob[5]);
-            *reinterpret_cast<uint2*>(P.pmask + (long long)oy * P.pmask_stride + ox) = make_uint2(om[0], om[1]);
+            if (!MASK_OPT || P.pmask) *reinterpret_cast<uint2*>(P.pmask + (long long)oy * P.pmask_stride + ox) = make_uint2(om[0], om[1]);
             if (P.pano16) {
                 uint32_t* p16 = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(P.pano16) + (long long)oy * P.pano16_stride +
                                                             (long long)ox * 6);
@@ -1187,7 +1188,7 @@ STX_DEV unsigned long long mb_cover_word(const MbLevelK& P, int tile_tx, int Y0)
     return ((StxCoverPtr)P.cover)[idx];
 }
 
-template <bool WF>
+template <bool WF, bool MASK_OPT = false>
 STX_DEV void level0_epilogue_pk(const MbLevelK& P, int X0, int Y0, uint32_t (&acc)[2][3][4], uint32_t (&cnt)[2][4], const float (*ws)[8]);
 
 // CONTRIB: the image table may hold received contribution strips (kind 1); EMIT: write un-normalised sums.
@@ -1639,7 +1640,8 @@ STX_DEV uint32_t bgr_dword(const uint32_t (&U)[3][4])
 
 // WF: the weight sums are fp32 values `ws` (grey masks somewhere under the wavefront): every pixel takes the division, and `cnt` holds
 // 1 / 0 per pixel for "weight sum > WEIGHT_EPS" (only the final mask and the zeroing look at it)
-template <bool WF>
+// MASK_OPT: as level_epilogue's (the REPLAY instantiations of mb_level0_pk_kernel)
+template <bool WF, bool MASK_OPT>
 STX_DEV void level0_epilogue_pk(const MbLevelK& P, int X0, int Y0, uint32_t (&acc)[2][3][4], uint32_t (&cnt)[2][4], const float (*ws)[8])
 {
     // The constants (1, 1) and (-1, -1) as values the compiler cannot see through: against literal constants LLVM rewrites
@@ -1773,8 +1775,9 @@ STX_DEV void level0_epilogue_pk(const MbLevelK& P, int X0, int Y0, uint32_t (&ac
         *reinterpret_cast<uint2*>(po + 2) = make_uint2(bgr_dword<2>(U), bgr_dword<3>(U));
         *reinterpret_cast<uint2*>(po + 4) = make_uint2(bgr_dword<4>(U), bgr_dword<5>(U));
         // mask bytes of pixels 0..3 = keep[0].lo, keep[2].lo, keep[0].hi, keep[2].hi; 4..7 likewise from keep[1], keep[3]
-        *reinterpret_cast<uint2*>(P.pmask + (long long)oy * P.pmask_stride + ox) =
-            make_uint2(__builtin_amdgcn_perm(keep[2], keep[0], 0x06020400u), __builtin_amdgcn_perm(keep[3], keep[1], 0x06020400u));
+        if (!MASK_OPT || P.pmask)
+            *reinterpret_cast<uint2*>(P.pmask + (long long)oy * P.pmask_stride + ox) =
+                make_uint2(__builtin_amdgcn_perm(keep[2], keep[0], 0x06020400u), __builtin_amdgcn_perm(keep[3], keep[1], 0x06020400u));
         if (P.pano16) {
             uint32_t* p16 = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(P.pano16) + (long long)oy * P.pano16_stride + (long long)ox * 6);
             int w[8][3];
@@ -1963,7 +1966,7 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(L0_W
         cnt[r][2] = pair_u8<1, 3>(cntb[r]);
         cnt[r][3] = pair_u8<5, 7>(cntb[r]);
     }
-    level0_epilogue_pk<false>(P, X0, Y0, acc, cnt, nullptr);
+    level0_epilogue_pk<false, REPLAY>(P, X0, Y0, acc, cnt, nullptr);
 }
 
 
@@ -2050,7 +2053,7 @@ __global__ __launch_bounds__(256) void mb_level0_deferred_kernel(MbLevelK P)
                         ws[r][j] = fadd(ws[r][j], w);
                     }
             }
-            if (live) level_epilogue<true>(P, X0, Y0, acc, ws);
+            if (live) level_epilogue<true, true>(P, X0, Y0, acc, ws);
         }
         g0 += nb;
     }
@@ -2413,24 +2416,46 @@ static bool no_defer()
     return off;
 }
 
+// The two decisions of stx_fast_mb_level that stx_fast_mb_level0_skips_mask has to know as well, each made in ONE place:
+// the rig's cover table instead of the image search (MbLevelK::cover, which emit mode reads as out_w): one word holds 64 images, and the
+// record has no strips
+static bool mb_replays(const MbLevelK& K) { return !K.emit && K.cover != nullptr && K.n_images <= 64 && !K.has_contrib; }
+// which launch a level-0 block takes — L0_PK: mb_level0_pk_kernel (every mask 0 / 255); L0_DEFER: the same with per-lane deferral and
+// mb_level0_deferred_kernel behind it (u8 images whose masks may be grey); L0_OTHER: neither (emit, strips, int16 images, other levels)
+enum MbL0Path { L0_OTHER, L0_PK, L0_DEFER };
+static MbL0Path mb_level0_path(const MbLevelK& K)
+{
+    if (K.level != 0 || K.emit || K.num_bands <= 0) return L0_OTHER;
+    if (K.pk_ok) return L0_PK;
+    return K.all_u8 && !K.has_contrib && !no_defer() ? L0_DEFER : L0_OTHER;
+}
+
+// a level-0 launch of K runs REPLAY instantiations of mb_level0_pk_kernel (and, deferring, mb_level0_deferred_kernel): the only gathers
+// that pass over a null K.pmask.  (all_u8: what stx_launch_mb_level asks of a level-0 block before it comes here at all)
+bool stx_fast_mb_level0_skips_mask(const MbLevelK& K)
+{
+    MbLevelK KT;
+    return K.all_u8 && fast_level_ok(K, &KT) && mb_replays(K) && mb_level0_path(K) != L0_OTHER;
+}
+
 bool stx_fast_mb_level(stx_ctx* ctx, const MbLevelK& K)
 {
     MbLevelK KT;
     if (!fast_level_ok(K, &KT)) return false;
+    if (K.level == 0 && !K.emit && !K.pmask && !stx_fast_mb_level0_skips_mask(K)) return false;  // (stx_launch_mb_level refuses it)
     dim3 grid(stx_tile_grid(KT.tiles), 1);
     hipStream_t st = ctx->stream;
-    // the rig's cover table instead of the image search (MbLevelK::cover, which emit mode reads as out_w): one word holds 64 images, and
-    // the record has no strips
-    const bool replay = !K.emit && K.cover != nullptr && K.n_images <= 64 && !K.has_contrib;
+    const bool replay = mb_replays(K);
+    const MbL0Path l0 = mb_level0_path(K);
     bool replayed = false;
-    if (K.level == 0 && K.pk_ok && !K.emit && K.num_bands > 0) {
+    if (l0 == L0_PK) {
         // STITCHING_AMD_L0_LDS (diagnostic): dynamic LDS as an occupancy limit, see stx_warp.hip
         static const unsigned pad_lds = getenv("STITCHING_AMD_L0_LDS") ? (unsigned)atoi(getenv("STITCHING_AMD_L0_LDS")) : 0u;
         if (K.has_contrib) hipLaunchKernelGGL(mb_level0_pk_kernel<true>, grid, dim3(LV_THREADS), pad_lds, st, KT);
         else if (replay) hipLaunchKernelGGL((mb_level0_pk_kernel<false, false, true>), grid, dim3(LV_THREADS), pad_lds, st, KT);
         else hipLaunchKernelGGL(mb_level0_pk_kernel<false>, grid, dim3(LV_THREADS), pad_lds, st, KT);
         replayed = replay && !K.has_contrib;
-    } else if (K.level == 0 && K.all_u8 && !K.has_contrib && !K.emit && K.num_bands > 0 && !no_defer()) {
+    } else if (l0 == L0_DEFER) {
         // u8 images whose masks are not known to be binary (resized seam masks: the reference's default pipeline): the packed kernel
         // with per-lane deferral + the fp32-weight pass over the queued patches.  The queue has room for every patch of the region; it
         // and its counter come from the stream-ordered allocator and go back to it right behind the second launch.

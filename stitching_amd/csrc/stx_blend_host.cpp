@@ -199,15 +199,16 @@ static int mb_feed(stx_blender* b, const stx_buf* img, const stx_buf* mask, int 
         const int lw = im.fw >> i, lh = im.fh >> i;
         // rows of 64 bytes either way
         const long long gs = (long long)align_up((size_t)lw, im.g_u8 ? 64 : 32), ws = (long long)align_up((size_t)lw, 16);
-        void *g = nullptr, *wt = nullptr;
+        void* g = nullptr;
         // MB_FRONT_PAD in front, 64 bytes behind: the pyrUp tap windows of the gather kernels start up to 4 bytes in front of a row
         // and end up to 8 bytes behind its last sample (up_row_window / up_row_window_u8)
         STX_TRY(stx_dev_alloc(ctx, MB_FRONT_PAD + (size_t)gs * lh * 3 * (im.g_u8 ? 1 : sizeof(short)) + 64, &g));
         b->pyr_allocs.push_back(g);
-        STX_TRY(stx_dev_alloc(ctx, (size_t)ws * lh * ((i == 1 && im.w1_f16) ? sizeof(uint16_t) : sizeof(float)), &wt));
-        b->wt_allocs.push_back(wt);
         im.g[i] = (short*)((uint8_t*)g + MB_FRONT_PAD); im.g_stride[i] = gs; im.g_plane[i] = gs * lh;
-        im.wt[i] = (float*)wt; im.wt_stride[i] = ws;
+        // the weights' blocks are taken where the pyramids are built (mb_ensure_pyramids): a blender that adopts a handle's weights
+        // before that (stx_blend_use_weights) never takes any — and leaves the allocator's free blocks to the next panorama of the rig as
+        // it found them, which keeps the addresses in its descriptor table the same from panorama to panorama
+        im.wt[i] = nullptr; im.wt_stride[i] = ws;
     }
     // deferred: the pyramids of all images are built together (one launch per level), at the first
     // export / blend() that needs them
@@ -227,12 +228,58 @@ static int mb_upload(stx_blender* b, const StxMbImage* h, int n, StxMbImage** d_
     STX_TRY(stx_dev_alloc(ctx, sizeof(StxMbImage) * std::max(n, 1), &d));
     b->pyr_allocs.push_back(d);
     if (n > 0) STX_TRY(stx_stage_upload(ctx, d, h, sizeof(StxMbImage) * (size_t)n));
+    ctx->blend_uploads++;
     *d_out = (StxMbImage*)d;
+    return STX_OK;
+}
+
+// The descriptor table of a blender that adopted `w`, all n = w->images.size() of its images: the resident copy that equals it byte for
+// byte, or the least recently used slot after an upload into it.  Stream order keeps the gathers of earlier blends, which may still read
+// the slot, in front of the copy; the handle outlives the launches (the blender holds a reference until it is released behind them, and
+// the handle's blocks go back to the allocator in stream order).
+static int mb_resident_table(stx_blender* b, stx_mb_weights* w, const StxMbImage* h, int n, StxMbImage** d_out)
+{
+    stx_ctx* ctx = b->ctx;
+    const size_t bytes = sizeof(StxMbImage) * (size_t)n;
+    stx_mb_weights::Resident* lru = &w->resident[0];
+    for (stx_mb_weights::Resident& r : w->resident) {
+        if (r.d && r.shadow.size() == (size_t)n && memcmp(r.shadow.data(), h, bytes) == 0) {
+            r.used = ++w->resident_clock;
+            *d_out = r.d;
+            return STX_OK;
+        }
+        if (r.used < lru->used) lru = &r;
+    }
+    if (!lru->d) {
+        void* d = nullptr;
+        STX_TRY(stx_dev_alloc(ctx, bytes, &d));
+        w->allocs.push_back(d);
+        lru->d = (StxMbImage*)d;
+    }
+    lru->shadow.clear();  // no shadow answers for a slot whose upload failed
+    STX_TRY(stx_stage_upload(ctx, lru->d, h, bytes));
+    ctx->blend_uploads++;
+    lru->shadow.assign(h, h + n);
+    lru->used = ++w->resident_clock;
+    *d_out = lru->d;
     return STX_OK;
 }
 
 static int mb_ensure_pyramids(stx_blender* b)
 {
+    // weight blocks of the images about to be built, unless they came with an adopted handle (mb_feed left them open)
+    for (size_t i = 0; i < b->images.size(); i++) {
+        StxMbImage& im = b->images[i];
+        if (im.kind != 0 || b->built[i]) continue;
+        for (int l = 1; l <= b->num_bands; l++) {
+            if (im.wt[l]) continue;
+            void* wt = nullptr;
+            STX_TRY(stx_dev_alloc(b->ctx, (size_t)im.wt_stride[l] * (im.fh >> l) * ((l == 1 && im.w1_f16) ? sizeof(uint16_t) : sizeof(float)), &wt));
+            b->wt_allocs.push_back(wt);
+            im.wt[l] = (float*)wt;
+            b->d_all = nullptr;
+        }
+    }
     std::vector<StxMbImage> todo;
     for (size_t i = 0; i < b->images.size(); i++)
         if (b->images[i].kind == 0 && !b->built[i]) todo.push_back(b->images[i]);
@@ -268,7 +315,10 @@ static int mb_ensure_pyramids(stx_blender* b)
         }
     }
     StxMbImage* d = nullptr;
-    STX_TRY(mb_upload(b, todo.data(), (int)todo.size(), &d));
+    // an adopted blender (todo is then every image, as many as the handle recorded): the handle's resident copies; all others upload
+    b->d_all_resident = b->adopted && todo.size() == b->images.size() && todo.size() == b->adopted->images.size();
+    if (b->d_all_resident) STX_TRY(mb_resident_table(b, b->adopted, todo.data(), (int)todo.size(), &d));
+    else STX_TRY(mb_upload(b, todo.data(), (int)todo.size(), &d));
     // every image of the blender in this pass (the usual case): blend() reads the very same table — one upload, one copy dispatch fewer
     // between the pyramids and the collapse
     b->d_all = todo.size() == b->images.size() && memcmp(todo.data(), b->images.data(), sizeof(StxMbImage) * todo.size()) == 0 ? d : nullptr;
@@ -394,12 +444,16 @@ static const unsigned long long* mb_cover_for(const stx_mb_weights* w, const MbL
     return c.table;
 }
 
-static int mb_finish(stx_blender* b, stx_buf* pano, stx_buf* pmask, stx_buf* pano16)
+// *pmask: the panorama mask — a new buffer the level-0 launch stores, or, for a blender that adopted a handle over the output region the
+// handle's mask was recorded for, that very buffer (one more reference): the launch then stores no mask
+static int mb_finish(stx_blender* b, stx_buf* pano, StxBufRef* pmask, stx_buf* pano16)
 {
     stx_ctx* ctx = b->ctx;
     const int nb = b->num_bands, n = (int)b->images.size();
     STX_TRY(mb_ensure_pyramids(b));
     StxMbImage* d_images = b->d_all;
+    // a resident copy found by an earlier stx_blend_build may have been evicted by other adopters since: looked up again (a hit is a memcmp)
+    if (d_images && b->d_all_resident) STX_TRY(mb_resident_table(b, b->adopted, b->images.data(), n, &d_images));
     if (!d_images) STX_TRY(mb_upload(b, b->images.data(), n, &d_images));
     b->d_gather = d_images;
     bool all_u8 = true, has_contrib = false, pk_ok = true;
@@ -430,9 +484,21 @@ static int mb_finish(stx_blender* b, stx_buf* pano, stx_buf* pmask, stx_buf* pan
         }
         if (lv == 0) {
             K.pano = pano->ptr; K.pano_stride = (long long)pano->stride;
-            K.pmask = pmask->ptr; K.pmask_stride = (long long)pmask->stride;
             if (pano16) { K.pano16 = (short*)pano16->ptr; K.pano16_stride = (long long)pano16->stride; }
             K.pano_x0 = b->band_x0; K.pano_y0 = 0;
+            // the panorama mask of a known rig: kept with the weights, for the output region it was made over and no other (the cover
+            // table's test, which K.cover has passed); only the REPLAY instantiations pass over a null — the launcher says whether K takes them
+            const stx_mb_weights* w = b->adopted;
+            K.pmask = nullptr;
+            if (w && w->pmask && K.cover && w->pmask_x0 == b->band_x0 && w->pmask_x1 == b->band_x1 && w->pmask_h == b->fh &&
+                w->pmask->w == pano->w && w->pmask->h == pano->h && stx_fast_mb_level0_skips_mask(K)) {
+                stx_buf_retain(w->pmask);
+                pmask->reset(w->pmask);
+            } else {
+                STX_TRY(stx_buf_new(ctx, pano->w, pano->h, 1, STX_U8, pmask));
+                K.pmask = (*pmask)->ptr; K.pmask_stride = (long long)(*pmask)->stride;
+            }
+            ctx->blend_mask_stored = K.pmask ? 1 : 0;
         } else {
             const int w = xe[lv] - xb[lv], ph = b->rh >> lv;
             const long long st = (long long)align_up((size_t)std::max(w, 1), 32);
@@ -463,6 +529,7 @@ void stx_mb_weights_release(stx_mb_weights* w)
     if (!w || --w->refs > 0) return;
     if (w->ctx) hipSetDevice(w->ctx->device);
     for (StxMbKept& k : w->images) stx_buf_release(k.mask);
+    if (w->pmask) stx_buf_release(w->pmask);  // (whoever was handed the mask holds a reference of their own)
     for (void* p : w->allocs) stx_dev_free(w->ctx, p);  // stream-ordered, as blender_release
     delete w;
 }
@@ -480,7 +547,7 @@ static bool mb_weights_eligible(const stx_blender* b, bool built)
 }
 
 // blend() succeeded: the weights and occupancy maps of a blender marked by stx_blend_keep_weights move to its handle
-static void mb_hand_over_weights(stx_blender* b)
+static void mb_hand_over_weights(stx_blender* b, stx_buf* pmask)
 {
     stx_mb_weights* w = b->keep;
     if (!w || b->images.empty() || !mb_weights_eligible(b, true)) return;
@@ -505,6 +572,18 @@ static void mb_hand_over_weights(stx_blender* b)
         w->images.push_back(k);
     }
     w->allocs.swap(b->wt_allocs);
+    // the resident descriptor tables' device blocks, all of them now: an adopter that took one from the allocator between its feeds and its
+    // launches would leave the next adopter another set of free blocks, and with it other addresses in the very table the slot is to match
+    for (stx_mb_weights::Resident& r : w->resident) {
+        void* d = nullptr;
+        if (stx_dev_alloc(b->ctx, sizeof(StxMbImage) * b->images.size(), &d) != STX_OK) break;
+        w->allocs.push_back(d);
+        r.d = (StxMbImage*)d;
+    }
+    // the finished panorama mask over this blender's output region: what every later blend of the rig over that region would store again
+    stx_buf_retain(pmask);
+    w->pmask = pmask;
+    w->pmask_x0 = b->band_x0; w->pmask_x1 = b->band_x1; w->pmask_h = b->fh;
     // the image search of the packed gathers (levels 0 .. B - 3), recorded while this blender's descriptor table is still alive: rectangles,
     // occupancy maps, tile positions and feed order are the rig's, and stx_blend_use_weights pins every one of them.  One word per tile
     // holds 64 images: larger rigs keep no cover and search as ever.
@@ -563,9 +642,7 @@ STX_EXPORT int stx_blend_use_weights(stx_blender* b, stx_mb_weights* w, int* out
     STX_TRY(stx_set_device(b->ctx));
     for (size_t i = 0; i < b->images.size(); i++)
         for (int l = 1; l <= b->num_bands; l++) { b->images[i].wt[l] = w->images[i].wt[l]; b->images[i].occ[l] = w->images[i].occ[l]; }
-    for (void* p : b->wt_allocs) stx_dev_free(b->ctx, p);  // the blender's own, untouched
-    b->wt_allocs.clear();
-    b->d_all = nullptr;
+    b->d_all = nullptr;  // (the blender has no weight blocks of its own yet: mb_ensure_pyramids takes them)
     w->refs++;
     b->adopted = w;
     *out_adopted = 1;
@@ -576,6 +653,20 @@ STX_EXPORT int stx_debug_blend_replayed(stx_ctx* ctx, int* out_launches)
 {
     if (!ctx || !out_launches) return stx_fail(STX_ERR_INVALID, "null argument");
     *out_launches = ctx->blend_replayed;
+    return STX_OK;
+}
+
+STX_EXPORT int stx_debug_blend_mask_stored(stx_ctx* ctx, int* out_stored)
+{
+    if (!ctx || !out_stored) return stx_fail(STX_ERR_INVALID, "null argument");
+    *out_stored = ctx->blend_mask_stored;
+    return STX_OK;
+}
+
+STX_EXPORT int stx_debug_blend_uploads(stx_ctx* ctx, int* out_uploads)
+{
+    if (!ctx || !out_uploads) return stx_fail(STX_ERR_INVALID, "null argument");
+    *out_uploads = ctx->blend_uploads;
     return STX_OK;
 }
 
@@ -649,6 +740,11 @@ STX_EXPORT int stx_blend_export_contribs(stx_blender* b, int n, const int* order
         srcs[i] = *src;
     }
     STX_TRY(mb_ensure_pyramids(b));
+    // (the copies above were taken before the pyramids' weight blocks were: mb_ensure_pyramids takes them at the first build)
+    for (int i = 0; i < n; i++)
+        for (const StxMbImage& im : b->images)
+            if (im.kind == 0 && im.order == orders[i])
+                for (int l = 1; l <= nb; l++) srcs[i].wt[l] = im.wt[l];
     std::vector<StxBufRef> packed(n);
     std::vector<ContribLayout> Ls(n);
     for (int i = 0; i < n; i++) {
@@ -801,17 +897,19 @@ STX_EXPORT int stx_blend_finish_ex(stx_blender* b, stx_buf** out_pano_u8, stx_bu
     STX_TRY(stx_set_device(b->ctx));
     stx_ctx* ctx = b->ctx;
     ctx->blend_replayed = 0;
+    ctx->blend_uploads = 0;
+    ctx->blend_mask_stored = 0;
     const int ow = b->kind == STX_BLEND_MULTIBAND ? b->band_x1 - b->band_x0 : b->rw, oh = b->kind == STX_BLEND_MULTIBAND ? b->fh : b->rh;
     StxBufRef p16, pmask, pano;  // (what the caller does not take is released in the order pano, pmask, p16)
     const int rc = [&]() {
         STX_TRY(stx_buf_new(ctx, ow, oh, 3, STX_U8, &pano));
-        STX_TRY(stx_buf_new(ctx, ow, oh, 1, STX_U8, &pmask));
+        if (b->kind != STX_BLEND_MULTIBAND) STX_TRY(stx_buf_new(ctx, ow, oh, 1, STX_U8, &pmask));  // (multi-band: mb_finish's, or the rig's)
         if (out_pano_s16) STX_TRY(stx_buf_new(ctx, ow, oh, 3, STX_S16, &p16));
-        if (b->kind == STX_BLEND_MULTIBAND) return mb_finish(b, pano.get(), pmask.get(), p16.get());
+        if (b->kind == STX_BLEND_MULTIBAND) return mb_finish(b, pano.get(), &pmask, p16.get());
         if (b->kind == STX_BLEND_NO) return no_finish(b, pano.get(), pmask.get(), p16.get());
         return feather_finish(b, pano.get(), pmask.get(), p16.get());
     }();
-    if (rc == STX_OK) mb_hand_over_weights(b);
+    if (rc == STX_OK && b->kind == STX_BLEND_MULTIBAND) mb_hand_over_weights(b, pmask.get());
     // whatever the outcome, the blender is spent
     b->finished = true;
     blender_release(b);  // stream-ordered: the kernels above were enqueued before any reuse

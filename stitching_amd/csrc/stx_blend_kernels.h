@@ -72,6 +72,9 @@ struct MbLevelK {
 // preconditions do not hold and the generic kernel must be used instead.
 bool stx_fast_mb_down_batch(stx_ctx* ctx, const StxMbImage* d_images, const StxMbImage* h_images, int n, int level, bool weights);
 bool stx_fast_mb_level(stx_ctx* ctx, const MbLevelK& K);
+// level 0: would stx_fast_mb_level(K) launch kernels that pass over a null K.pmask (the REPLAY instantiations of the packed gather, with
+// the deferred pass behind them)?  Only then may a level-0 block go out without a mask buffer: every other kernel stores the mask
+bool stx_fast_mb_level0_skips_mask(const MbLevelK& K);
 // cover tables (MbLevelK::cover): the tile dimensions of the packed gathers over a region, and the launch that fills one table of
 // tiles_x * tiles_y words for at most 64 images (false: nothing was launched)
 void stx_fast_mb_cover_dims(int x0, int x1, int y0, int y1, int* tiles_x, int* tiles_y, int* band_rows);

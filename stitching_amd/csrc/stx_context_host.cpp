@@ -127,8 +127,16 @@ int stx_dev_alloc(stx_ctx* ctx, size_t bytes, void** out)
     std::lock_guard<std::mutex> lock(ctx->alloc_mutex);
     auto it = ctx->free_blocks.find(b);
     if (it != ctx->free_blocks.end() && !it->second.empty()) {
-        *out = it->second.back();
-        it->second.pop_back();
+        // the free block with the LOWEST address, not the one freed last: which block a request gets then depends on the set of free
+        // blocks alone, never on the order they came back in (Python finalizers, a blender's release) — the n-th panorama of a rig is
+        // handed the addresses of the (n - 1)-th, which the resident descriptor tables of stx_mb_weights live on.  The lists are short.
+        std::vector<void*>& v = it->second;
+        size_t lo = 0;
+        for (size_t i = 1; i < v.size(); i++)
+            if (v[i] < v[lo]) lo = i;
+        *out = v[lo];
+        v[lo] = v.back();
+        v.pop_back();
         return STX_OK;
     }
     void* p = nullptr;

@@ -91,6 +91,11 @@ struct stx_ctx {
     double* exp_sqrt = nullptr;
     // gather launches of the last blend() that took their images from a cover table (stx_debug_blend_replayed)
     int blend_replayed = 0;
+    // table kernels the last batched warp launched (stx_debug_warp_table_launches), descriptor uploads of the last blend()
+    // (stx_debug_blend_uploads)
+    int warp_table_launches = 0;
+    int blend_uploads = 0;
+    int blend_mask_stored = 0;  // the level-0 launch of the last multi-band blend() stored the panorama mask (stx_debug_blend_mask_stored)
 };
 
 #define STX_STAGE_SEGS 4
@@ -204,8 +209,19 @@ struct StxWarpLaunch {
 };
 // typed projectors only (plane / affine / cylindrical / spherical / mercator), Q15 or float remap: what a fused gain needs
 bool stx_warp_fast_eligible(const StxWarpLaunch& L);
+// The column / row tables of one batched warp call of the typed projectors, kept between calls (stx_warp_batch_rects_kept): the device
+// block and, per image, everything warp_tables_kernel reads.  The launcher compares the record with the call in front of it and rebuilds
+// the tables into the handle on any difference: the decision is never the caller's.
+struct StxWarpTabRec { int family, dw, dh, tlx, tly, trig; float scale, t0, t1, kr1, kr4, kr7; };
+struct stx_warp_tables {
+    stx_ctx* ctx = nullptr;
+    int type = -1;                   // the launcher's instantiation (STX_WARP_PLANE / _CYLINDRICAL / _SPHERICAL); -1: nothing recorded
+    std::vector<StxWarpTabRec> rec;  // one per image of the call, in order
+    void* block = nullptr;           // an allocator block of `floats2` float2: the cursor layout of launch_typed follows from dw and dh
+    size_t floats2 = 0;
+};
 int stx_launch_warp(stx_ctx* ctx, const StxWarpLaunch& L);
-int stx_launch_warp_batch(stx_ctx* ctx, const StxWarpLaunch* Ls, int n);
+int stx_launch_warp_batch(stx_ctx* ctx, const StxWarpLaunch* Ls, int n, stx_warp_tables* kept = nullptr);
 int stx_launch_roi_minmax(stx_ctx* ctx, int n, const StxProjector* projs, const int* sizes_wh, float* out_minmax4);
 
 // multi-band -------------------------------------------------------------------------------------
@@ -426,6 +442,7 @@ struct stx_blender {
     stx_mb_weights* adopted = nullptr;  // stx_blend_use_weights: the handle whose weights the images point to (one reference held);
                                       // the pyramids are then built without their weight half
     StxMbImage* d_all = nullptr;      // device copy of `images` as the pyramid pass uploaded it, while it still equals `images` (else null)
+    bool d_all_resident = false;      // d_all is a resident copy of the adopted handle (mb_resident_table), not one of pyr_allocs
     StxMbImage* d_gather = nullptr;   // the device table the gathers of blend() ran on (one of pyr_allocs; mb_hand_over_weights records the cover from it)
     int band_x0 = 0, band_x1 = 0;     // columns of the final roi this blender produces (sharded blending)
     int next_order = 0;
@@ -456,6 +473,20 @@ struct stx_mb_weights {
     // 8 bytes per 512 x 2 tile (one of `allocs`)
     struct Cover { int x0, x1, y0, y1, tiles_x, tiles_y, band_rows; unsigned long long* table; };
     Cover cover[STX_MAX_BANDS + 1] = {};
+    // device copies of the descriptor table (StxMbImage per image) of the blenders that adopted this handle, each with its host shadow:
+    // the table is the rig's constants plus buffer addresses, and the context's caching allocator hands the same addresses out again
+    // (the lowest free block of a size: stx_dev_alloc), in a cycle of a few sets where the caller holds results across panoramas.  A blender whose table equals a shadow byte for byte runs on
+    // that copy without an upload; else the least recently used slot is overwritten in stream order (mb_resident_table).  The device
+    // blocks are among `allocs`.
+    struct Resident { StxMbImage* d = nullptr; std::vector<StxMbImage> shadow; unsigned long long used = 0; };
+    static constexpr int kResidentSlots = 4;
+    Resident resident[kResidentSlots];
+    unsigned long long resident_clock = 0;
+    // the finished panorama mask of the blend that filled the handle (one reference held; null: none): a function of the fed masks alone,
+    // so an adopted blender whose output region is [pmask_x0, pmask_x1) x [0, pmask_h) hands this buffer out, shared and read-only, and its
+    // level-0 gather stores no mask (mb_finish).  w * h bytes of the panorama.
+    stx_buf* pmask = nullptr;
+    int pmask_x0 = 0, pmask_x1 = 0, pmask_h = 0;
 };
 void stx_mb_weights_release(stx_mb_weights* w);
 // MultiBandBlender::feed geometry: the feed rectangle (tl_new .. br_new) relative to the padded roi

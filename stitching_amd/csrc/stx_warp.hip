@@ -1195,16 +1195,46 @@ bool fast_ok(const WarpK& K)
 }
 
 template <int TYPE>
-int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, const char* prof_name, const double* algo_bytes, int dbg)
+int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, const char* prof_name, const double* algo_bytes, int dbg,
+                 stx_warp_tables* kept)
 {
     hipStream_t s = ctx->stream;
     // per-column / per-row trig tables (a few KB per image, L2 resident), one allocation for the batch, freed in stream order
     size_t total = 0;
     // in float2 units: dw4 column entries + dh4 / 4 row blocks of 16 floats + dh4 floats (rb), rounded up to 3 dh4 float2
     for (int i = 0; i < n; i++) total += (((size_t)Ks[i].dw + 3) & ~(size_t)3) + 3 * (((size_t)Ks[i].dh + 3) & ~(size_t)3) + 32;
+    // kept tables (stx_warp_tables): everything warp_tables_kernel reads, compared with the handle's record — equal: the tables of the
+    // handle's block are the ones this call would make (the cursor layout below follows from dw and dh, which are part of the record);
+    // else they are made again, into the handle.  Stream order keeps earlier warps' reads in front of the rewrite.
+    bool make_tables = true;
     StxDevBlock tab;
-    STX_TRY(stx_dev_alloc(ctx, total * sizeof(float2), &tab));
-    float2* cursor = (float2*)tab.get();
+    float2* cursor = nullptr;
+    if (kept) {
+        std::vector<StxWarpTabRec> rec(n);
+        memset(rec.data(), 0, sizeof(StxWarpTabRec) * (size_t)n);
+        for (int i = 0; i < n; i++) {
+            const WarpK& K = Ks[i];
+            StxWarpTabRec& r = rec[i];
+            r.family = K.family; r.dw = K.dw; r.dh = K.dh; r.tlx = K.tlx; r.tly = K.tly; r.trig = K.trig;
+            r.scale = K.scale; r.t0 = K.t[0]; r.t1 = K.t[1]; r.kr1 = K.kr[1]; r.kr4 = K.kr[4]; r.kr7 = K.kr[7];
+        }
+        make_tables = !(kept->block && kept->type == TYPE && kept->floats2 == total && kept->rec.size() == (size_t)n &&
+                        memcmp(kept->rec.data(), rec.data(), sizeof(StxWarpTabRec) * (size_t)n) == 0);
+        if (make_tables) {
+            kept->type = -1;  // nothing recorded until the block below is this call's
+            if (kept->floats2 != total || !kept->block) {
+                if (kept->block) stx_dev_free(ctx, kept->block);
+                kept->block = nullptr; kept->floats2 = 0;
+                STX_TRY(stx_dev_alloc(ctx, total * sizeof(float2), &kept->block));
+                kept->floats2 = total;
+            }
+            kept->rec.swap(rec);  // valid (type = TYPE) once every batch's table launch is queued: below
+        }
+        cursor = (float2*)kept->block;
+    } else {
+        STX_TRY(stx_dev_alloc(ctx, total * sizeof(float2), &tab));
+        cursor = (float2*)tab.get();
+    }
     for (int base = 0, m = 0; base < n; base += m) {
         // a launch takes up to WARP_BATCH images of one remap model (the sampling block is compiled per model), all with or all without a gain
         const int rm = Ks[base].src ? Ks[base].remap : STX_REMAP_Q15;
@@ -1238,9 +1268,10 @@ int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, cons
             tab_bytes += (double)K.dw * sizeof(float2) + (double)K.dh * 5 * sizeof(float);
             bytes += algo_bytes[base + i];
         }
-        {
+        if (make_tables) {
             StxProfScope prof(ctx, "warp_tables", tab_bytes);
             hipLaunchKernelGGL((warp_tables_kernel<TYPE>), dim3((max_tab + 255) / 256, m), dim3(256), 0, s, B);
+            ctx->warp_table_launches++;
         }
         if (fast) {
             // one launch in this bracket: with the profiler on its events are attached to the launch itself (the kernel's own begin / end
@@ -1315,6 +1346,7 @@ int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, cons
     tab.reset();  // stream-ordered reuse
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return stx_fail(STX_ERR_HIP, "warp kernel launch failed: %s", hipGetErrorString(e));
+    if (kept && make_tables) kept->type = TYPE;
     return STX_OK;
 }
 
@@ -1417,8 +1449,9 @@ void fill_warpk(const StxWarpLaunch& L, WarpK* Kp, double* bytes)
 }  // namespace
 
 // All launches of one call share the projector type and the (image, mask) output selection.
-int stx_launch_warp_batch(stx_ctx* ctx, const StxWarpLaunch* Ls, int n)
+int stx_launch_warp_batch(stx_ctx* ctx, const StxWarpLaunch* Ls, int n, stx_warp_tables* kept)
 {
+    ctx->warp_table_launches = 0;
     if (n <= 0) return STX_OK;
     std::vector<WarpK> Ks(n);
     std::vector<double> bytes(n);
@@ -1427,11 +1460,11 @@ int stx_launch_warp_batch(stx_ctx* ctx, const StxWarpLaunch* Ls, int n)
     const int dbg = Ls[0].debug_maps;  // stx_debug_warp_maps: dimg / dmask are the two float maps
     const char* name = dbg ? "warp_debug_maps" : (img ? (mask ? "warp_img_mask" : "warp_img") : "warp_mask");
     switch (Ls[0].proj.family) {
-    case STX_F_PLANE: return launch_typed<STX_WARP_PLANE>(ctx, Ks.data(), n, img, mask, name, bytes.data(), dbg);
-    case STX_F_CYLINDRICAL: return launch_typed<STX_WARP_CYLINDRICAL>(ctx, Ks.data(), n, img, mask, name, bytes.data(), dbg);
+    case STX_F_PLANE: return launch_typed<STX_WARP_PLANE>(ctx, Ks.data(), n, img, mask, name, bytes.data(), dbg, kept);
+    case STX_F_CYLINDRICAL: return launch_typed<STX_WARP_CYLINDRICAL>(ctx, Ks.data(), n, img, mask, name, bytes.data(), dbg, kept);
     case STX_F_SPHERICAL:
     case STX_F_MERCATOR:  // separable like the sphere (row table: warp_tables_kernel)
-        return launch_typed<STX_WARP_SPHERICAL>(ctx, Ks.data(), n, img, mask, name, bytes.data(), dbg);
+        return launch_typed<STX_WARP_SPHERICAL>(ctx, Ks.data(), n, img, mask, name, bytes.data(), dbg, kept);
     default: return launch_general(ctx, Ks.data(), n, img, mask, name, bytes.data(), dbg);
     }
 }

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <memory>
 
 #include "stx_internal.h"
 
@@ -327,7 +328,8 @@ STX_EXPORT int stx_warp(stx_ctx* ctx, int type, float scale, const float K[9], c
 // coordinates (any sub-rectangle of the ROI gives exactly the ROI warp's pixels there: every pixel is mapped on its own)
 static int warp_batch_impl(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s,
                            const stx_buf* const* srcs, const int* rects, stx_buf** out_imgs, stx_buf** out_masks, int* out_xywh,
-                           const stx_buf* const* gains = nullptr, const int* gflags = nullptr, bool fresh_rois = false)
+                           const stx_buf* const* gains = nullptr, const int* gflags = nullptr, bool fresh_rois = false,
+                           stx_warp_tables* kept = nullptr)
 {
     if (!ctx || !K9s || !R9s || !srcs || n < 0) return stx_fail(STX_ERR_INVALID, "bad argument");
     if (!out_imgs && !out_masks) return stx_fail(STX_ERR_INVALID, "nothing requested");
@@ -433,7 +435,7 @@ static int warp_batch_impl(stx_ctx* ctx, int type, float scale, int n, const flo
             STX_TRY(stx_launch_gain_rows(ctx, n, wh.data(), gains, sub.data(), Hs.data(), yts.data()));
         }
     }
-    STX_TRY(stx_launch_warp_batch(ctx, Ls.data(), n));
+    STX_TRY(stx_launch_warp_batch(ctx, Ls.data(), n, kept));
     gscratch.reset();  // stream-ordered reuse
     if (gains && !fused) STX_TRY(stx_block_gain_apply_batch(ctx, n, stx_buf_ptrs(bi).data(), gains, sub.data(), gflags));
     for (int i = 0; i < n; i++) {
@@ -465,6 +467,89 @@ STX_EXPORT int stx_warp_batch_gain(stx_ctx* ctx, int type, float scale, int n, c
     if (!gain_maps || !out_imgs) return stx_fail(STX_ERR_INVALID, "null argument");
     return warp_batch_impl(ctx, type, scale, n, K9s, R9s, srcs, rects_xywh_or_null, out_imgs, out_masks, rects_xywh_or_null ? nullptr : out_xywh_or_null,
                            gain_maps, gain_flags);
+}
+
+// ---- tables kept per rig (include/stitching_amd.h: stx_warp_batch_rects_kept) ----------------------------------------------------------
+// the handle of a call: the caller's, or a new one that becomes the caller's when the call succeeds
+static int warp_kept_call(stx_ctx* ctx, stx_warp_tables** tables, int (*call)(stx_warp_tables*, void*), void* args)
+{
+    if (!ctx || !tables) return stx_fail(STX_ERR_INVALID, "null argument");
+    if (*tables && (*tables)->ctx != ctx)
+        return stx_fail(STX_ERR_INVALID, "warp tables: the handle belongs to another context (no cross-stream use)");
+    stx_warp_tables* t = *tables;
+    std::unique_ptr<stx_warp_tables> fresh;
+    if (!t) {
+        fresh.reset(new stx_warp_tables());
+        fresh->ctx = ctx;
+        t = fresh.get();
+    }
+    const int rc = call(t, args);
+    if (rc != STX_OK) {
+        if (fresh && fresh->block) { stx_set_device(ctx); stx_dev_free(ctx, fresh->block); }
+        return rc;
+    }
+    if (fresh) *tables = fresh.release();
+    return STX_OK;
+}
+
+STX_EXPORT int stx_warp_batch_rects_kept(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s,
+                                         const stx_buf* const* srcs, const int* rects_xywh, stx_buf** out_imgs, stx_buf** out_masks,
+                                         stx_warp_tables** tables)
+{
+    if (!rects_xywh) return stx_fail(STX_ERR_INVALID, "null argument");
+    struct A { stx_ctx* ctx; int type; float scale; int n; const float *K, *R; const stx_buf* const* srcs; const int* rects; stx_buf **oi, **om; };
+    A a{ctx, type, scale, n, K9s, R9s, srcs, rects_xywh, out_imgs, out_masks};
+    return warp_kept_call(ctx, tables, [](stx_warp_tables* t, void* p) {
+        const A& a = *static_cast<A*>(p);
+        return warp_batch_impl(a.ctx, a.type, a.scale, a.n, a.K, a.R, a.srcs, a.rects, a.oi, a.om, nullptr, nullptr, nullptr, false, t);
+    }, &a);
+}
+
+STX_EXPORT int stx_warp_batch_gain_kept(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s,
+                                        const stx_buf* const* srcs, const int* rects_xywh, const stx_buf* const* gain_maps, const int* gain_flags,
+                                        stx_buf** out_imgs, stx_buf** out_masks, stx_warp_tables** tables)
+{
+    if (!rects_xywh || !gain_maps || !out_imgs) return stx_fail(STX_ERR_INVALID, "null argument");
+    struct A { stx_ctx* ctx; int type; float scale; int n; const float *K, *R; const stx_buf* const* srcs; const int* rects;
+               const stx_buf* const* gains; const int* gflags; stx_buf **oi, **om; };
+    A a{ctx, type, scale, n, K9s, R9s, srcs, rects_xywh, gain_maps, gain_flags, out_imgs, out_masks};
+    return warp_kept_call(ctx, tables, [](stx_warp_tables* t, void* p) {
+        const A& a = *static_cast<A*>(p);
+        return warp_batch_impl(a.ctx, a.type, a.scale, a.n, a.K, a.R, a.srcs, a.rects, a.oi, a.om, nullptr, a.gains, a.gflags, false, t);
+    }, &a);
+}
+
+STX_EXPORT int stx_warp_batch_with_rois_kept(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s,
+                                             const stx_buf* const* srcs, const stx_buf* const* gain_maps_or_null, const int* gain_flags_or_null,
+                                             stx_buf** out_imgs, stx_buf** out_masks, int* out_xywh, stx_warp_tables** tables)
+{
+    if (!out_xywh) return stx_fail(STX_ERR_INVALID, "null argument");
+    if (gain_maps_or_null && !out_imgs) return stx_fail(STX_ERR_INVALID, "gains without images");
+    struct A { stx_ctx* ctx; int type; float scale; int n; const float *K, *R; const stx_buf* const* srcs;
+               const stx_buf* const* gains; const int* gflags; stx_buf **oi, **om; int* xywh; };
+    A a{ctx, type, scale, n, K9s, R9s, srcs, gain_maps_or_null, gain_flags_or_null, out_imgs, out_masks, out_xywh};
+    return warp_kept_call(ctx, tables, [](stx_warp_tables* t, void* p) {
+        const A& a = *static_cast<A*>(p);
+        return warp_batch_impl(a.ctx, a.type, a.scale, a.n, a.K, a.R, a.srcs, nullptr, a.oi, a.om, a.xywh, a.gains, a.gflags, true, t);
+    }, &a);
+}
+
+STX_EXPORT int stx_warp_tables_free(stx_warp_tables* t)
+{
+    if (!t) return STX_OK;
+    if (t->block) {
+        hipSetDevice(t->ctx->device);
+        stx_dev_free(t->ctx, t->block);  // stream-ordered, as stx_mb_weights_free
+    }
+    delete t;
+    return STX_OK;
+}
+
+STX_EXPORT int stx_debug_warp_table_launches(stx_ctx* ctx, int* out_launches)
+{
+    if (!ctx || !out_launches) return stx_fail(STX_ERR_INVALID, "null argument");
+    *out_launches = ctx->warp_table_launches;
+    return STX_OK;
 }
 
 STX_EXPORT int stx_warp_batch_with_rois(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s,

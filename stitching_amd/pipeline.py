@@ -21,7 +21,7 @@ from .seam_estimation import SeamEstimator
 from .seam_finder import DEVICE_SEAM_FINDERS, SeamFinder
 from .stitching_error import StitchingError
 from .synthetic import blend_strength_for_bands
-from .warper import Warper
+from .warper import Warper, WarpTables
 
 
 def mask_box(mask):
@@ -107,10 +107,11 @@ class _RigGeometry:
     masks they are fed, what the blender is prepared on — and the blender's weight pyramids, which follow from all of that."""
 
     __slots__ = ("key", "rects", "prep_corners", "prep_sizes", "feed_corners", "feed_masks", "blend_strength", "crop", "gain_in_warp",
-                 "gain_corners", "gain_sub", "weights", "blender")
+                 "gain_corners", "gain_sub", "weights", "tables", "blender")
 
     def __init__(self):
         self.key = self.weights = self.crop = self.gain_corners = self.gain_sub = None
+        self.tables = WarpTables()  # the warp's column / row tables: filled by the first images-only warp into the kept rectangles
         self.blender = None  # the pass's own prepared blender, where it needed one before its warps: taken by the run that made it
         self.gain_in_warp = True
 
@@ -242,6 +243,8 @@ class StitchJob:
         g, self._geometry = self._geometry, None
         if g is not None and g.weights is not None:
             g.weights.free()
+        if g is not None:
+            g.tables.free()
 
     def geometry_key(self):
         """rig_key of the job as it stands now"""
@@ -270,7 +273,7 @@ class StitchJob:
                 # a panorama of a known rig: the images alone, into the kept rectangles (no ROI pass, no wait, no mask, no seam_resize)
                 imgs, _, _ = self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect, rects=g.rects,
                                                                compensator=self.compensator if g.gain_in_warp else None,
-                                                               camera_arrays=self._cam_arrays, masks=False)
+                                                               camera_arrays=self._cam_arrays, masks=False, tables=g.tables)
                 if self.compensator is not None and not g.gain_in_warp:
                     imgs = self.compensator.apply_all(g.gain_corners, imgs, None, sub=g.gain_sub, ctx=self.ctx)
             self.last_crop = g.crop
@@ -308,7 +311,8 @@ class StitchJob:
         warped = None
         if self._mask_cols is None:
             warped = self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect, compensator=self.compensator,
-                                                       with_rois=True, camera_arrays=self._cam_arrays)
+                                                       with_rois=True, camera_arrays=self._cam_arrays,
+                                                       tables=g.tables if self.reuse_geometry else None)
             self._adopt([r[0:2] for r in warped[2]], [r[2:4] for r in warped[2]])
         else:
             self.plan()
@@ -321,7 +325,8 @@ class StitchJob:
             box = [c if c is not None else (0, w, 0, h) for c, (w, h) in zip(crop, self.warped_sizes)]
             rects = [(cx + x0, cy + y0, x1 - x0, y1 - y0) for (x0, x1, y0, y1), (cx, cy) in zip(box, self.corners)]
             imgs, masks, rois = self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect, rects=rects,
-                                                                  compensator=self.compensator, camera_arrays=self._cam_arrays)
+                                                                  compensator=self.compensator, camera_arrays=self._cam_arrays,
+                                                                  tables=g.tables if self.reuse_geometry else None)
             if self.feed_masks is not None:
                 masks = [m[y0:y1, x0:x1] for m, (x0, x1, y0, y1) in zip(self.feed_masks, box)]
             else:

@@ -30,6 +30,33 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+class WarpTables:
+    """Owns one stx_warp_tables: the column / row tables of a batched warp of the typed projectors, kept for the next panoramas of the
+    same rig (include/stitching_amd.h: stx_warp_batch_rects_kept).  A few KB per image.  The library fills it at the first call that
+    takes it and decides at every later one whether the tables still answer."""
+
+    def __init__(self):
+        self.ctx, self._h = None, C.c_void_p()
+
+    def _ref(self, ctx):
+        """the handle as the entry points take it (in and out); bound to the context of its first call"""
+        if self.ctx is None:
+            self.ctx = ctx
+        return C.byref(self._h)
+
+    def free(self):
+        if self._h is not None and self._h.value:
+            if getattr(self.ctx, "handle", None):
+                self.ctx._lib.stx_warp_tables_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Warper:
     """https://docs.opencv.org/4.x/da/db8/classcv_1_1detail_1_1RotationWarper.html"""
 
@@ -154,7 +181,8 @@ class Warper:
                                                     src._h, C.byref(oi), C.byref(om), roi))
         return (self._result(DeviceImage(ctx, oi)), self._result(DeviceImage(ctx, om)), tuple(int(v) for v in roi))
 
-    def warp_images_and_masks(self, imgs, cameras, aspect=1, rects=None, compensator=None, with_rois=False, camera_arrays=None, masks=True):
+    def warp_images_and_masks(self, imgs, cameras, aspect=1, rects=None, compensator=None, with_rois=False, camera_arrays=None, masks=True,
+                              tables=None):
         """Batched form of warp_images + create_and_warp_masks (stitching/warper.py:39-41, 54-56) for a list of
         images: one ROI pass, one table launch and one remap launch for all of them (stx_warp_batch).
         Returns (warped_images, warped_masks, rois).
@@ -167,7 +195,9 @@ class Warper:
         launched right behind it from native code (stx_warp_batch_with_rois: a panorama's latency, see StitchJob.run).
         camera_arrays: Warper.camera_arrays(cameras, aspect), for callers that keep it.
         masks=False (with rects): the images alone — no mask is written, None comes back in their place (a caller that kept the masks
-        of an earlier call with the same cameras and rectangles: StitchJob)."""
+        of an earlier call with the same cameras and rectangles: StitchJob).
+        tables (with rects or with_rois): a WarpTables — the typed projectors' column / row tables are kept in it from call to call; the library
+        compares what they depend on and makes them again where anything differs (stx_warp_batch_rects_kept)."""
         ctx = self._ctx()
         srcs = [self._source(img, ctx) for img in imgs]
         cameras = list(cameras)
@@ -181,6 +211,8 @@ class Warper:
             if rects is None:
                 raise StitchingError("masks=False needs rects: the rectangles of the call that made the masks")
             h_mask = None
+        if tables is not None and rects is None and not with_rois:
+            raise StitchingError("tables= needs rects or with_rois: kept tables belong to given rectangles")
         rois = np.zeros((n, 4), np.int32)
         blocks = compensator is not None and compensator.compensator_type in ("gain_blocks", "channel_blocks")
         if blocks and compensator.gains is None:
@@ -191,8 +223,12 @@ class Warper:
                 gm = [compensator._gain_map(i, ctx) for i in range(n)]
                 ga, fl = (C.c_void_p * n)(*[g[0]._h for g in gm]), (C.c_int * n)(*[g[1] for g in gm])
                 compensator = None
-            _lib.check(ctx._lib.stx_warp_batch_with_rois(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src, ga, fl,
-                                                         h_img, h_mask, rois.ctypes.data_as(C.POINTER(C.c_int))))
+            if tables is not None:
+                _lib.check(ctx._lib.stx_warp_batch_with_rois_kept(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src, ga,
+                                                                  fl, h_img, h_mask, rois.ctypes.data_as(C.POINTER(C.c_int)), tables._ref(ctx)))
+            else:
+                _lib.check(ctx._lib.stx_warp_batch_with_rois(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src, ga, fl,
+                                                             h_img, h_mask, rois.ctypes.data_as(C.POINTER(C.c_int))))
         elif blocks:
             gm = [compensator._gain_map(i, ctx) for i in range(n)]
             ga, fl = (C.c_void_p * n)(*[g[0]._h for g in gm]), (C.c_int * n)(*[g[1] for g in gm])
@@ -200,13 +236,21 @@ class Warper:
             if rects is not None:
                 rois = np.ascontiguousarray(np.asarray(rects, np.int32).reshape(n, 4))
                 rp = rois.ctypes.data_as(C.POINTER(C.c_int))
-            _lib.check(ctx._lib.stx_warp_batch_gain(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src, rp, ga, fl,
-                                                    h_img, h_mask, None if rects is not None else rois.ctypes.data_as(C.POINTER(C.c_int))))
+            if tables is not None:
+                _lib.check(ctx._lib.stx_warp_batch_gain_kept(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src, rp, ga,
+                                                             fl, h_img, h_mask, tables._ref(ctx)))
+            else:
+                _lib.check(ctx._lib.stx_warp_batch_gain(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src, rp, ga, fl,
+                                                        h_img, h_mask, None if rects is not None else rois.ctypes.data_as(C.POINTER(C.c_int))))
             compensator = None
         elif rects is not None:
             rois = np.ascontiguousarray(np.asarray(rects, np.int32).reshape(n, 4))
-            _lib.check(ctx._lib.stx_warp_batch_rects(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src,
-                                                     rois.ctypes.data_as(C.POINTER(C.c_int)), h_img, h_mask))
+            if tables is not None:
+                _lib.check(ctx._lib.stx_warp_batch_rects_kept(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src,
+                                                              rois.ctypes.data_as(C.POINTER(C.c_int)), h_img, h_mask, tables._ref(ctx)))
+            else:
+                _lib.check(ctx._lib.stx_warp_batch_rects(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src,
+                                                         rois.ctypes.data_as(C.POINTER(C.c_int)), h_img, h_mask))
         else:
             _lib.check(ctx._lib.stx_warp_batch(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src,
                                                h_img, h_mask, rois.ctypes.data_as(C.POINTER(C.c_int))))

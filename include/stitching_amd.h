@@ -474,6 +474,20 @@ int stx_features_detect(stx_ctx* ctx, int n, const stx_buf* const* images, const
 int stx_match_features(stx_ctx* ctx, int n, const unsigned char* const* desc, const int* desc_shape, const double* const* pts,
                        const int* pts_rows, int ratio_T, int range_width, int ransac_iters, double threshold_sq, unsigned seed,
                        int* out_counts, int* out_matches, unsigned char* out_mask, int* out_pick, double* out_H, double out_info[4]);
+/* stx_match_features with the geometric model of the RANSAC chosen: STX_MATCH_MODEL_HOMOGRAPHY is stx_match_features bit for bit (which
+ * forwards here with it).  The affine models are for scans and flat tiles; pts are then level-0 pixels that are NOT centred, the frame
+ * the affine warper applies a camera's R in.  _AFFINE_PARTIAL: a similarity (4 degrees of freedom) of 2 sampled matches; _AFFINE_FULL:
+ * an affine map (6) of 3.  The sampler is the homography's restricted to the first 2 or 3 draws; the closed forms are division free
+ * and homogeneous, out_H[9 k] = {h0 .. h5, +0.0, +0.0, h8} with h8 > 0 after the sign rule (h8 == 0, coincident or collinear sample
+ * points: no inliers); inliers, best hypothesis and mask as for the homography.  tests/numpy_affine.py is the contract (DESIGN.md
+ * section 18).  A model outside the three is refused with STX_ERR_INVALID before anything is launched. */
+#define STX_MATCH_MODEL_HOMOGRAPHY 0
+#define STX_MATCH_MODEL_AFFINE_PARTIAL 1
+#define STX_MATCH_MODEL_AFFINE_FULL 2
+int stx_match_features_model(stx_ctx* ctx, int n, const unsigned char* const* desc, const int* desc_shape, const double* const* pts,
+                             const int* pts_rows, int ratio_T, int range_width, int ransac_iters, double threshold_sq, unsigned seed,
+                             int model, int* out_counts, int* out_matches, unsigned char* out_mask, int* out_pick, double* out_H,
+                             double out_info[4]);
 /* ---- ray bundle adjustment: the project's OWN solver, not cv.detail.BundleAdjusterRay ("ray" stays cv2's) ----------------------------
  * The normal equations of CameraSolver's Levenberg-Marquardt steps.  An edge is a pair of cameras i < j with its inlier matches
  * (x, y) in image i and (u, v) in image j, level-0 pixels relative to the image centre.  A camera has 9 variants of 10 doubles
@@ -494,6 +508,14 @@ typedef struct stx_ray_problem stx_ray_problem;
 int stx_ray_problem_create(stx_ctx* ctx, int n_edges, const int* edge_cams, const long long* offsets, const double* pts,
                            stx_ray_problem** out);
 int stx_ray_problem_eval(stx_ray_problem* problem, int n_cams, const double* variants, double* out, double out_info[4]);
+/* The normal equations of CameraSolver's affine-partial adjustment (model="affine"), on a problem made by stx_ray_problem_create from
+ * points that are NOT centred.  A camera is the similarity T = [[a, -b, tx], [b, a, ty], [0, 0, 1]] from its image to the panorama
+ * plane; it has 9 variants of 8 doubles {a, b, tx, ty, a', b', tx', ty'}, the map and its inverse: its parameters, then + and - 1e-3
+ * on each of the four (made by the caller).  Per match P = T_i (x, y), Q = T_j^-1 P, the residual (u, v) - Q in image j's pixels and
+ * its 2 x 8 Jacobian by central differences over the variants; per edge the same 45 sums in the same order of summation as
+ * stx_ray_problem_eval.  Multiplies, adds and subtractions only.  tests/numpy_affine.py is the contract, in the bits of all 45 sums
+ * (DESIGN.md section 18).  variants[n_cams * 72] -> out[45 e]; out_info and the refusals as stx_ray_problem_eval's. */
+int stx_affine_problem_eval(stx_ray_problem* problem, int n_cams, const double* variants, double* out, double out_info[4]);
 int stx_ray_problem_free(stx_ray_problem* problem);
 /* stx_resize_linear_exact <- stitching/images.py:122-124 cv.resize(img, size, interpolation=cv.INTER_LINEAR_EXACT) (u8x1 / u8x3:
  *                            the final-resolution resize of Images.resize, next row N3)

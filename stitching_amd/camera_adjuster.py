@@ -2,8 +2,9 @@
 
 Without `solver=` it is the reference's class: the name picks cv.detail's BundleAdjusterRay / Reproj / AffinePartial / NoBundleAdjuster —
 OpenCV's, on the host.  With `solver=CameraSolver()` the cameras are refined by the project's own ray adjustment on the device.  That
-adjustment answers to no name here: "ray" stays cv2's; "reproj" and "affine" have no counterpart, and neither has a refinement mask
-other than "xxxxx" (all of focal and rotation move; the principal point and the aspect are not parameters).
+adjustment answers to no name here: "ray" stays cv2's; "reproj" has no counterpart, "affine" goes with a solver only where that solver's
+own `model` is "affine", and no refinement mask other than "xxxxx" has one (all of focal and rotation move; the principal point and the
+aspect are not parameters).
 """
 import numpy as np
 
@@ -33,7 +34,7 @@ class CameraAdjuster:
         self.adjuster = None
         self.kind, self.confidence_threshold = adjuster, confidence_threshold
         if solver is not None:
-            if adjuster in ("reproj", "affine"):
+            if adjuster == "reproj" or (adjuster == "affine" and getattr(solver, "model", None) != "affine"):
                 raise StitchingError(f'the "{adjuster}" camera adjuster has no counterpart in the solver: it adjusts rays')
             if adjuster not in self.CAMERA_ADJUSTER_CHOICES:
                 raise StitchingError(f"unknown camera adjuster {adjuster!r}")

@@ -11,6 +11,11 @@ their Jacobian with respect to both cameras, summed into the normal equations â€
 device (csrc/stx_cameras.hip), equal to the contract in the bits of all 45 float64 sums of an edge; DESIGN.md section 17 has the kernel
 and the limits.  What is small and wants float64 with a library behind it is numpy on the host: the subset, the focals, the spanning
 tree and its rotations, the 9 variants of every camera, the 4n x 4n solve, the wave correction.
+
+With model="affine" the same solver registers scans and flat tiles: a camera is a transform of the plane (camera.R the 3 x 3 map from
+image pixels to the panorama plane, focal = 1, ppx = ppy = 0, as the affine warper takes it), estimated along the same spanning tree
+and refined as a similarity (a, b, tx, ty) by the same Levenberg-Marquardt loop over a residual in pixels; tests/numpy_affine.py is
+that contract and DESIGN.md section 18 the description.
 """
 import ctypes as C
 import math
@@ -21,10 +26,12 @@ import numpy as np
 from . import _lib
 from .camera import CameraParams
 from .device import get_context
-from .match_estimation import centred_points
+from .match_estimation import centred_points, level0_points
 from .stitching_error import StitchingError, StitchingWarning
 
 STEP = 1e-3  # of the central differences, on every parameter
+MODELS = ("rotation", "affine")
+_UNSET = object()  # a wave_correct that was not passed: "horiz" for rotations, "no" for the affine model
 WAVE_KINDS = ("horiz", "vert", "no")
 NO_MATCH_MESSAGE = ("No match exceeds the given confidence threshold. Do your images have enough overlap and common features? If yes, "
                     "you might want to lower the 'confidence_threshold' or try another 'detector'.")
@@ -170,6 +177,25 @@ def tree_rotations(matches, n, focals):
     return [R[k] for k in range(n)]
 
 
+def tree_transforms(matches, n):
+    """float64 affine transforms along the spanning tree from its centre (T = I there): T_to = T_from H_(to -> from), image pixels to
+    the centre image's pixels"""
+    near, centre = spanning_tree(matches, n)
+    if near is None:
+        raise StitchingError("Homography estimation failed.")
+    T = {centre: np.eye(3)}
+    front = [centre]
+    while front:
+        nxt = []
+        for a in front:
+            for b in near[a]:
+                if b not in T:
+                    T[b] = T[a] @ _homography(matches, n, b, a)
+                    nxt.append(b)
+        front = nxt
+    return [T[k] for k in range(n)]
+
+
 # ---- Rodrigues -----------------------------------------------------------------------------------------------------------------------------
 def rotation_matrix(r):
     """Rodrigues vector -> (3, 3) float64: (1 - c) k k^T + c I + s [k]x with (1 - c) k_a multiplied first, as the contract writes it"""
@@ -229,6 +255,37 @@ def camera_variants(params):
     return out
 
 
+def similarity_parameters(R):
+    """a, b, tx, ty of the similarity nearest to the linear part of the transform R, its translation kept"""
+    T = np.asarray(R, np.float64)
+    return [(T[0, 0] + T[1, 1]) / 2, (T[1, 0] - T[0, 1]) / 2, T[0, 2], T[1, 2]]
+
+
+def similarity_matrix(p):
+    a, b, tx, ty = (float(v) for v in p)
+    return np.array([[a, -b, tx], [b, a, ty], [0.0, 0.0, 1.0]])
+
+
+def similarity_variants(params):
+    """(n, 9, 8) float64 for params (n, 4) rows a, b, tx, ty: per camera its parameters, then + and - STEP on each of the four (+ before
+    -); a variant is the map a, b, tx, ty and its inverse a' = a / d, b' = -b / d, tx' = -(a' tx - b' ty), ty' = -(b' tx + a' ty),
+    d = a a + b b (not finite where d is 0)."""
+    params = np.ascontiguousarray(params, np.float64).reshape(-1, 4)
+    shifts = np.zeros((9, 4), np.float64)
+    for k in range(4):
+        shifts[1 + 2 * k, k], shifts[2 + 2 * k, k] = STEP, -STEP
+    out = np.zeros((len(params), 9, 8), np.float64)
+    with np.errstate(all="ignore"):
+        moved = params[:, None, :] + shifts[None, :, :]
+        a, b, tx, ty = (moved[:, :, k] for k in range(4))
+        d = a * a + b * b
+        ai, bi = a / d, -b / d
+        out[:, :, 0:4] = moved
+        out[:, :, 4], out[:, :, 5] = ai, bi
+        out[:, :, 6], out[:, :, 7] = -(ai * tx - bi * ty), -(bi * tx + ai * ty)
+    return out
+
+
 # ---- the ray problem on the device ---------------------------------------------------------------------------------------------------------
 def ray_edges(matches, n, conf_thresh):
     """the pairs i < j whose confidence is above conf_thresh, ascending"""
@@ -255,8 +312,10 @@ class RayProblem:
     """The edges of one adjustment on the device (stx_ray_problem): uploaded once, evaluated once per Levenberg-Marquardt step.  Use it
     as a context manager: the handle must go before its context does."""
 
-    def __init__(self, edges, offsets, xyuv, ctx=None):
+    def __init__(self, edges, offsets, xyuv, ctx=None, model="rotation"):
+        """model "affine": the edges are the same; an evaluation takes (n, 9, 8) similarity variants (stx_affine_problem_eval)"""
         self.ctx = ctx or get_context()
+        self.model = model
         self.n_edges = len(edges)
         self._h = C.c_void_p()
         cams = np.ascontiguousarray(np.asarray(edges, np.int32).reshape(-1, 2))
@@ -270,10 +329,12 @@ class RayProblem:
     def evaluate(self, variants):
         """(n, 9, 10) variants -> (e, 45) float64 sums E, g[8], B[36] of every edge; one launch, one wait"""
         variants = np.ascontiguousarray(variants, np.float64)
+        if self.model == "affine" and (variants.ndim != 3 or variants.shape[1:] != (9, 8)):
+            raise StitchingError(f"variants of shape {variants.shape}: the affine adjustment takes (cameras, 9, 8)")
         out, info = np.zeros((self.n_edges, 45), np.float64), np.zeros(4, np.float64)
         dp = C.POINTER(C.c_double)
-        _lib.check(self.ctx._lib.stx_ray_problem_eval(self._h, int(variants.shape[0]), variants.ctypes.data_as(dp), out.ctypes.data_as(dp),
-                                                      info.ctypes.data_as(dp)))
+        entry = self.ctx._lib.stx_affine_problem_eval if self.model == "affine" else self.ctx._lib.stx_ray_problem_eval
+        _lib.check(entry(self._h, int(variants.shape[0]), variants.ctypes.data_as(dp), out.ctypes.data_as(dp), info.ctypes.data_as(dp)))
         self.info = {"edges": int(info[0]), "matches": int(info[1]), "device_ms": float(info[2]), "device_ms_with_copy": float(info[3])}
         return out
 
@@ -344,11 +405,24 @@ class CameraSolver:
 
     tests/numpy_cameras.py states it exactly and is the contract; DESIGN.md section 17 has the launch shape.  Construction needs no GPU.
     Limits, refused with a StitchingError before anything is launched: at most MAX_CAMERAS images, at most MAX_MATCHES inlier matches
-    on a pair, parameters that are finite.  Nothing handed in is written; cameras come back as new CameraParams with a float32 R."""
+    on a pair, parameters that are finite.  Nothing handed in is written; cameras come back as new CameraParams with a float32 R.
+
+    model="affine" (scans and flat tiles, on the matches of MatchEstimator(model="affine")): estimate chains the pairs' transforms along
+    the spanning tree (R is the 3 x 3 map from image pixels to the panorama plane, focal = 1, ppx = ppy = 0); adjust refines a
+    similarity a, b, tx, ty per camera over the residual (u, v) - T_j^-1 T_i (x, y) in pixels, one launch a step as well; there is no
+    wave correction (a wave_correct that is not passed means "no", "horiz" and "vert" are refused).  tests/numpy_affine.py is that
+    contract; DESIGN.md section 18."""
 
     MAX_CAMERAS, MAX_MATCHES = _lib.RAY_MAX_CAMERAS, _lib.RAY_MAX_MATCHES
 
-    def __init__(self, conf_thresh=1.0, wave_correct="horiz", max_evals=100):
+    def __init__(self, conf_thresh=1.0, wave_correct=_UNSET, max_evals=100, model="rotation"):
+        if model not in MODELS:
+            raise StitchingError(f"unknown camera model {model!r}: the solver takes {MODELS}")
+        if wave_correct is _UNSET:
+            wave_correct = "no" if model == "affine" else "horiz"
+        elif model == "affine" and wave_correct in ("horiz", "vert"):
+            raise StitchingError(f'the affine camera model has no wave correction: "no" only, got {wave_correct!r}')
+        self.model = model
         if wave_correct == "auto":
             raise StitchingError('wave correction "auto" is cv2\'s: the solver takes "horiz", "vert" or "no"')
         if wave_correct not in WAVE_KINDS:
@@ -382,6 +456,8 @@ class CameraSolver:
         features = list(features)
         n = len(features)
         self._check_count(n)
+        if self.model == "affine":
+            return [self._affine_camera(T) for T in tree_transforms(matches, n)]
         focal = starting_focal(features, matches)
         return [self._camera(f, focal, R) for f, R in zip(features, tree_rotations(matches, n, [focal] * n))]
 
@@ -390,15 +466,21 @@ class CameraSolver:
         w0, h0 = feature.img_size
         return CameraParams(focal=focal, aspect=1.0, ppx=w0 / 2, ppy=h0 / 2, R=np.asarray(R).astype(np.float32))
 
+    @staticmethod
+    def _affine_camera(T):
+        return CameraParams(focal=1.0, aspect=1.0, ppx=0.0, ppy=0.0, R=np.asarray(T).astype(np.float32))
+
+    def _variants(self, params):
+        return similarity_variants(params) if self.model == "affine" else camera_variants(params)
+
     def _check_count(self, n):
         if n > self.MAX_CAMERAS:
             raise StitchingError(f"camera registration of {n} images: the solver takes up to {self.MAX_CAMERAS}")
 
     # -- adjust
-    @staticmethod
-    def _sums(problem, evaluate, params):
+    def _sums(self, problem, evaluate, params):
         """(e, 45) sums at params, or None where a variant is not finite (a rejected step, not evaluated) â€” the device's, or evaluate's"""
-        variants = camera_variants(params)
+        variants = self._variants(params)
         if not np.isfinite(variants).all():
             return None
         if evaluate is None:
@@ -411,14 +493,15 @@ class CameraSolver:
         if len(params) != n:
             raise StitchingError(f"{len(params)} parameter rows for {n} cameras")
         if not np.isfinite(params).all():
-            raise StitchingError("camera adjustment needs finite parameters (focal and Rodrigues vector per camera)")
+            what = "a, b, tx, ty" if self.model == "affine" else "focal and Rodrigues vector"
+            raise StitchingError(f"camera adjustment needs finite parameters ({what} per camera)")
         return params
 
     def _problem(self, features, matches, conf_thresh=None):
         n = len(features)
         self._check_count(n)
         edges = ray_edges(matches, n, self.conf_thresh if conf_thresh is None else float(conf_thresh))
-        offsets, xyuv = edge_points(features, matches, edges)
+        offsets, xyuv = edge_points(features, matches, edges, [level0_points(f) for f in features] if self.model == "affine" else None)
         counts = np.diff(offsets)
         if len(counts) and int(counts.max()) > self.MAX_MATCHES:
             raise StitchingError(f"a pair with {int(counts.max())} inlier matches: the solver takes up to {self.MAX_MATCHES}")
@@ -426,12 +509,12 @@ class CameraSolver:
 
     def normal_equations(self, features, matches, params, ctx=None):
         """E (e,), g (e, 8) and the upper triangle B (e, 36) of the normal equations of every edge (the pairs i < j with confidence above
-        conf_thresh, ascending) at params (n, 4) rows focal, rx, ry, rz â€” one launch on the device."""
+        conf_thresh, ascending) at params (n, 4) rows focal, rx, ry, rz (model "affine": a, b, tx, ty) â€” one launch on the device."""
         features = list(features)
         params = self._check_params(params, len(features))
         edges, offsets, xyuv = self._problem(features, matches)
-        with RayProblem(edges, offsets, xyuv, ctx) as problem:
-            sums = problem.evaluate(camera_variants(params))
+        with RayProblem(edges, offsets, xyuv, ctx, self.model) as problem:
+            sums = problem.evaluate(self._variants(params))
             self.info = dict(problem.info, evaluations=1)
         return sums[:, 0].copy(), sums[:, 1:9].copy(), sums[:, 9:].copy()
 
@@ -443,20 +526,28 @@ class CameraSolver:
         n = len(features)
         if len(cameras) != n:
             raise StitchingError(f"{len(cameras)} cameras for {n} images")
-        start = self._check_params([[c.focal] + list(rotation_vector(c.R)) for c in cameras], n)
+        if self.model == "affine":
+            start = self._check_params([similarity_parameters(c.R) for c in cameras], n)
+        else:
+            start = self._check_params([[c.focal] + list(rotation_vector(c.R)) for c in cameras], n)
         edges, offsets, xyuv = self._problem(features, matches, conf_thresh)
         if evaluate is not None:
             params, info = self._levenberg_marquardt(None, evaluate, edges, start)
         else:
-            with RayProblem(edges, offsets, xyuv, ctx) as problem:
+            with RayProblem(edges, offsets, xyuv, ctx, self.model) as problem:
                 params, info = self._levenberg_marquardt(problem, None, edges, start)
         info["edges"], info["matches"] = len(edges), int(offsets[-1])
         self.info = info
-        if not np.isfinite(params).all() or (params[:, 0] <= 0).any():
+        failed = ((params[:, 0] == 0) & (params[:, 1] == 0)).any() if self.model == "affine" else (params[:, 0] <= 0).any()
+        if not np.isfinite(params).all() or failed:
             raise StitchingError("Camera parameters adjusting failed.")
         _, centre = spanning_tree(matches, n)
         if centre < 0:
             raise StitchingError("Camera parameters adjusting failed.")
+        if self.model == "affine":
+            Ts = [similarity_matrix(p) for p in params]
+            back = np.linalg.inv(Ts[centre])
+            return [self._affine_camera(back @ T) for T in Ts]
         Rs = [rotation_matrix(p[1:4]) for p in params]
         back = np.linalg.inv(Rs[centre])
         return [self._camera(f, float(p[0]), back @ R) for f, p, R in zip(features, params, Rs)]
@@ -515,6 +606,10 @@ class CameraSolver:
         if kind not in WAVE_KINDS:
             raise StitchingError(f"unknown wave correction {kind!r}: the solver takes {WAVE_KINDS}")
         cameras = list(cameras)
+        if self.model == "affine":
+            if kind != "no":
+                raise StitchingError(f'the affine camera model has no wave correction: "no" only, got {kind!r}')
+            return cameras
         out = []
         for cam, R in zip(cameras, wave_corrected([c.R for c in cameras], kind)):
             out.append(CameraParams(focal=cam.focal, aspect=cam.aspect, ppx=cam.ppx, ppy=cam.ppy, R=R, t=cam.t))

@@ -2,7 +2,7 @@
 
 Without `solver=` it is the reference's class: the name picks cv.detail's HomographyBasedEstimator or AffineBasedEstimator — OpenCV's, on
 the host.  With `solver=CameraSolver()` the cameras come from the project's own solver.  That solver answers to no name here:
-"homography" stays cv2's, and "affine" has no counterpart at all.
+"homography" stays cv2's, and "affine" goes with a solver only where that solver's own `model` is "affine".
 """
 import numpy as np
 
@@ -25,12 +25,12 @@ class CameraEstimator:
     DEFAULT_CAMERA_ESTIMATOR = "homography"
 
     def __init__(self, estimator=DEFAULT_CAMERA_ESTIMATOR, solver=None, **kwargs):
-        """`solver`: a CameraSolver (it carries its own settings); the name is then looked at only to refuse "affine".  Default: the cv2
-        estimator the reference builds for the name."""
+        """`solver`: a CameraSolver (it carries its own settings); the name is then looked at only to refuse "affine" with a solver whose
+        `model` is not "affine".  Default: the cv2 estimator the reference builds for the name."""
         self.solver = solver
         self.estimator = None
         if solver is not None:
-            if estimator == "affine":
+            if estimator == "affine" and getattr(solver, "model", None) != "affine":
                 raise StitchingError('the "affine" camera estimator has no counterpart in the solver: it estimates rotations and focals')
             if kwargs:
                 raise StitchingError(f"a camera solver takes its settings at construction, got {sorted(kwargs)}")

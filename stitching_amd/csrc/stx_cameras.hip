@@ -7,6 +7,9 @@
 //                         Jacobian column at a time from the + and - variant of one parameter, consumed at once (g_k, B_lk for l <= k),
 //                         so that only the 8 columns and not 18 rays are live.  The lane sums are folded in the contract's order:
 //                         strides 128 and 64 through LDS, 32 .. 1 inside the first wavefront, v[l] += v[l + s] either way.
+//   affine_normal_equations  the same launch shape, sums and fold for CameraSolver(model="affine") (tests/numpy_affine.py, DESIGN.md
+//                         section 18): a camera is a similarity of the plane, 9 variants of 8 doubles (the map and its inverse); the
+//                         residual is (u, v) - T_j^-1 T_i (x, y) in image j's pixels — multiplies, adds and subtractions only.
 // The fp64 arithmetic is IEEE multiply, add, subtract, divide and square root in the contract's order: no FMA (the file is compiled with
 // -ffp-contract=off and says so itself below), no MFMA.
 #include "stx_internal.h"
@@ -44,6 +47,35 @@ __device__ inline double dot3(const Ray3& p, const Ray3& q)
 
 // first index of row k of the upper triangle of an 8 x 8 matrix, row-major
 __device__ constexpr int tri_row(int k) { return k * 8 - k * (k - 1) / 2; }
+
+// the 256 lane sums of a workgroup folded in the contract's order, v[l] += v[l + s] for s = 128 .. 1, and written by lane 0: strides 128
+// and 64 through LDS (the upper half of the live lanes writes), 32 .. 1 inside the first wavefront
+__device__ inline void fold_lane_sums(double (&acc)[RAY_SUMS], double* fold, int tid, double* __restrict__ out)
+{
+#pragma unroll
+    for (int s = RAY_WG / 2; s >= 64; s >>= 1) {
+        if (tid >= s && tid < 2 * s) {
+#pragma unroll
+            for (int a = 0; a < RAY_SUMS; a++) fold[a * (RAY_WG / 2) + (tid - s)] = acc[a];
+        }
+        __syncthreads();
+        if (tid < s) {
+#pragma unroll
+            for (int a = 0; a < RAY_SUMS; a++) acc[a] = __dadd_rn(acc[a], fold[a * (RAY_WG / 2) + tid]);
+        }
+        __syncthreads();
+    }
+    if (tid >= 64) return;  // three whole wavefronts
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+#pragma unroll
+        for (int a = 0; a < RAY_SUMS; a++) acc[a] = __dadd_rn(acc[a], __shfl_down(acc[a], s, 64));  // lanes >= s: not used below
+    }
+    if (tid == 0) {
+#pragma unroll
+        for (int a = 0; a < RAY_SUMS; a++) out[a] = acc[a];
+    }
+}
 
 __global__ __launch_bounds__(RAY_WG) void ray_normal_equations_kernel(const int* __restrict__ edge_cams, const long long* __restrict__ offsets,
                                                                       const double* __restrict__ pts, const double* __restrict__ variants,
@@ -83,33 +115,79 @@ __global__ __launch_bounds__(RAY_WG) void ray_normal_equations_kernel(const int*
             for (int l = 0; l <= k; l++) acc[9 + tri_row(l) + (k - l)] = __dadd_rn(acc[9 + tri_row(l) + (k - l)], dot3(J[l], J[k]));
         }
     }
-    // v[l] += v[l + 128], then v[l] += v[l + 64]: the upper half of the live lanes through LDS
+    fold_lane_sums(acc, fold, tid, out + (size_t)e * RAY_SUMS);
+}
+
+// ---- affine partial ----------------------------------------------------------------------------------------------------------------------
+struct Vec2 { double a, b; };
+
+// (a x - b y) + tx, (b x + a y) + ty for S = {a, b, tx, ty}
+__device__ inline Vec2 similarity_of(const double* __restrict__ S, double x, double y)
+{
+    return Vec2{__dadd_rn(__dsub_rn(__dmul_rn(S[0], x), __dmul_rn(S[1], y)), S[2]),
+                __dadd_rn(__dadd_rn(__dmul_rn(S[1], x), __dmul_rn(S[0], y)), S[3])};
+}
+
+// (u, v) - Tj^-1 p: Vj is a variant of camera j, whose inverse map is its second half
+__device__ inline Vec2 affine_residual_of(const double* __restrict__ Vj, const Vec2& p, double u, double v)
+{
+    const Vec2 q = similarity_of(Vj + 4, p.a, p.b);
+    return Vec2{__dsub_rn(u, q.a), __dsub_rn(v, q.b)};
+}
+
+__device__ inline double dot2(const Vec2& p, const Vec2& q) { return __dadd_rn(__dmul_rn(p.a, q.a), __dmul_rn(p.b, q.b)); }
+
+__global__ __launch_bounds__(RAY_WG) void affine_normal_equations_kernel(const int* __restrict__ edge_cams, const long long* __restrict__ offsets,
+                                                                         const double* __restrict__ pts, const double* __restrict__ variants,
+                                                                         double* __restrict__ out)
+{
+    __shared__ double fold[RAY_SUMS * (RAY_WG / 2)];
+    const int e = blockIdx.x, tid = threadIdx.x;
+    const double* __restrict__ Vi = variants + (size_t)edge_cams[2 * e] * 72;
+    const double* __restrict__ Vj = variants + (size_t)edge_cams[2 * e + 1] * 72;
+    const long long first = offsets[e], last = offsets[e + 1];
+    double acc[RAY_SUMS];
 #pragma unroll
-    for (int s = RAY_WG / 2; s >= 64; s >>= 1) {
-        if (tid >= s && tid < 2 * s) {
+    for (int a = 0; a < RAY_SUMS; a++) acc[a] = 0.0;
+    for (long long m = first + tid; m < last; m += RAY_WG) {
+        const double2 xy = *(const double2*)(pts + m * 4), uv = *(const double2*)(pts + m * 4 + 2);
+        const Vec2 P = similarity_of(Vi, xy.x, xy.y);
+        const Vec2 r = affine_residual_of(Vj, P, uv.x, uv.y);
+        acc[0] = __dadd_rn(acc[0], dot2(r, r));
+        Vec2 J[8];
 #pragma unroll
-            for (int a = 0; a < RAY_SUMS; a++) fold[a * (RAY_WG / 2) + (tid - s)] = acc[a];
+        for (int k = 0; k < 8; k++) {
+            Vec2 p, q;
+            if (k < 4) {
+                p = affine_residual_of(Vj, similarity_of(Vi + (1 + 2 * k) * 8, xy.x, xy.y), uv.x, uv.y);
+                q = affine_residual_of(Vj, similarity_of(Vi + (2 + 2 * k) * 8, xy.x, xy.y), uv.x, uv.y);
+            } else {
+                p = affine_residual_of(Vj + (1 + 2 * (k - 4)) * 8, P, uv.x, uv.y);
+                q = affine_residual_of(Vj + (2 + 2 * (k - 4)) * 8, P, uv.x, uv.y);
+            }
+            J[k] = Vec2{__dmul_rn(__dsub_rn(p.a, q.a), 500.0), __dmul_rn(__dsub_rn(p.b, q.b), 500.0)};
+            acc[1 + k] = __dadd_rn(acc[1 + k], dot2(J[k], r));
+#pragma unroll
+            for (int l = 0; l <= k; l++) acc[9 + tri_row(l) + (k - l)] = __dadd_rn(acc[9 + tri_row(l) + (k - l)], dot2(J[l], J[k]));
         }
-        __syncthreads();
-        if (tid < s) {
-#pragma unroll
-            for (int a = 0; a < RAY_SUMS; a++) acc[a] = __dadd_rn(acc[a], fold[a * (RAY_WG / 2) + tid]);
-        }
-        __syncthreads();
     }
-    if (tid >= 64) return;  // three whole wavefronts
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-#pragma unroll
-        for (int a = 0; a < RAY_SUMS; a++) acc[a] = __dadd_rn(acc[a], __shfl_down(acc[a], s, 64));  // lanes >= s: not used below
-    }
-    if (tid == 0) {
-#pragma unroll
-        for (int a = 0; a < RAY_SUMS; a++) out[(size_t)e * RAY_SUMS + a] = acc[a];
-    }
+    fold_lane_sums(acc, fold, tid, out + (size_t)e * RAY_SUMS);
 }
 
 }  // namespace
+
+int stx_launch_affine_normal_equations(stx_ctx* ctx, int n_edges, const int* d_edge_cams, const long long* d_offsets, const double* d_pts,
+                                       const double* d_variants, double* d_out, hipEvent_t start, hipEvent_t stop)
+{
+    StxProfScope prof(ctx, "affine_normal_equations", 0.0);
+    if (start) STX_HIP(hipEventRecord(start, ctx->stream));
+    hipLaunchKernelGGL(affine_normal_equations_kernel, dim3(n_edges), dim3(RAY_WG), 0, ctx->stream, d_edge_cams, d_offsets, d_pts, d_variants,
+                       d_out);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return stx_fail(STX_ERR_HIP, "affine_normal_equations launch failed: %s", hipGetErrorString(err));
+    if (stop) STX_HIP(hipEventRecord(stop, ctx->stream));
+    return STX_OK;
+}
 
 int stx_launch_ray_normal_equations(stx_ctx* ctx, int n_edges, const int* d_edge_cams, const long long* d_offsets, const double* d_pts,
                                     const double* d_variants, double* d_out, hipEvent_t start, hipEvent_t stop)

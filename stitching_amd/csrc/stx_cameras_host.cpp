@@ -47,26 +47,31 @@ STX_EXPORT int stx_ray_problem_create(stx_ctx* ctx, int n_edges, const int* edge
     return STX_OK;
 }
 
-STX_EXPORT int stx_ray_problem_eval(stx_ray_problem* P, int n_cams, const double* variants, double* out, double out_info[4])
+namespace {
+using NormalEquationsLaunch = int (*)(stx_ctx*, int, const int*, const long long*, const double*, const double*, double*, hipEvent_t, hipEvent_t);
+
+// one evaluation of either adjustment: a camera's 9 variants are `width` doubles each (at most 10: the problem's block holds 90 a camera)
+int problem_eval(stx_ray_problem* P, const char* what, int width, NormalEquationsLaunch launch, int n_cams, const double* variants, double* out,
+                 double out_info[4])
 {
+    const size_t per_cam = (size_t)width * 9;
     if (!P) return stx_fail(STX_ERR_INVALID, "problem is null");
     if (out_info) std::fill(out_info, out_info + 4, 0.0);
     if (n_cams < P->min_cams || n_cams > STX_RAY_MAX_CAMERAS)
-        return stx_fail(STX_ERR_INVALID, "ray adjustment of %d cameras: the edges name %d, the limit is %d", n_cams, P->min_cams, STX_RAY_MAX_CAMERAS);
+        return stx_fail(STX_ERR_INVALID, "%s adjustment of %d cameras: the edges name %d, the limit is %d", what, n_cams, P->min_cams, STX_RAY_MAX_CAMERAS);
     if (n_cams > 0 && !variants) return stx_fail(STX_ERR_INVALID, "null argument");
-    for (size_t k = 0; k < (size_t)n_cams * 90; k++)
+    for (size_t k = 0; k < (size_t)n_cams * per_cam; k++)
         if (!std::isfinite(variants[k]))
-            return stx_fail(STX_ERR_INVALID, "camera %zu: variant %zu is not finite", k / 90, (k % 90) / 10);
+            return stx_fail(STX_ERR_INVALID, "camera %zu: variant %zu is not finite", k / per_cam, (k % per_cam) / (size_t)width);
     if (out_info) { out_info[0] = P->n_edges; out_info[1] = (double)P->total; }
     if (P->n_edges == 0) return STX_OK;
     if (!out) return stx_fail(STX_ERR_INVALID, "null argument");
     stx_ctx* ctx = P->ctx;
     STX_TRY(stx_set_device(ctx));
     STX_HIP(hipEventRecord(P->ev[0], ctx->stream));
-    STX_HIP(hipMemcpyAsync(P->d_variants.get(), variants, (size_t)P->min_cams * 90 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    STX_TRY(stx_launch_ray_normal_equations(ctx, P->n_edges, (const int*)P->d_edge_cams.get(), (const long long*)P->d_offsets.get(),
-                                            (const double*)P->d_pts.get(), (const double*)P->d_variants.get(), (double*)P->d_out.get(),
-                                            P->ev[1], P->ev[2]));
+    STX_HIP(hipMemcpyAsync(P->d_variants.get(), variants, (size_t)P->min_cams * per_cam * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    STX_TRY(launch(ctx, P->n_edges, (const int*)P->d_edge_cams.get(), (const long long*)P->d_offsets.get(), (const double*)P->d_pts.get(),
+                   (const double*)P->d_variants.get(), (double*)P->d_out.get(), P->ev[1], P->ev[2]));
     STX_HIP(hipMemcpyAsync(out, P->d_out.get(), (size_t)P->n_edges * 45 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     STX_HIP(hipEventRecord(P->ev[3], ctx->stream));
     STX_HIP(hipStreamSynchronize(ctx->stream));  // the one wait
@@ -77,6 +82,17 @@ STX_EXPORT int stx_ray_problem_eval(stx_ray_problem* P, int n_cams, const double
         out_info[2] = a; out_info[3] = b;
     }
     return STX_OK;
+}
+}  // namespace
+
+STX_EXPORT int stx_ray_problem_eval(stx_ray_problem* P, int n_cams, const double* variants, double* out, double out_info[4])
+{
+    return problem_eval(P, "ray", 10, stx_launch_ray_normal_equations, n_cams, variants, out, out_info);
+}
+
+STX_EXPORT int stx_affine_problem_eval(stx_ray_problem* P, int n_cams, const double* variants, double* out, double out_info[4])
+{
+    return problem_eval(P, "affine", 8, stx_launch_affine_normal_equations, n_cams, variants, out, out_info);
 }
 
 STX_EXPORT int stx_ray_problem_free(stx_ray_problem* P)

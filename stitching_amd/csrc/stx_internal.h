@@ -353,10 +353,11 @@ int stx_launch_match_2nn(stx_ctx* ctx, const StxMatchJob* d_jobs, int njobs, int
                          double compares, bool lds);
 int stx_launch_match_union(stx_ctx* ctx, const StxMatchPair* d_pairs, int np, const uint2* d_nn, const double* d_pts, int ratio_T,
                            int* d_counts, int* d_matches, double* d_xyuv);
+// model: STX_MATCH_MODEL_* (checked by the caller), the hypothesis function of both kernels
 int stx_launch_match_ransac(stx_ctx* ctx, const StxMatchPair* d_pairs, int np, const int* d_counts, const double* d_xyuv, int iters,
-                            double threshold_sq, uint32_t seed, int* d_hyp);
+                            double threshold_sq, uint32_t seed, int model, int* d_hyp);
 int stx_launch_match_pick(stx_ctx* ctx, const StxMatchPair* d_pairs, int np, const int* d_counts, const double* d_xyuv, int iters,
-                          double threshold_sq, uint32_t seed, const int* d_hyp, int* d_pick, double* d_H, uint8_t* d_mask);
+                          double threshold_sq, uint32_t seed, int model, const int* d_hyp, int* d_pick, double* d_H, uint8_t* d_mask);
 // ray bundle adjustment (stx_cameras.hip; host side in stx_cameras_host.cpp) ---------------------------------------------------------
 // the edges of one adjustment, on the device for all its evaluations: cameras (i < j) per edge, the edges' first points (ascending,
 // first 0, n_edges + 1 entries), the points x, y, u, v; variants / out: the blocks every evaluation writes and reads
@@ -372,6 +373,9 @@ struct stx_ray_problem {
 // E, g[8], B upper triangle[36] of every edge -> d_out[45 n_edges]; start / stop (or null): recorded around the launch
 int stx_launch_ray_normal_equations(stx_ctx* ctx, int n_edges, const int* d_edge_cams, const long long* d_offsets, const double* d_pts,
                                     const double* d_variants, double* d_out, hipEvent_t start, hipEvent_t stop);
+// the same sums of the affine-partial residual; d_variants: 72 doubles per camera
+int stx_launch_affine_normal_equations(stx_ctx* ctx, int n_edges, const int* d_edge_cams, const long long* d_offsets, const double* d_pts,
+                                       const double* d_variants, double* d_out, hipEvent_t start, hipEvent_t stop);
 // cv::resize(INTER_LINEAR_EXACT) u8 (next rows N2 / N3); d_xt / d_yt: device tables of (offset, coeff1 | interior << 16)
 int stx_launch_resize_exact(stx_ctx* ctx, const stx_buf* src, stx_buf* dst, const int* d_xt, const int* d_yt, bool dilate,
                             const stx_buf* andmask);

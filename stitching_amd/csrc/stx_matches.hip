@@ -7,7 +7,9 @@
 //   match_union   one workgroup per pair i < j: ratio test, duplicate test, a block prefix sum that places the forward matches and then
 //                 the backward extras; writes the matches, their coordinates (x, y, u, v) and the count.
 //   match_ransac  one wavefront per hypothesis: the 4 indices and H are the same in every lane, the lanes stride over the pair's
-//                 matches, the count is ballot + popcount.
+//                 matches, the count is ballot + popcount.  The geometric model (STX_MATCH_MODEL_*) is a template parameter of this
+//                 kernel and the next: only the hypothesis differs — the homography of 4 matches, or for scans and flat tiles the
+//                 similarity of 2 or the affine map of 3 (tests/numpy_affine.py), homogeneous 3 x 3 all of them.
 //   match_pick    one workgroup per pair: arg-max of the counts (the smallest k among equals), H of that k once more, the inlier mask.
 // The fp64 arithmetic is IEEE multiplies, adds and subtractions in the contract's order: no FMA (the file is compiled with
 // -ffp-contract=off and says so itself below), no division, no libm, no MFMA.
@@ -148,11 +150,12 @@ __device__ inline uint32_t mix32(uint32_t x)
     return x;
 }
 
-// the 4 distinct match indices of hypothesis k of pair p with m >= 4 matches, in the order drawn: no rejection loop
-__device__ inline void match_sample(uint32_t seed, uint32_t p, uint32_t k, int m, int out[4])
+// the first S <= 4 distinct match indices of hypothesis k of pair p with m >= 4 matches, in the order drawn: no rejection loop
+template <int S>
+__device__ inline void match_sample(uint32_t seed, uint32_t p, uint32_t k, int m, int out[S])
 {
-    int s[4];  // the choices so far, ascending
-    for (int t = 0; t < 4; t++) {
+    int s[S];  // the choices so far, ascending
+    for (int t = 0; t < S; t++) {
         int r = (int)(mix32(seed ^ mix32(p * 0x9E3779B9u + mix32(4u * k + (uint32_t)t + 1u))) % (uint32_t)(m - t));
         for (int c = 0; c < t; c++)
             if (r >= s[c]) r++;
@@ -186,11 +189,61 @@ __device__ inline void basis3(const double* x, const double* y, double* A)
     }
 }
 
+// the similarity (x, y) -> (u, v) of 2 sampled matches, times W = |p1 - p0|^2: H = [A, -B, C, B, A, D, 0, 0, W]
+__device__ inline void affine_partial_form(const double* x, const double* y, const double* u, const double* v, double* H)
+{
+    const double dx = __dsub_rn(x[1], x[0]), dy = __dsub_rn(y[1], y[0]), du = __dsub_rn(u[1], u[0]), dv = __dsub_rn(v[1], v[0]);
+    const double W = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
+    const double A = __dadd_rn(__dmul_rn(du, dx), __dmul_rn(dv, dy));
+    const double B = __dsub_rn(__dmul_rn(dv, dx), __dmul_rn(du, dy));
+    H[0] = A; H[1] = -B; H[2] = __dsub_rn(__dmul_rn(u[0], W), __dsub_rn(__dmul_rn(A, x[0]), __dmul_rn(B, y[0])));
+    H[3] = B; H[4] = A; H[5] = __dsub_rn(__dmul_rn(v[0], W), __dadd_rn(__dmul_rn(B, x[0]), __dmul_rn(A, y[0])));
+    H[6] = 0.0; H[7] = 0.0; H[8] = W;
+}
+
+// the affine map of 3 sampled matches, times det M: rows 0 and 1 of N adj(M), M the source points as homogeneous columns
+__device__ inline void affine_full_form(const double* x, const double* y, const double* u, const double* v, double* H)
+{
+    const double m[9] = {x[0], x[1], x[2], y[0], y[1], y[2], 1.0, 1.0, 1.0};
+    double a[9];
+    adj3(m, a);
+    for (int cc = 0; cc < 3; cc++) {
+        H[cc] = sum3(__dmul_rn(u[0], a[cc]), __dmul_rn(u[1], a[3 + cc]), __dmul_rn(u[2], a[6 + cc]));
+        H[3 + cc] = sum3(__dmul_rn(v[0], a[cc]), __dmul_rn(v[1], a[3 + cc]), __dmul_rn(v[2], a[6 + cc]));
+    }
+    H[6] = 0.0; H[7] = 0.0; H[8] = sum3(__dmul_rn(x[0], a[0]), __dmul_rn(x[1], a[3]), __dmul_rn(x[2], a[6]));
+}
+
+// H of hypothesis k of an affine model with the sign rule applied (h6 = h7 = +0.0 stay); false: h8 == 0 (coincident or collinear
+// sample points), the hypothesis has no inliers
+template <int MODEL>
+__device__ inline bool affine_hypothesis(const double* __restrict__ c, int m, uint32_t seed, uint32_t p, uint32_t k, double* H)
+{
+    constexpr int S = MODEL == STX_MATCH_MODEL_AFFINE_PARTIAL ? 2 : 3;
+    int idx[S];
+    match_sample<S>(seed, p, k, m, idx);
+    double x[S], y[S], u[S], v[S];
+    for (int t = 0; t < S; t++) {
+        const double2 a = *(const double2*)(c + (size_t)idx[t] * 4), b = *(const double2*)(c + (size_t)idx[t] * 4 + 2);
+        x[t] = a.x; y[t] = a.y; u[t] = b.x; v[t] = b.y;
+    }
+    if (MODEL == STX_MATCH_MODEL_AFFINE_PARTIAL) affine_partial_form(x, y, u, v, H);
+    else affine_full_form(x, y, u, v, H);
+    const double w = H[8];
+    if (w < 0.0) {
+        for (int i = 0; i < 6; i++) H[i] = -H[i];
+        H[8] = -w;
+    }
+    return w != 0.0;
+}
+
 // H of hypothesis k with the sign rule applied; false: W at sample point 0 is 0, the hypothesis has no inliers
+template <int MODEL>
 __device__ inline bool match_hypothesis(const double* __restrict__ c, int m, uint32_t seed, uint32_t p, uint32_t k, double* H)
 {
+    if (MODEL != STX_MATCH_MODEL_HOMOGRAPHY) return affine_hypothesis<MODEL>(c, m, seed, p, k, H);
     int idx[4];
-    match_sample(seed, p, k, m, idx);
+    match_sample<4>(seed, p, k, m, idx);
     double x[4], y[4], u[4], v[4];
     for (int t = 0; t < 4; t++) {
         const double2 a = *(const double2*)(c + (size_t)idx[t] * 4), b = *(const double2*)(c + (size_t)idx[t] * 4 + 2);
@@ -220,6 +273,7 @@ __device__ inline bool match_inlier(const double* H, const double* __restrict__ 
 }
 
 // grid: pair * hb + block of STX_MATCH_HYP_PER_WG hypotheses, hb = ceil(iters / STX_MATCH_HYP_PER_WG)
+template <int MODEL>
 __global__ __launch_bounds__(64 * STX_MATCH_HYP_PER_WG) void match_ransac_kernel(const StxMatchPair* __restrict__ pairs,
                                                                                  const int* __restrict__ counts,
                                                                                  const double* __restrict__ xyuv, int iters, int hb,
@@ -235,7 +289,7 @@ __global__ __launch_bounds__(64 * STX_MATCH_HYP_PER_WG) void match_ransac_kernel
     const double* c = xyuv + P.out_off * 4;
     double H[9];
     int n = 0;
-    if (match_hypothesis(c, m, seed, (uint32_t)P.p, (uint32_t)k, H)) {
+    if (match_hypothesis<MODEL>(c, m, seed, (uint32_t)P.p, (uint32_t)k, H)) {
         for (int e0 = 0; e0 < m; e0 += 64) {
             const int e = e0 + lane;
             n += __popcll(__ballot(e < m && match_inlier(H, c, e, t2)));
@@ -244,6 +298,7 @@ __global__ __launch_bounds__(64 * STX_MATCH_HYP_PER_WG) void match_ransac_kernel
     if (lane == 0) hyp[(size_t)pi * iters + k] = n;
 }
 
+template <int MODEL>
 __global__ __launch_bounds__(256) void match_pick_kernel(const StxMatchPair* __restrict__ pairs, const int* __restrict__ counts,
                                                          const double* __restrict__ xyuv, int iters, double t2, uint32_t seed,
                                                          const int* __restrict__ hyp, int* __restrict__ pick, double* __restrict__ Hs,
@@ -275,7 +330,7 @@ __global__ __launch_bounds__(256) void match_pick_kernel(const StxMatchPair* __r
     const int k = s_k[0];
     const double* c = xyuv + P.out_off * 4;
     double H[9];
-    const bool ok = match_hypothesis(c, m, seed, (uint32_t)P.p, (uint32_t)k, H);
+    const bool ok = match_hypothesis<MODEL>(c, m, seed, (uint32_t)P.p, (uint32_t)k, H);
     for (int e = tid; e < m; e += 256) mask[P.out_off + e] = ok && match_inlier(H, c, e, t2) ? 1 : 0;
     if (tid == 0) {
         pick[2 * pi] = s_n[0]; pick[2 * pi + 1] = k;
@@ -304,20 +359,49 @@ int stx_launch_match_union(stx_ctx* ctx, const StxMatchPair* d_pairs, int np, co
 }
 
 int stx_launch_match_ransac(stx_ctx* ctx, const StxMatchPair* d_pairs, int np, const int* d_counts, const double* d_xyuv, int iters,
-                            double threshold_sq, uint32_t seed, int* d_hyp)
+                            double threshold_sq, uint32_t seed, int model, int* d_hyp)
 {
     const int hb = (iters + STX_MATCH_HYP_PER_WG - 1) / STX_MATCH_HYP_PER_WG;
     StxProfScope prof(ctx, "match_ransac", 0.0);
-    hipLaunchKernelGGL(match_ransac_kernel, dim3((unsigned)np * (unsigned)hb), dim3(64 * STX_MATCH_HYP_PER_WG), 0, ctx->stream, d_pairs,
-                       d_counts, d_xyuv, iters, hb, threshold_sq, seed, d_hyp);
+    const dim3 grid((unsigned)np * (unsigned)hb), wg(64 * STX_MATCH_HYP_PER_WG);
+    switch (model) {
+    case STX_MATCH_MODEL_HOMOGRAPHY:
+        hipLaunchKernelGGL(match_ransac_kernel<STX_MATCH_MODEL_HOMOGRAPHY>, grid, wg, 0, ctx->stream, d_pairs, d_counts, d_xyuv, iters, hb,
+                           threshold_sq, seed, d_hyp);
+        break;
+    case STX_MATCH_MODEL_AFFINE_PARTIAL:
+        hipLaunchKernelGGL(match_ransac_kernel<STX_MATCH_MODEL_AFFINE_PARTIAL>, grid, wg, 0, ctx->stream, d_pairs, d_counts, d_xyuv, iters, hb,
+                           threshold_sq, seed, d_hyp);
+        break;
+    case STX_MATCH_MODEL_AFFINE_FULL:
+        hipLaunchKernelGGL(match_ransac_kernel<STX_MATCH_MODEL_AFFINE_FULL>, grid, wg, 0, ctx->stream, d_pairs, d_counts, d_xyuv, iters, hb,
+                           threshold_sq, seed, d_hyp);
+        break;
+    default:
+        return stx_fail(STX_ERR_INVALID, "unknown match model %d", model);
+    }
     return match_check_launch("match_ransac");
 }
 
 int stx_launch_match_pick(stx_ctx* ctx, const StxMatchPair* d_pairs, int np, const int* d_counts, const double* d_xyuv, int iters,
-                          double threshold_sq, uint32_t seed, const int* d_hyp, int* d_pick, double* d_H, uint8_t* d_mask)
+                          double threshold_sq, uint32_t seed, int model, const int* d_hyp, int* d_pick, double* d_H, uint8_t* d_mask)
 {
     StxProfScope prof(ctx, "match_pick", 0.0);
-    hipLaunchKernelGGL(match_pick_kernel, dim3(np), dim3(256), 0, ctx->stream, d_pairs, d_counts, d_xyuv, iters, threshold_sq, seed, d_hyp,
-                       d_pick, d_H, d_mask);
+    switch (model) {
+    case STX_MATCH_MODEL_HOMOGRAPHY:
+        hipLaunchKernelGGL(match_pick_kernel<STX_MATCH_MODEL_HOMOGRAPHY>, dim3(np), dim3(256), 0, ctx->stream, d_pairs, d_counts, d_xyuv, iters,
+                           threshold_sq, seed, d_hyp, d_pick, d_H, d_mask);
+        break;
+    case STX_MATCH_MODEL_AFFINE_PARTIAL:
+        hipLaunchKernelGGL(match_pick_kernel<STX_MATCH_MODEL_AFFINE_PARTIAL>, dim3(np), dim3(256), 0, ctx->stream, d_pairs, d_counts, d_xyuv,
+                           iters, threshold_sq, seed, d_hyp, d_pick, d_H, d_mask);
+        break;
+    case STX_MATCH_MODEL_AFFINE_FULL:
+        hipLaunchKernelGGL(match_pick_kernel<STX_MATCH_MODEL_AFFINE_FULL>, dim3(np), dim3(256), 0, ctx->stream, d_pairs, d_counts, d_xyuv, iters,
+                           threshold_sq, seed, d_hyp, d_pick, d_H, d_mask);
+        break;
+    default:
+        return stx_fail(STX_ERR_INVALID, "unknown match model %d", model);
+    }
     return match_check_launch("match_pick");
 }

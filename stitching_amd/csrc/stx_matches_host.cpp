@@ -26,7 +26,18 @@ STX_EXPORT int stx_match_features(stx_ctx* ctx, int n, const unsigned char* cons
                                   int* out_counts, int* out_matches, unsigned char* out_mask, int* out_pick, double* out_H,
                                   double out_info[4])
 {
+    return stx_match_features_model(ctx, n, desc, desc_shape, pts, pts_rows, ratio_T, range_width, ransac_iters, threshold_sq, seed,
+                                    STX_MATCH_MODEL_HOMOGRAPHY, out_counts, out_matches, out_mask, out_pick, out_H, out_info);
+}
+
+STX_EXPORT int stx_match_features_model(stx_ctx* ctx, int n, const unsigned char* const* desc, const int* desc_shape,
+                                        const double* const* pts, const int* pts_rows, int ratio_T, int range_width, int ransac_iters,
+                                        double threshold_sq, unsigned seed, int model, int* out_counts, int* out_matches,
+                                        unsigned char* out_mask, int* out_pick, double* out_H, double out_info[4])
+{
     if (!ctx) return stx_fail(STX_ERR_INVALID, "ctx is null");
+    if (model != STX_MATCH_MODEL_HOMOGRAPHY && model != STX_MATCH_MODEL_AFFINE_PARTIAL && model != STX_MATCH_MODEL_AFFINE_FULL)
+        return stx_fail(STX_ERR_INVALID, "feature matching with the model %d: homography (0), affine partial (1) or affine full (2)", model);
     if (n < 0 || (n > 0 && (!desc || !desc_shape || !pts || !pts_rows))) return stx_fail(STX_ERR_INVALID, "bad argument");
     if (ransac_iters < 1 || ransac_iters > STX_MATCH_MAX_ITERS)
         return stx_fail(STX_ERR_INVALID, "feature matching with %d RANSAC hypotheses: 1 .. %d", ransac_iters, STX_MATCH_MAX_ITERS);
@@ -116,9 +127,9 @@ STX_EXPORT int stx_match_features(stx_ctx* ctx, int n, const unsigned char* cons
     STX_TRY(stx_launch_match_union(ctx, (const StxMatchPair*)d_pairs.get(), (int)np, (const uint2*)d_nn.get(), (const double*)d_pts.get(), ratio_T,
                                    (int*)d_counts.get(), (int*)d_matches.get(), (double*)d_xyuv.get()));
     STX_TRY(stx_launch_match_ransac(ctx, (const StxMatchPair*)d_pairs.get(), (int)np, (const int*)d_counts.get(), (const double*)d_xyuv.get(),
-                                    ransac_iters, threshold_sq, seed, (int*)d_hyp.get()));
+                                    ransac_iters, threshold_sq, seed, model, (int*)d_hyp.get()));
     STX_TRY(stx_launch_match_pick(ctx, (const StxMatchPair*)d_pairs.get(), (int)np, (const int*)d_counts.get(), (const double*)d_xyuv.get(),
-                                  ransac_iters, threshold_sq, seed, (const int*)d_hyp.get(), (int*)d_pick.get(), (double*)d_H.get(),
+                                  ransac_iters, threshold_sq, seed, model, (const int*)d_hyp.get(), (int*)d_pick.get(), (double*)d_H.get(),
                                   (uint8_t*)d_mask.get()));
     if (out_info) STX_HIP(hipEventRecord(X.ev[2], ctx->stream));
     STX_HIP(hipMemcpyAsync(out_counts, d_counts.get(), np * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));

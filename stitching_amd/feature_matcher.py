@@ -2,8 +2,8 @@
 
 Without `estimator=` it is the reference's class: the name picks cv.detail's BestOf2Nearest / BestOf2NearestRange / AffineBestOf2Nearest
 matcher — OpenCV's, on the host.  With `estimator=MatchEstimator()` the features go to the device matcher.  That matcher is the
-project's own and answers to no name here: "homography" stays cv2's, and "affine" has no device counterpart at all.  The numpy helpers
-need no cv2; the drawing helpers do.
+project's own and answers to no name here: "homography" stays cv2's, and "affine" goes with an estimator only where that estimator's own
+`model` is an affine one (MatchEstimator(model="affine")).  The numpy helpers need no cv2; the drawing helpers do.
 """
 import math
 
@@ -30,12 +30,12 @@ class FeatureMatcher:
 
     def __init__(self, matcher_type=DEFAULT_MATCHER, range_width=DEFAULT_RANGE_WIDTH, estimator=None, **kwargs):
         """`estimator`: any object with match(features) -> n * n match objects, row-major (a MatchEstimator, which carries its own
-        range_width and match_conf); the name is then looked at only to refuse "affine", for which no model is built here.  Default:
-        the cv2 matcher the reference builds for the name."""
+        range_width and match_conf); the name is then looked at only to refuse "affine" with an estimator whose `model` is not an affine
+        one.  Default: the cv2 matcher the reference builds for the name."""
         self.estimator = estimator
         self.matcher = None
         if estimator is not None:
-            if matcher_type == "affine":
+            if matcher_type == "affine" and not str(getattr(estimator, "model", "homography")).startswith("affine"):
                 raise StitchingError('the "affine" matcher has no device estimator: only a homography is fitted there')
             if kwargs:
                 raise StitchingError(f"a match estimator takes its settings at construction, got {sorted(kwargs)}")

@@ -8,6 +8,10 @@ every integer array and in the float64 bits of the winning sample homography; DE
 What is small and needs float64 with a library behind it is computed here on the host, as the exposure solver does for its small
 system: the integer ratio threshold, the centred level-0 coordinates, the refit of the winning hypothesis over its inliers (Hartley
 normalised DLT, SVD), the confidence and the mirrored entries.
+
+With model="affine" the RANSAC fits a similarity (2 matches a sample) or, with full_affine=True, an affine map (3) on points that are not
+centred — the registration of scans and flat tiles, whose cameras the affine warper applies to raw pixels.  Everything but the hypothesis
+and the refit is shared with the homography; tests/numpy_affine.py is that contract and DESIGN.md section 18 the description.
 """
 import ctypes as C
 import math
@@ -41,6 +45,20 @@ def centred_points(features):
     return out
 
 
+def level0_points(features):
+    """(n, 2) float64: the keypoints of one ImageFeatures in level-0 pixels, not centred (the affine models' frame):
+    x0 = (x + 0.5) * w0 / wl - 0.5 in this order of operations, y alike."""
+    n = len(features.level)
+    out = np.zeros((n, 2), np.float64)
+    if n == 0:
+        return out
+    w0, h0 = features.img_size
+    sizes = np.asarray(features.level_sizes, np.float64).reshape(-1, 2)[np.asarray(features.level, np.int64)]
+    out[:, 0] = (np.asarray(features.x, np.float64) + 0.5) * float(w0) / sizes[:, 0] - 0.5
+    out[:, 1] = (np.asarray(features.y, np.float64) + 0.5) * float(h0) / sizes[:, 1] - 0.5
+    return out
+
+
 def _hartley(p):
     c = p.mean(axis=0)
     d = np.sqrt(((p - c) ** 2).sum(axis=1)).mean()
@@ -61,6 +79,24 @@ def refit_homography(src, dst):
     h = np.linalg.svd(a)[2][-1].reshape(3, 3)
     h = np.linalg.inv(td) @ h @ ts
     return h / h[2, 2]
+
+
+def refit_affine(src, dst, full=False):
+    """(3, 3) float64 with the last row 0, 0, 1: the least-squares similarity (full=False: closed form about the two centroids) or
+    affine map (full=True: lstsq on the centred points) of k correspondences src -> dst ((k, 2) each)."""
+    src, dst = np.asarray(src, np.float64), np.asarray(dst, np.float64)
+    cp, cq = src.mean(axis=0), dst.mean(axis=0)
+    if full:
+        sol = np.linalg.lstsq(np.concatenate([src - cp, np.ones((len(src), 1))], axis=1), dst - cq, rcond=None)[0]
+        linear, cq = sol[0:2].T, cq + sol[2]
+    else:
+        dx, dy = (src - cp).T
+        du, dv = (dst - cq).T
+        d = (dx * dx + dy * dy).sum()
+        a, b = (dx * du + dy * dv).sum() / d, (dx * dv - dy * du).sum() / d
+        linear = np.array([[a, -b], [b, a]])
+    t = cq - linear @ cp
+    return np.array([[linear[0, 0], linear[0, 1], t[0]], [linear[1, 0], linear[1, 1], t[1]], [0.0, 0.0, 1.0]])
 
 
 def finite_inverse(h):
@@ -129,12 +165,21 @@ class MatchEstimator:
 
     Plug it in where a matcher goes: FeatureMatcher(estimator=MatchEstimator()).
 
+    model: "homography" (the default), or "affine" for scans and flat tiles — a similarity of 2 matches ("affine_partial", as OpenCV's
+    full_affine=False default), or with full_affine=True an affine map of 3 ("affine_full"); `model` reads back the resolved name.  The
+    affine models work on points that are not centred and refit by least squares; tests/numpy_affine.py is their contract
+    (FeatureMatcher("affine", estimator=MatchEstimator(model="affine"))).
+
     Limits, refused with a StitchingError before anything is launched: at most MAX_FEATURES features in an image, ransac_iters in
     1 .. MAX_ITERS, descriptors of shape (n, 32) u8, as many keypoints as descriptors."""
 
     MAX_FEATURES, MAX_ITERS = _lib.MATCH_MAX_FEATURES, _lib.MATCH_MAX_ITERS
 
-    def __init__(self, match_conf=0.3, range_width=-1, ransac_iters=500, ransac_threshold=3.0, seed=0x5EED):
+    def __init__(self, match_conf=0.3, range_width=-1, ransac_iters=500, ransac_threshold=3.0, seed=0x5EED, model="homography",
+                 full_affine=False):
+        if model not in ("homography", "affine"):
+            raise StitchingError(f'unknown match model {model!r}: "homography", or "affine" (a similarity; with full_affine=True an affine map)')
+        self.model = model if model == "homography" else "affine_full" if full_affine else "affine_partial"
         if not 0.0 <= float(match_conf) <= 1.0:
             raise StitchingError(f"feature matching needs a match_conf in 0 .. 1, got {match_conf}")
         if not 0.0 <= float(ransac_threshold) <= 1e6:
@@ -157,7 +202,7 @@ class MatchEstimator:
             d = np.ascontiguousarray(f.descriptors)
             if d.ndim != 2:
                 raise StitchingError(f"image {i}: descriptors of shape {d.shape}: feature matching needs n x 32 u8")
-            p = np.ascontiguousarray(centred_points(f))
+            p = np.ascontiguousarray(centred_points(f) if self.model == "homography" else level0_points(f))
             shape[i] = (d.shape[0], d.shape[1], d.dtype.itemsize)
             rows[i] = len(p)
             desc.append(d)
@@ -172,10 +217,14 @@ class MatchEstimator:
         da = (C.c_void_p * n)(*[d.ctypes.data for d in desc])
         pa = (C.c_void_p * n)(*[p.ctypes.data for p in pts])
         t = self.ransac_threshold
-        _lib.check(ctx._lib.stx_match_features(
-            ctx.handle, n, da, shape.ctypes.data_as(ip), pa, rows.ctypes.data_as(ip), ratio_threshold(self.match_conf), self.range_width,
-            self.ransac_iters, t * t, self.seed, counts.ctypes.data_as(ip), matches.ctypes.data_as(ip),
-            mask.ctypes.data_as(C.POINTER(C.c_ubyte)), pick.ctypes.data_as(ip), Hs.ctypes.data_as(dp), info.ctypes.data_as(dp)))
+        front = (ctx.handle, n, da, shape.ctypes.data_as(ip), pa, rows.ctypes.data_as(ip), ratio_threshold(self.match_conf), self.range_width,
+                 self.ransac_iters, t * t, self.seed)
+        back = (counts.ctypes.data_as(ip), matches.ctypes.data_as(ip), mask.ctypes.data_as(C.POINTER(C.c_ubyte)), pick.ctypes.data_as(ip),
+                Hs.ctypes.data_as(dp), info.ctypes.data_as(dp))
+        if self.model == "homography":
+            _lib.check(ctx._lib.stx_match_features(*front, *back))
+        else:
+            _lib.check(ctx._lib.stx_match_features_model(*front, _lib.MATCH_MODELS[self.model], *back))
         self.info = {"pairs": int(info[0]), "matches": int(info[1]), "device_ms": float(info[2]), "device_ms_with_copy": float(info[3])}
         slot = 0
         for k, (i, j) in enumerate(pairs):
@@ -186,7 +235,8 @@ class MatchEstimator:
                 if int(pick[k, 0]) >= MIN_MATCHES:
                     keep = mask[slot:slot + m] != 0
                     with np.errstate(all="ignore"):
-                        h = refit_homography(pts[i][e.matches[keep, 0]], pts[j][e.matches[keep, 1]])
+                        src, dst = pts[i][e.matches[keep, 0]], pts[j][e.matches[keep, 1]]
+                        h = refit_homography(src, dst) if self.model == "homography" else refit_affine(src, dst, self.model == "affine_full")
                     if finite_inverse(h) is not None:
                         e.inliers_mask, e.num_inliers, e.H = mask[slot:slot + m].copy(), int(pick[k, 0]), h
                         e.confidence = match_confidence(e.num_inliers, m)

@@ -8,6 +8,7 @@ builds and the final gather are enqueued on one HIP stream; the only host syncs 
 ROI read-back at the start and whatever the caller does with the result.
 """
 import ctypes as C
+import warnings
 
 import numpy as np
 
@@ -19,7 +20,7 @@ from .exposure_error_compensator import ExposureErrorCompensator
 from .images import Images
 from .seam_estimation import SeamEstimator
 from .seam_finder import DEVICE_SEAM_FINDERS, SeamFinder
-from .stitching_error import StitchingError
+from .stitching_error import StitchingError, StitchingWarning
 from .synthetic import blend_strength_for_bands
 from .warper import Warper, WarpTables
 
@@ -485,6 +486,8 @@ class Composer:
         "blend_strength": Blender.DEFAULT_BLEND_STRENGTH,
     }
 
+    REGISTRATION_MODELS = ("homography", "rotation")  # of the MatchEstimator and the CameraSolver that stitch() makes where none is given
+
     def __init__(self, ctx=None, seam_estimator=None, **kwargs):
         """seam_estimator (not a setting): a finder object with find(imgs, corners, masks), e.g. a ColorSeamEstimator — `prepare` then finds
         its seams with it whatever "finder" names, and never looks for cv2."""
@@ -596,8 +599,8 @@ class Composer:
         if len(frames) < 2:
             raise StitchingError("stitching needs at least two images")
         feature_estimator = feature_estimator or FeatureEstimator()
-        match_estimator = match_estimator or MatchEstimator()
-        camera_solver = camera_solver or CameraSolver()
+        match_estimator = match_estimator or MatchEstimator(model=self.REGISTRATION_MODELS[0])
+        camera_solver = camera_solver or CameraSolver(model=self.REGISTRATION_MODELS[1])
         imgs_obj = Images.of(frames, st["medium_megapix"], st["low_megapix"], st["final_megapix"])
         prev = config.device_resident()
         config.set_device_resident(True)
@@ -610,6 +613,26 @@ class Composer:
         indices, cameras = camera_solver.register(features, matches, ctx=ctx)
         self.registration = {"indices": list(indices), "cameras": cameras, "info": camera_solver.info}
         return self.compose([frames[i] for i in indices], cameras)
+
+
+class AffineComposer(Composer):
+    """Composer for scans and flat tiles, as the reference's AffineStitcher is its Stitcher (stitching/stitcher.py:267-287): the affine
+    warper and no exposure compensation by default, and `stitch` registers with the affine models of the project's own estimators —
+    MatchEstimator(model="affine") and CameraSolver(model="affine"), whose cameras carry the 3 x 3 map from image pixels to the panorama
+    plane in R (focal = 1, ppx = ppy = 0), with no wave correction.  DESIGN.md section 18."""
+
+    # the reference's AFFINE_DEFAULTS that are settings of Composer (its matcher, estimator, adjuster and wave correction are
+    # REGISTRATION_MODELS here)
+    AFFINE_DEFAULTS = {"warper_type": "affine", "compensator": "no"}
+    DEFAULT_SETTINGS = dict(Composer.DEFAULT_SETTINGS, **AFFINE_DEFAULTS)
+    REGISTRATION_MODELS = ("affine", "affine")
+
+    def __init__(self, ctx=None, seam_estimator=None, **kwargs):
+        for key, value in kwargs.items():
+            if key in self.AFFINE_DEFAULTS and value != self.AFFINE_DEFAULTS[key]:
+                warnings.warn(f"You are overwriting an affine default ({key}={self.AFFINE_DEFAULTS[key]}) with another value ({value}). "
+                              "Make sure this is intended", StitchingWarning)
+        super().__init__(ctx=ctx, seam_estimator=seam_estimator, **kwargs)
 
 
 def stitch(frames, cameras, **kw):

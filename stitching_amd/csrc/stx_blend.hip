@@ -771,13 +771,6 @@ STX_DEV int wave_excl_prefix_min(int v)
     return __builtin_amdgcn_update_dpp(ID, v, 0x138, 0xf, 0xf, false);       // wave_shr:1
 }
 
-int check_launch(const char* what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return stx_fail(STX_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
-    return STX_OK;
-}
-
 inline dim3 grid64x4(int w, int h) { return dim3((w + 63) / 64, (h + 3) / 4); }
 
 }  // namespace
@@ -821,7 +814,7 @@ int stx_launch_mb_pyramids(stx_ctx* ctx, const StxMbImage* d_images, const StxMb
                 hipLaunchKernelGGL(mb_down_kernel, grid64x4(ow, oh), dim3(256), 0, ctx->stream, im, lv, pyr_mode, pyr_lanes);
             }
         }
-        STX_TRY(check_launch("mb_down"));
+        STX_TRY(stx_check_launch("mb_down"));
     }
     return STX_OK;
 }
@@ -840,7 +833,7 @@ int stx_launch_mb_coarse(stx_ctx* ctx, const MbLevelK& K, double algo_bytes)
     C.pw = K.pw; C.ph = K.ph;
     const dim3 grid((K.x1 - K.x0 + CO_TW - 1) / CO_TW, (K.y1 + CO_TH - 1) / CO_TH);
     hipLaunchKernelGGL(mb_coarse_kernel, grid, dim3(256), 0, ctx->stream, C);
-    return check_launch("mb_coarse");
+    return stx_check_launch("mb_coarse");
 }
 
 int stx_launch_mb_level(stx_ctx* ctx, const MbLevelK& K, double algo_bytes)
@@ -853,7 +846,7 @@ int stx_launch_mb_level(stx_ctx* ctx, const MbLevelK& K, double algo_bytes)
     const dim3 grid = grid64x4(K.x1 - K.x0, K.y1 - K.y0);
     if (K.level == 0) hipLaunchKernelGGL(mb_level_kernel<true>, grid, dim3(256), 0, ctx->stream, K);
     else hipLaunchKernelGGL(mb_level_kernel<false>, grid, dim3(256), 0, ctx->stream, K);
-    return check_launch("mb_level");
+    return stx_check_launch("mb_level");
 }
 
 int stx_launch_mb_emit_batch(stx_ctx* ctx, const MbLevelK* d_Ks, const MbLevelK* h_Ks, const int* classes, int n, double bytes)
@@ -866,7 +859,7 @@ int stx_launch_mb_emit_batch(stx_ctx* ctx, const MbLevelK* d_Ks, const MbLevelK*
         while (end < n && classes[end] == classes[start]) end++;
         const int cls = classes[start], count = end - start;
         if (cls >= 0) {
-            if (!stx_fast_mb_emit_launch(ctx, cls, d_Ks + start, h_Ks + start, count)) return check_launch("mb_contrib");
+            if (!stx_fast_mb_emit_launch(ctx, cls, d_Ks + start, h_Ks + start, count)) return stx_check_launch("mb_contrib");
         } else {
             int gx = 1, gy = 1;
             for (int i = start; i < end; i++) {
@@ -879,7 +872,7 @@ int stx_launch_mb_emit_batch(stx_ctx* ctx, const MbLevelK* d_Ks, const MbLevelK*
         }
         start = end;
     }
-    return check_launch("mb_contrib");
+    return stx_check_launch("mb_contrib");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1231,7 +1224,7 @@ int stx_launch_feather_weights(stx_ctx* ctx, const FeatherImg* d_imgs, const Fea
         hipLaunchKernelGGL(dt_rows_batch_kernel, dim3((max_h + rows - 1) / rows, n), dim3(256), (size_t)lds_pitch * 16 * rows, ctx->stream,
                            d_imgs, rows, lds_pitch);
     }
-    return check_launch("feather_weights");
+    return stx_check_launch("feather_weights");
 }
 
 int stx_launch_feather_gather(stx_ctx* ctx, const FeatherGatherK& K, double algo_bytes)
@@ -1240,7 +1233,7 @@ int stx_launch_feather_gather(stx_ctx* ctx, const FeatherGatherK& K, double algo
     const dim3 grid((K.w + 255) / 256, (K.h + 3) / 4);
     if (K.pano16) hipLaunchKernelGGL(feather_gather_kernel<true>, grid, dim3(256), 0, ctx->stream, K);
     else hipLaunchKernelGGL(feather_gather_kernel<false>, grid, dim3(256), 0, ctx->stream, K);
-    return check_launch("feather_gather");
+    return stx_check_launch("feather_gather");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1346,834 +1339,5 @@ int stx_launch_no_gather(stx_ctx* ctx, const NoGatherK& K, double algo_bytes)
     const dim3 grid((K.w + 255) / 256, (K.h + 3) / 4);
     if (K.pano16) hipLaunchKernelGGL(no_gather_kernel<true>, grid, dim3(256), 0, ctx->stream, K);
     else hipLaunchKernelGGL(no_gather_kernel<false>, grid, dim3(256), 0, ctx->stream, K);
-    return check_launch("no_gather");
-}
-
-// ---------------------------------------------------------------------------------------------
-// "next" rows of the scope table: consumers / producers either side of the path
-// ---------------------------------------------------------------------------------------------
-namespace {
-// GainCompensator::apply / ChannelsCompensator::apply: cv::multiply(u8x3 image, double scalar) evaluates in fp32
-// (arithm_op demotes a CV_64F scalar to CV_32F for 8-bit sources) and stores saturate_cast<uchar>(float) = cvRound + clamp
-struct GainK { uint8_t* img; long long stride; int w, h; float g[3]; };
-__global__ __launch_bounds__(256) void gain_apply_kernel(GainK P)
-{
-    const int x4 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;  // 4 pixels = 12 bytes = 3 dwords per lane
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x4 >= P.w || y >= P.h) return;
-    uint8_t* row = P.img + (long long)y * P.stride;
-    if (x4 + 4 <= P.w) {
-        uint32_t* q = reinterpret_cast<uint32_t*>(row + (long long)x4 * 3);
-        uint32_t d[3] = {q[0], q[1], q[2]}, o[3] = {0, 0, 0};
-#pragma unroll
-        for (int b = 0; b < 12; b++) {
-            const float v = stxd::fmul((float)((d[b >> 2] >> (8 * (b & 3))) & 255u), P.g[b % 3]);
-            const int r = min(max(stxd::cv_round(v), 0), 255);
-            o[b >> 2] |= (uint32_t)r << (8 * (b & 3));
-        }
-        q[0] = o[0]; q[1] = o[1]; q[2] = o[2];
-    } else {
-        for (int x = x4; x < P.w; x++)
-            for (int c = 0; c < 3; c++) {
-                const float v = stxd::fmul((float)row[x * 3 + c], P.g[c]);
-                row[x * 3 + c] = (uint8_t)min(max(stxd::cv_round(v), 0), 255);
-            }
-    }
-}
-}  // namespace
-
-int stx_launch_gain_apply(stx_ctx* ctx, stx_buf* img, const float g[3])
-{
-    GainK K;
-    K.img = img->ptr; K.stride = (long long)img->stride; K.w = img->w; K.h = img->h;
-    K.g[0] = g[0]; K.g[1] = g[1]; K.g[2] = g[2];
-    StxProfScope prof(ctx, "gain_apply", 6.0 * img->w * img->h);
-    hipLaunchKernelGGL(gain_apply_kernel, dim3((img->w + 255) / 256, (img->h + 3) / 4), dim3(256), 0, ctx->stream, K);
-    return check_launch("gain_apply");
-}
-
-// ---------------------------------------------------------------------------------------------
-// Strip packing (image-strip sharding): the columns [x0, x0 + w) of up to STRIP_BATCH warped images and of
-// their masks -> flat buffers (image rows at pitch si, then mask rows at pitch sm), one launch.  8 bytes per lane; w is
-// copied in whole 8-pixel groups (rows of every image buffer hold whole groups), x0 is a multiple of 8.
-// ---------------------------------------------------------------------------------------------
-namespace {
-constexpr int STRIP_BATCH = 16;
-struct StripK { const uint8_t* img; const uint8_t* mask; uint8_t* dst; long long istride, mstride, si, sm; int h, img_chunks, mask_chunks, bits; };
-struct StripBatchK { StripK k[STRIP_BATCH]; };
-constexpr int STRIP_ROWS = 4;  // rows per workgroup: four independent 8-byte copies in flight per lane
-// bit j of the result = byte j of m is not 0
-STX_DEV uint32_t strip_nz4(uint32_t m)
-{
-    const uint32_t t = ((((m & 0x7f7f7f7fu) + 0x7f7f7f7fu) | m) & 0x80808080u) >> 7;  // bit 8 j = byte j != 0
-    return (t | (t >> 7) | (t >> 14) | (t >> 21)) & 15u;
-}
-// receiver side of STX_STRIP_MASK_BITS: one byte of bits -> 8 mask bytes 0 / 255 (a lane per 8 pixels, rows on blockIdx.y)
-struct StripBitsK { const uint8_t* bits; long long sm; uint8_t* mask; long long mstride; int groups, h; };
-struct StripBitsBatchK { StripBitsK k[STRIP_BATCH]; };
-__global__ __launch_bounds__(256) void strip_bits_expand_kernel(StripBitsBatchK B)
-{
-    const StripBitsK& P = B.k[blockIdx.z];
-    const int row0 = blockIdx.y * STRIP_ROWS;
-    if (row0 >= P.h) return;
-    for (int g = blockIdx.x * 256 + threadIdx.x; g < P.groups; g += gridDim.x * 256) {
-#pragma unroll
-        for (int r = 0; r < STRIP_ROWS; r++)
-            if (row0 + r < P.h) {
-                const uint32_t b = P.bits[(long long)(row0 + r) * P.sm + g];
-                // bit k of a nibble -> byte k: n * (1 + 2^7 + 2^14 + 2^21) puts bit k at 8 k (and elsewhere: masked off)
-                const uint32_t lo = (((b & 15u) * 0x00204081u) & 0x01010101u) * 255u, hi = (((b >> 4) * 0x00204081u) & 0x01010101u) * 255u;
-                *reinterpret_cast<uint2*>(P.mask + (long long)(row0 + r) * P.mstride + 8ll * g) = make_uint2(lo, hi);
-            }
-    }
-}
-__global__ __launch_bounds__(256) void strip_pack_kernel(StripBatchK B)
-{
-    const StripK& P = B.k[blockIdx.z];
-    const int row0 = blockIdx.y * STRIP_ROWS;
-    if (row0 >= P.h) return;
-    const int per_row = P.img_chunks + P.mask_chunks;
-    for (int c = blockIdx.x * 256 + threadIdx.x; c < per_row; c += gridDim.x * 256) {
-        const bool im = c < P.img_chunks;
-        if (!im && P.bits) {  // STX_STRIP_MASK_BITS: 8 mask bytes -> one byte, bit j = pixel j is not 0
-            const uint8_t* ms = P.mask + 8ll * (c - P.img_chunks);
-            uint8_t* md = P.dst + P.si * P.h + (c - P.img_chunks);
-#pragma unroll
-            for (int r = 0; r < STRIP_ROWS; r++)
-                if (row0 + r < P.h) {
-                    const uint2 v = *reinterpret_cast<const uint2*>(ms + (long long)(row0 + r) * P.mstride);
-                    md[(long long)(row0 + r) * P.sm] = (uint8_t)(strip_nz4(v.x) | (strip_nz4(v.y) << 4));
-                }
-            continue;
-        }
-        const uint8_t* src = im ? P.img + 8ll * c : P.mask + 8ll * (c - P.img_chunks);
-        uint8_t* dst = im ? P.dst + 8ll * c : P.dst + P.si * P.h + 8ll * (c - P.img_chunks);
-        const long long ss = im ? P.istride : P.mstride, ds = im ? P.si : P.sm;
-        uint2 v[STRIP_ROWS];
-#pragma unroll
-        for (int r = 0; r < STRIP_ROWS; r++)
-            if (row0 + r < P.h) v[r] = *reinterpret_cast<const uint2*>(src + (long long)(row0 + r) * ss);
-#pragma unroll
-        for (int r = 0; r < STRIP_ROWS; r++)
-            if (row0 + r < P.h) *reinterpret_cast<uint2*>(dst + (long long)(row0 + r) * ds) = v[r];
-    }
-}
-}  // namespace
-
-int stx_launch_strip_pack(stx_ctx* ctx, int n, const stx_buf* const* imgs, const stx_buf* const* masks, const int* x0, const int* w,
-                          stx_buf* const* dsts, const size_t* si, const size_t* sm, bool mask_bits)
-{
-    for (int base = 0; base < n; base += STRIP_BATCH) {
-        const int m = std::min(STRIP_BATCH, n - base);
-        StripBatchK B = {};
-        int max_h = 0, max_chunks = 0;
-        double bytes = 0.0;
-        for (int i = 0; i < m; i++) {
-            const int g = base + i, w8 = (w[g] + 7) & ~7;
-            StripK& K = B.k[i];
-            K.img = imgs[g]->ptr + (size_t)x0[g] * 3; K.mask = masks[g]->ptr + x0[g]; K.dst = dsts[g]->ptr;
-            K.istride = (long long)imgs[g]->stride; K.mstride = (long long)masks[g]->stride; K.si = (long long)si[g]; K.sm = (long long)sm[g];
-            K.h = imgs[g]->h; K.img_chunks = w8 * 3 / 8; K.mask_chunks = w8 / 8; K.bits = mask_bits ? 1 : 0;
-            max_h = std::max(max_h, K.h);
-            max_chunks = std::max(max_chunks, K.img_chunks + K.mask_chunks);
-            bytes += (mask_bits ? 7.125 : 8.0) * (double)w[g] * K.h;
-        }
-        StxProfScope prof(ctx, "strip_pack", bytes);
-        hipLaunchKernelGGL(strip_pack_kernel, dim3((max_chunks + 255) / 256, (max_h + STRIP_ROWS - 1) / STRIP_ROWS, m), dim3(256), 0, ctx->stream, B);
-    }
-    return check_launch("strip_pack");
-}
-
-// masks[i] (w x h, whole 8-pixel groups per row) <- the bit rows at bits[i] (pitch sm[i])
-int stx_launch_strip_bits_expand(stx_ctx* ctx, int n, const uint8_t* const* bits, const size_t* sm, stx_buf* const* masks)
-{
-    for (int base = 0; base < n; base += STRIP_BATCH) {
-        const int m = std::min(STRIP_BATCH, n - base);
-        StripBitsBatchK B = {};
-        int max_h = 0, max_groups = 0;
-        double bytes = 0.0;
-        for (int i = 0; i < m; i++) {
-            const int g = base + i;
-            StripBitsK& K = B.k[i];
-            K.bits = bits[g]; K.sm = (long long)sm[g]; K.mask = masks[g]->ptr; K.mstride = (long long)masks[g]->stride;
-            K.groups = (masks[g]->w + 7) / 8; K.h = masks[g]->h;
-            max_h = std::max(max_h, K.h); max_groups = std::max(max_groups, K.groups);
-            bytes += 1.125 * (double)masks[g]->w * K.h;
-        }
-        StxProfScope prof(ctx, "strip_unpack", bytes);
-        hipLaunchKernelGGL(strip_bits_expand_kernel, dim3((max_groups + 255) / 256, (max_h + STRIP_ROWS - 1) / STRIP_ROWS, m), dim3(256), 0, ctx->stream, B);
-    }
-    return check_launch("strip_unpack");
-}
-
-// ---------------------------------------------------------------------------------------------
-// cv::resize(INTER_LINEAR_EXACT) for 8-bit images (next rows N2 / N3): 8.8 fixed-point coefficients made on the host in
-// double precision exactly as interpolationLinear<ufixedpoint16>::getCoeffs does (tables: x = offset, y = coeff1 |
-// interior << 16), horizontal sums p0 * c0 + p1 * c1 in 8.8, vertical (h0 * d0 + h1 * d1 + 2^15) >> 16, rows
-// outside the source (h + 128) >> 8.  DILATE: the source is read through cv::dilate(3x3) on the fly and the result is
-// ANDed with a mask of the destination size (SeamFinder.resize, stitching/seam_finder.py:37-43).
-// ---------------------------------------------------------------------------------------------
-namespace {
-struct ResizeK {
-    const uint8_t* src; long long sstride; int sw, sh;
-    uint8_t* dst; long long dstride; int dw, dh;
-    const int2* xt; const int2* yt;
-    const uint8_t* andmask; long long amstride;
-};
-template <int C, bool DILATE>
-STX_DEV uint32_t resize_src(const ResizeK& P, int x, int y, int ch)
-{
-    if (!DILATE) return P.src[(long long)y * P.sstride + x * C + ch];
-    uint32_t m = 0;
-#pragma unroll
-    for (int dy = -1; dy <= 1; dy++)
-#pragma unroll
-        for (int dx = -1; dx <= 1; dx++) {
-            const int xx = x + dx, yy = y + dy;
-            if ((unsigned)xx < (unsigned)P.sw && (unsigned)yy < (unsigned)P.sh) m = max(m, (uint32_t)P.src[(long long)yy * P.sstride + xx]);
-        }
-    return m;
-}
-// one destination pixel (x, y) from its table entries tx / ty = (offset, coeff1 | interior << 16): the body of the single-image and of
-// the batched kernel
-template <int C, bool DILATE>
-STX_DEV void resize_exact_pixel(const ResizeK& P, int x, int y, int2 tx, int2 ty)
-{
-    const int ox = tx.x, oy = ty.x;
-    const uint32_t cx1 = (uint32_t)tx.y & 0xffffu, cx0 = 256u - cx1, cy1 = (uint32_t)ty.y & 0xffffu, cy0 = 256u - cy1;
-    const bool iy = (ty.y >> 16) != 0;
-    const int ox1 = min(ox + 1, P.sw - 1), oy1 = min(oy + 1, P.sh - 1);
-#pragma unroll
-    for (int ch = 0; ch < C; ch++) {
-        const uint32_t h0 = resize_src<C, DILATE>(P, ox, oy, ch) * cx0 + resize_src<C, DILATE>(P, ox1, oy, ch) * cx1;
-        uint32_t v;
-        if (iy) {
-            const uint32_t h1 = resize_src<C, DILATE>(P, ox, oy1, ch) * cx0 + resize_src<C, DILATE>(P, ox1, oy1, ch) * cx1;
-            v = (h0 * cy0 + h1 * cy1 + 32768u) >> 16;
-        } else {
-            v = (h0 + 128u) >> 8;
-        }
-        v = min(v, 255u);
-        if (P.andmask) v &= P.andmask[(long long)y * P.amstride + x];
-        P.dst[(long long)y * P.dstride + x * C + ch] = (uint8_t)v;
-    }
-}
-template <int C, bool DILATE>
-__global__ __launch_bounds__(256) void resize_exact_kernel(ResizeK P)
-{
-    const int x = blockIdx.x * STX_RESIZE_TW + (threadIdx.x & 63);
-    const int y = blockIdx.y * STX_RESIZE_TH + (threadIdx.x >> 6);
-    if (x >= P.dw || y >= P.dh) return;
-    resize_exact_pixel<C, DILATE>(P, x, y, P.xt[x], P.yt[y]);
-}
-}  // namespace
-
-namespace {
-// SeamFinder.resize, fast form (the reference's default pipeline runs it once per image and panorama): the 3x3 dilation of
-// the small low-resolution mask is done once into a scratch image (a few tens of KB, L2 resident) instead of nine
-// bounds-checked byte loads per tap; a lane then produces 4 adjacent destination pixels (taps from the scratch, one
-// dword of the final warped mask, one dword store).  Same integer arithmetic as resize_exact_kernel<1, true>.
-__global__ __launch_bounds__(256) void dilate3x3_kernel(const uint8_t* __restrict__ src, long long sstride, int w, int h,
-                                                        uint8_t* __restrict__ dst, long long dstride)
-{
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= w || y >= h) return;
-    uint32_t m = 0;
-#pragma unroll
-    for (int dy = -1; dy <= 1; dy++)
-#pragma unroll
-        for (int dx = -1; dx <= 1; dx++) {
-            const int xx = x + dx, yy = y + dy;
-            if ((unsigned)xx < (unsigned)w && (unsigned)yy < (unsigned)h) m = max(m, (uint32_t)src[(long long)yy * sstride + xx]);
-        }
-    dst[(long long)y * dstride + x] = (uint8_t)m;
-}
-
-constexpr int SEAM_ROWS = 16;  // destination rows per lane (seam_resize4_body)
-STX_DEV void seam_resize4_body(const ResizeK& P);
-__global__ __launch_bounds__(256) void seam_resize4_kernel(ResizeK P) { seam_resize4_body(P); }  // P.src: the dilated low-resolution mask
-// all seam masks of a panorama in one launch each (blockIdx.z = image); the argument blocks travel as kernel arguments
-constexpr int SEAM_BATCH = 16;
-struct SeamBatchK { ResizeK k[SEAM_BATCH]; const uint8_t* raw[SEAM_BATCH]; long long raw_stride[SEAM_BATCH]; };
-__global__ __launch_bounds__(256) void seam_resize4_batch_kernel(SeamBatchK B) { seam_resize4_body(B.k[blockIdx.z]); }
-__global__ __launch_bounds__(256) void dilate3x3_batch_kernel(SeamBatchK B)
-{
-    const ResizeK& P = B.k[blockIdx.z];
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= P.sw || y >= P.sh) return;
-    const uint8_t* src = B.raw[blockIdx.z];
-    const long long ss = B.raw_stride[blockIdx.z];
-    uint32_t m = 0;
-#pragma unroll
-    for (int dy = -1; dy <= 1; dy++)
-#pragma unroll
-        for (int dx = -1; dx <= 1; dx++) {
-            const int xx = x + dx, yy = y + dy;
-            if ((unsigned)xx < (unsigned)P.sw && (unsigned)yy < (unsigned)P.sh) m = max(m, (uint32_t)src[(long long)yy * ss + xx]);
-        }
-    const_cast<uint8_t*>(P.src)[(long long)y * P.sstride + x] = (uint8_t)m;
-}
-// One lane = 4 adjacent columns of SEAM_ROWS consecutive destination rows.  The seam masks are enlarged (0.1 Mpix -> final
-// size, about 11 x): consecutive destination rows interpolate between the same two source rows, so the horizontal sums
-// (8.8 fixed point) are kept in registers and recomputed only when the source row changes (a wave-uniform test: the row is);
-// a destination pixel then costs the vertical blend, the AND and a quarter of a dword store.
-STX_DEV void seam_resize4_body(const ResizeK& P)
-{
-    const int x4 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
-    const int yb = (blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * SEAM_ROWS;
-    if (x4 >= P.dw || yb >= P.dh) return;
-    // the table holds dw entries rounded up to 4 (host), so the four reads are always inside it
-    const int4 ta = *reinterpret_cast<const int4*>(P.xt + x4), tb = *reinterpret_cast<const int4*>(P.xt + x4 + 2);
-    const int ox[4] = {ta.x, ta.z, tb.x, tb.z}, cf[4] = {ta.y, ta.w, tb.y, tb.w};
-    uint32_t h0[4] = {0, 0, 0, 0}, h1[4] = {0, 0, 0, 0};
-    int cur = -1;
-    uint32_t am[SEAM_ROWS];  // the final-size masks of all rows first: SEAM_ROWS loads in flight instead of one per iteration
-#pragma unroll
-    for (int r = 0; r < SEAM_ROWS; r++)
-        am[r] = yb + r < P.dh ? *reinterpret_cast<const uint32_t*>(P.andmask + (long long)(yb + r) * P.amstride + x4) : 0u;
-#pragma unroll
-    for (int r = 0; r < SEAM_ROWS; r++) {
-        const int y = yb + r;
-        if (y >= P.dh) break;
-        const int2 ty = P.yt[y];
-        if (ty.x != cur) {
-            cur = ty.x;
-            const uint8_t* r0 = P.src + (long long)cur * P.sstride;
-            const uint8_t* r1 = P.src + (long long)min(cur + 1, P.sh - 1) * P.sstride;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int o0 = ox[j], o1 = min(o0 + 1, P.sw - 1);
-                const uint32_t cx1 = (uint32_t)cf[j] & 0xffffu, cx0 = 256u - cx1;
-                h0[j] = (uint32_t)r0[o0] * cx0 + (uint32_t)r0[o1] * cx1;
-                h1[j] = (uint32_t)r1[o0] * cx0 + (uint32_t)r1[o1] * cx1;
-            }
-        }
-        const uint32_t cy1 = (uint32_t)ty.y & 0xffffu, cy0 = 256u - cy1;
-        const bool iy = (ty.y >> 16) != 0;
-        uint32_t out = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const uint32_t v = iy ? (h0[j] * cy0 + h1[j] * cy1 + 32768u) >> 16 : (h0[j] + 128u) >> 8;
-            out |= min(v, 255u) << (8 * j);
-        }
-        out &= am[r];
-        uint8_t* d = P.dst + (long long)y * P.dstride + x4;
-        if (x4 + 4 <= P.dw) *reinterpret_cast<uint32_t*>(d) = out;
-        else for (int j = 0; x4 + j < P.dw; j++) d[j] = (uint8_t)(out >> (8 * j));
-    }
-}
-}  // namespace
-
-// SeamFinder.resize for n images: tmp[i] = scratch of the dilated low-resolution mask (pitch tstride[i]), d_xt / d_yt per image
-int stx_launch_seam_resize_batch(stx_ctx* ctx, int n, const stx_buf* const* seams, const stx_buf* const* masks, stx_buf* const* dsts,
-                                 const int* const* d_xt, const int* const* d_yt, uint8_t* const* tmp, const size_t* tstride)
-{
-    for (int base = 0; base < n; base += SEAM_BATCH) {
-        const int m = std::min(SEAM_BATCH, n - base);
-        SeamBatchK B = {};
-        int msw = 0, msh = 0, mdw = 0, mdh = 0;
-        double bytes = 0.0;
-        for (int i = 0; i < m; i++) {
-            const int g = base + i;
-            ResizeK& K = B.k[i];
-            K.src = tmp[g]; K.sstride = (long long)tstride[g]; K.sw = seams[g]->w; K.sh = seams[g]->h;
-            K.dst = dsts[g]->ptr; K.dstride = (long long)dsts[g]->stride; K.dw = dsts[g]->w; K.dh = dsts[g]->h;
-            K.xt = (const int2*)d_xt[g]; K.yt = (const int2*)d_yt[g];
-            K.andmask = masks[g]->ptr; K.amstride = (long long)masks[g]->stride;
-            B.raw[i] = seams[g]->ptr; B.raw_stride[i] = (long long)seams[g]->stride;
-            msw = std::max(msw, K.sw); msh = std::max(msh, K.sh); mdw = std::max(mdw, K.dw); mdh = std::max(mdh, K.dh);
-            bytes += (double)K.sw * K.sh + 2.0 * K.dw * K.dh;
-        }
-        StxProfScope prof(ctx, "seam_mask_resize", bytes);
-        hipLaunchKernelGGL(dilate3x3_batch_kernel, dim3((msw + 63) / 64, (msh + 3) / 4, m), dim3(256), 0, ctx->stream, B);
-        hipLaunchKernelGGL(seam_resize4_batch_kernel, dim3((mdw + 255) / 256, (mdh + 4 * SEAM_ROWS - 1) / (4 * SEAM_ROWS), m), dim3(256), 0, ctx->stream, B);
-    }
-    return check_launch("seam_mask_resize");
-}
-
-// ---------------------------------------------------------------------------------------------
-// SeamFinder.resize as ONE launch (round 6; stitching/seam_finder.py:37-43, stitching/stitcher.py:124,223-225).
-// Until round 5 a panorama's seam masks took a table upload (448 KB of coefficients made by the host in double precision), a dilate
-// launch into a global scratch and the resize launch with byte gathers from that scratch (81.6 us for config 2's eight masks, 0.24 of
-// the HBM peak).  Here a workgroup owns a 512 x 32 tile of the destination:
-//   * the coefficients of its 512 columns and 32 rows are made IN the kernel with the same IEEE double operations the host table used
-//     (scale * (v + 0.5) - 0.5, floor, rint of the fraction * 256 — interpolationLinear<ufixedpoint16>::getCoeffs; this file is built
-//     with -ffp-contract=off) and kept in LDS: nothing is uploaded;
-//   * the low-resolution source window under the tile (+ 1 px) goes to LDS, is dilated 3 x 3 there, and every tap is an LDS byte;
-//   * a lane makes 8 adjacent pixels of 8 rows (rows per lane, one box, interleaved: 4: 48.4-50.0 us, 6: 48.6-49.4, 8: 47.7-49.1,
-//     16: 52.2-55.4, 32: 69.7-73.3 for config 2's eight masks): the final-mask dwords of all its rows are requested before the window is prepared,
-//     the horizontal 8.8 sums live in registers and are redone only when the source row changes, a pixel costs two 24-bit
-//     multiply-adds and 3/4 of a byte permute, a row leaves as one 8-byte store.
-// Same integers as resize_exact_kernel<1, true> (the tests compare both with the CPU checker).
-// ---------------------------------------------------------------------------------------------
-namespace {
-constexpr int SEAM1_COLS = 8, SEAM1_ROWS = 8;  // pixels and rows per lane (the A/B of 4 / 6 / 8 / 16 / 32 rows is quoted above)
-constexpr int SEAM1_TW = 64 * SEAM1_COLS, SEAM1_TH = 4 * SEAM1_ROWS;
-struct Seam1K {
-    const uint8_t* src; long long sstride; int sw, sh;  // the low-resolution seam mask as the seam finder made it
-    uint8_t* dst; long long dstride; int dw, dh;         // the destination rectangle ...
-    const uint8_t* am; long long amstride;               // ... and the same rectangle of the final warped mask
-    int x0, y0;                                          // where the rectangle lies in the full final mask
-    double xscale, yscale;                               // 1 / (full width / sw), 1 / (full height / sh): the host's doubles
-};
-struct Seam1BatchK { Seam1K k[SEAM_BATCH]; int pitch, raw_bytes; };
-
-// interpolationLinear<ufixedpoint16>::getCoeffs for destination index v: (offset, coeff1 | interior << 16) — stx_resize_host.cpp linear_exact_table
-STX_DEV int2 seam1_coeff(int v, double scale, int src_n)
-{
-    const double fval = scale * ((double)v + 0.5) - 0.5;
-    const int ival = (int)floor(fval);
-    int ofs = 0, c1 = 0, interior = 0;
-    if (ival >= 0 && src_n > 1) {
-        if (ival < src_n - 1) { ofs = ival; c1 = (int)rint((fval - (double)ival) * 256.0); interior = 1; }
-        else ofs = src_n - 1;
-    }
-    return make_int2(ofs, c1 | (interior << 16));
-}
-
-__global__ __launch_bounds__(256) void seam_resize_lds_kernel(Seam1BatchK B)
-{
-    extern __shared__ uint8_t s_win[];
-    __shared__ int2 s_xt[SEAM1_TW];
-    __shared__ int2 s_yt[SEAM1_TH];
-    const Seam1K& P = B.k[blockIdx.z];
-    const int X0 = blockIdx.x * SEAM1_TW, Y0 = blockIdx.y * SEAM1_TH;
-    if (X0 >= P.dw || Y0 >= P.dh) return;
-    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int x8 = X0 + lane * SEAM1_COLS, yb = Y0 + wv * SEAM1_ROWS;
-    const bool mine = x8 < P.dw && yb < P.dh;  // (the row pitch holds whole 8-pixel groups: host-checked)
-    // the final-mask bytes of this lane's rows: in flight while the window is prepared
-    uint2 am[SEAM1_ROWS];
-#pragma unroll
-    for (int r = 0; r < SEAM1_ROWS; r++)
-        am[r] = mine && yb + r < P.dh ? *reinterpret_cast<const uint2*>(P.am + (long long)(yb + r) * P.amstride + x8) : make_uint2(0u, 0u);
-    for (int i = tid; i < SEAM1_TW; i += 256) s_xt[i] = seam1_coeff(P.x0 + min(X0 + i, P.dw - 1), P.xscale, P.sw);
-    if (tid < SEAM1_TH) s_yt[tid] = seam1_coeff(P.y0 + min(Y0 + tid, P.dh - 1), P.yscale, P.sh);
-    __syncthreads();
-    // the source window under this tile
-    const int nx = min(SEAM1_TW, P.dw - X0), ny = min(SEAM1_TH, P.dh - Y0);
-    const int wx0 = s_xt[0].x, wx1 = min(s_xt[nx - 1].x + 1, P.sw - 1);
-    const int wy0 = s_yt[0].x, wy1 = min(s_yt[ny - 1].x + 1, P.sh - 1);
-    const int cw = wx1 - wx0 + 1, rh = wy1 - wy0 + 1, cw2 = cw + 2, pitch = B.pitch;
-    uint8_t* const s_raw = s_win;                 // (rh + 2) x (cw + 2): the window and one pixel around it, 0 outside the image
-    uint8_t* const s_dil = s_win + B.raw_bytes;   // rh x cw: cv::dilate(3 x 3) of it (pixels outside the image do not take part: 0 = no-op for max)
-    const float inv2 = 1.0f / (float)cw2, inv1 = 1.0f / (float)cw;
-    for (int i = tid; i < (rh + 2) * cw2; i += 256) {
-        int r = (int)((float)i * inv2);  // i / cw2: the estimate is one off at most (i < 2^24)
-        int c = i - r * cw2;
-        if (c < 0) { r--; c += cw2; } else if (c >= cw2) { r++; c -= cw2; }
-        const int sy = wy0 - 1 + r, sx = wx0 - 1 + c;
-        s_raw[r * pitch + c] = ((unsigned)sx < (unsigned)P.sw && (unsigned)sy < (unsigned)P.sh) ? P.src[(long long)sy * P.sstride + sx] : (uint8_t)0;
-    }
-    __syncthreads();
-    for (int i = tid; i < rh * cw; i += 256) {
-        int r = (int)((float)i * inv1);
-        int c = i - r * cw;
-        if (c < 0) { r--; c += cw; } else if (c >= cw) { r++; c -= cw; }
-        uint32_t m = 0;
-#pragma unroll
-        for (int dy = 0; dy < 3; dy++)
-#pragma unroll
-            for (int dx = 0; dx < 3; dx++) m = max(m, (uint32_t)s_raw[(r + dy) * pitch + c + dx]);
-        s_dil[r * pitch + c] = (uint8_t)m;
-    }
-    __syncthreads();
-    if (!mine) return;
-    int o0[SEAM1_COLS], o1[SEAM1_COLS];
-    uint32_t c1[SEAM1_COLS];
-#pragma unroll
-    for (int j = 0; j < SEAM1_COLS; j++) {
-        const int2 t = s_xt[lane * SEAM1_COLS + j];
-        o0[j] = t.x - wx0;
-        o1[j] = min(t.x + 1, P.sw - 1) - wx0;
-        c1[j] = (uint32_t)t.y & 0xffffu;
-    }
-    uint32_t h0[SEAM1_COLS], h1[SEAM1_COLS];
-    int cur = -(1 << 30);
-    const uint32_t keep_lo = x8 + 4 <= P.dw ? 0xffffffffu : (x8 + 0 < P.dw ? 0xffffffffu >> (8 * (4 - (P.dw - x8))) : 0u);
-    const uint32_t keep_hi = x8 + 8 <= P.dw ? 0xffffffffu : (x8 + 4 < P.dw ? 0xffffffffu >> (8 * (8 - (P.dw - x8))) : 0u);
-#pragma unroll
-    for (int r = 0; r < SEAM1_ROWS; r++) {
-        const int y = yb + r;
-        if (y >= P.dh) break;
-        const int2 ty = s_yt[wv * SEAM1_ROWS + r];
-        const int row = __builtin_amdgcn_readfirstlane(ty.x);
-        if (row != cur) {
-            cur = row;
-            const uint8_t* d0 = s_dil + (cur - wy0) * pitch;
-            const uint8_t* d1 = s_dil + (min(cur + 1, P.sh - 1) - wy0) * pitch;
-#pragma unroll
-            for (int j = 0; j < SEAM1_COLS; j++) {
-                const uint32_t a0 = 256u - c1[j];
-                h0[j] = (uint32_t)d0[o0[j]] * a0 + (uint32_t)d0[o1[j]] * c1[j];
-                h1[j] = (uint32_t)d1[o0[j]] * a0 + (uint32_t)d1[o1[j]] * c1[j];
-            }
-        }
-        const uint32_t cy1 = (uint32_t)__builtin_amdgcn_readfirstlane(ty.y) & 0xffffu, cy0 = 256u - cy1;
-        const bool iy = (__builtin_amdgcn_readfirstlane(ty.y) >> 16) != 0;
-        uint32_t sum[SEAM1_COLS];  // the result is byte 2 of every sum: (h0 cy0 + h1 cy1 + 2^15) >> 16 <= 255, ((h0 + 128) >> 8) << 16 likewise
-#pragma unroll
-        for (int j = 0; j < SEAM1_COLS; j++)
-            sum[j] = iy ? __umul24(h1[j], cy1) + (__umul24(h0[j], cy0) + 32768u) : (h0[j] + 128u) << 8;
-        uint2 out;
-        out.x = __builtin_amdgcn_perm(sum[1], sum[0], 0x0c0c0602u) | __builtin_amdgcn_perm(sum[3], sum[2], 0x06020c0cu);
-        out.y = __builtin_amdgcn_perm(sum[5], sum[4], 0x0c0c0602u) | __builtin_amdgcn_perm(sum[7], sum[6], 0x06020c0cu);
-        out.x &= am[r].x & keep_lo;  // bytes beyond the image inside the row pitch: 0, whatever stands in the final mask's padding
-        out.y &= am[r].y & keep_hi;
-        *reinterpret_cast<uint2*>(P.dst + (long long)y * P.dstride + x8) = out;
-    }
-}
-}  // namespace
-
-// -> STX_OK and *done = true when the images qualified and the launch was made; *done = false: the caller takes the table path
-int stx_launch_seam_resize_lds(stx_ctx* ctx, int n, const stx_buf* const* seams, const stx_buf* const* masks, stx_buf* const* dsts,
-                               const int* full_wh_xy0, bool* done)
-{
-    *done = false;
-    static const bool off = getenv("STITCHING_AMD_SEAM_LDS") && atoi(getenv("STITCHING_AMD_SEAM_LDS")) == 0;
-    if (off) return STX_OK;
-    int pitch = 0, rows = 0;
-    for (int i = 0; i < n; i++) {
-        const stx_buf *m = masks[i], *d = dsts[i];
-        const size_t w8 = ((size_t)d->w + 7) & ~(size_t)7;
-        if (((uintptr_t)m->ptr & 7) || (m->stride & 7) || w8 > m->stride || ((uintptr_t)d->ptr & 7) || (d->stride & 7) || w8 > d->stride) return STX_OK;
-        const int fw = full_wh_xy0 ? full_wh_xy0[4 * i] : d->w, fh = full_wh_xy0 ? full_wh_xy0[4 * i + 1] : d->h;
-        const double xs = 1.0 / ((double)fw / (double)seams[i]->w), ys = 1.0 / ((double)fh / (double)seams[i]->h);
-        // source columns / rows under a tile: floor((n - 1) scale) + 2, and one more for the fraction the first one starts at
-        pitch = std::max(pitch, std::min(seams[i]->w, (int)std::ceil(SEAM1_TW * xs) + 3) + 2);
-        rows = std::max(rows, std::min(seams[i]->h, (int)std::ceil(SEAM1_TH * ys) + 3));
-    }
-    pitch = (pitch + 3) & ~3;
-    const size_t raw_bytes = (size_t)pitch * (rows + 2), lds = raw_bytes + (size_t)pitch * rows;
-    if (lds > (40u << 10)) return STX_OK;  // an enlargement factor near 1: the window would not leave room for a second workgroup per CU
-    for (int base = 0; base < n; base += SEAM_BATCH) {
-        const int m = std::min(SEAM_BATCH, n - base);
-        Seam1BatchK B = {};
-        B.pitch = pitch; B.raw_bytes = (int)raw_bytes;
-        int mdw = 0, mdh = 0;
-        double bytes = 0.0;
-        for (int i = 0; i < m; i++) {
-            const int g = base + i;
-            Seam1K& K = B.k[i];
-            K.src = seams[g]->ptr; K.sstride = (long long)seams[g]->stride; K.sw = seams[g]->w; K.sh = seams[g]->h;
-            K.dst = dsts[g]->ptr; K.dstride = (long long)dsts[g]->stride; K.dw = dsts[g]->w; K.dh = dsts[g]->h;
-            K.am = masks[g]->ptr; K.amstride = (long long)masks[g]->stride;
-            const int fw = full_wh_xy0 ? full_wh_xy0[4 * g] : K.dw, fh = full_wh_xy0 ? full_wh_xy0[4 * g + 1] : K.dh;
-            K.x0 = full_wh_xy0 ? full_wh_xy0[4 * g + 2] : 0; K.y0 = full_wh_xy0 ? full_wh_xy0[4 * g + 3] : 0;
-            K.xscale = 1.0 / ((double)fw / (double)K.sw); K.yscale = 1.0 / ((double)fh / (double)K.sh);
-            mdw = std::max(mdw, K.dw); mdh = std::max(mdh, K.dh);
-            bytes += (double)K.sw * K.sh + 2.0 * K.dw * K.dh;
-        }
-        StxProfScope prof(ctx, "seam_mask_resize", bytes);
-        hipLaunchKernelGGL(seam_resize_lds_kernel, dim3((mdw + SEAM1_TW - 1) / SEAM1_TW, (mdh + SEAM1_TH - 1) / SEAM1_TH, m), dim3(256), lds, ctx->stream, B);
-    }
-    *done = true;
-    return check_launch("seam_mask_resize");
-}
-
-int stx_launch_resize_exact(stx_ctx* ctx, const stx_buf* src, stx_buf* dst, const int* d_xt, const int* d_yt, bool dilate,
-                            const stx_buf* andmask)
-{
-    ResizeK K;
-    K.src = src->ptr; K.sstride = (long long)src->stride; K.sw = src->w; K.sh = src->h;
-    K.dst = dst->ptr; K.dstride = (long long)dst->stride; K.dw = dst->w; K.dh = dst->h;
-    K.xt = (const int2*)d_xt; K.yt = (const int2*)d_yt;
-    K.andmask = andmask ? andmask->ptr : nullptr; K.amstride = andmask ? (long long)andmask->stride : 0;
-    const dim3 grid((dst->w + STX_RESIZE_TW - 1) / STX_RESIZE_TW, (dst->h + STX_RESIZE_TH - 1) / STX_RESIZE_TH);
-    StxProfScope prof(ctx, dilate ? "seam_mask_resize" : "resize_linear_exact", (double)src->w * src->h * src->c + (double)dst->w * dst->h * dst->c * (andmask ? 2 : 1));
-    // dword access to the destination and to the final mask: 4-byte aligned rows (every stx_buf_new image; views may not be),
-    // and the mask rows must be readable up to the next multiple of 4 columns
-    const bool fast = dilate && andmask && ((uintptr_t)dst->ptr & 3) == 0 && (dst->stride & 3) == 0 && ((uintptr_t)andmask->ptr & 3) == 0 &&
-                      (andmask->stride & 3) == 0 && (size_t)((dst->w + 3) & ~3) <= andmask->stride && (size_t)((dst->w + 3) & ~3) <= dst->stride;
-    if (fast) {
-        StxDevBlock tmp;  // back to the allocator behind the second launch: stream-ordered reuse
-        const size_t tstride = ((size_t)src->w + 63) & ~(size_t)63;
-        STX_TRY(stx_dev_alloc(ctx, tstride * src->h, &tmp));
-        hipLaunchKernelGGL(dilate3x3_kernel, dim3((src->w + 63) / 64, (src->h + 3) / 4), dim3(256), 0, ctx->stream, src->ptr,
-                           (long long)src->stride, src->w, src->h, (uint8_t*)tmp.get(), (long long)tstride);
-        K.src = (const uint8_t*)tmp.get(); K.sstride = (long long)tstride;
-        hipLaunchKernelGGL(seam_resize4_kernel, dim3((dst->w + 255) / 256, (dst->h + 4 * SEAM_ROWS - 1) / (4 * SEAM_ROWS)), dim3(256), 0, ctx->stream, K);
-    } else if (dilate) hipLaunchKernelGGL((resize_exact_kernel<1, true>), grid, dim3(256), 0, ctx->stream, K);
-    else if (src->c == 1) hipLaunchKernelGGL((resize_exact_kernel<1, false>), grid, dim3(256), 0, ctx->stream, K);
-    else if (src->c == 3) hipLaunchKernelGGL((resize_exact_kernel<3, false>), grid, dim3(256), 0, ctx->stream, K);
-    else return stx_fail(STX_ERR_UNSUPPORTED, "resize: 1 or 3 channels");
-    return check_launch("resize_linear_exact");
-}
-
-// ---------------------------------------------------------------------------------------------
-// cv::resize(INTER_LINEAR_EXACT) of n images of unequal sizes as ONE launch (the LOW pass of Images.resize: 64 frames -> 0.1 Mpx is 64
-// launches, table uploads and allocations of a kernel that runs a few microseconds).  The grid is the flat list of the destination
-// tiles of all images, image after image: a workgroup finds its image by bisecting the descriptors' first-tile numbers (uniform over
-// the workgroup: scalar loads), so no workgroup exists for an image smaller than the largest.  A tile is the single-image kernel's:
-// 64 adjacent pixels of a row per wavefront (a row segment leaves as 64 or 192 contiguous bytes), 4 rows per workgroup.  Nothing but
-// the descriptors is uploaded: a lane makes its own two coefficients with the IEEE double operations of the host table (seam1_coeff,
-// as the one-launch seam-mask resize does) and hands them to the single-image kernel's pixel body.
-// ---------------------------------------------------------------------------------------------
-namespace {
-__global__ __launch_bounds__(256) void resize_exact_batch_kernel(const StxResizeItem* __restrict__ items, int n)
-{
-    const int tile = blockIdx.x;
-    int lo = 0, hi = n - 1;  // the last image whose first tile is <= tile (tile0 is ascending, items[0].tile0 = 0)
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (items[mid].tile0 <= tile) lo = mid; else hi = mid - 1;
-    }
-    const StxResizeItem& D = items[lo];
-    const int t = tile - D.tile0, tyi = t / D.tiles_x, txi = t - tyi * D.tiles_x;
-    const int x = txi * STX_RESIZE_TW + (threadIdx.x & 63);
-    const int y = tyi * STX_RESIZE_TH + (threadIdx.x >> 6);
-    if (x >= D.dw || y >= D.dh) return;
-    ResizeK P;
-    P.src = D.src; P.sstride = D.sstride; P.sw = D.sw; P.sh = D.sh;
-    P.dst = D.dst; P.dstride = D.dstride; P.dw = D.dw; P.dh = D.dh;
-    P.xt = nullptr; P.yt = nullptr; P.andmask = nullptr; P.amstride = 0;
-    const int2 tx = seam1_coeff(x, D.xscale, D.sw), ty = seam1_coeff(y, D.yscale, D.sh);
-    if (D.c == 3) resize_exact_pixel<3, false>(P, x, y, tx, ty);
-    else resize_exact_pixel<1, false>(P, x, y, tx, ty);
-}
-}  // namespace
-
-int stx_launch_resize_exact_batch(stx_ctx* ctx, const StxResizeItem* d_items, int n, int total_tiles, double algo_bytes)
-{
-    StxProfScope prof(ctx, "resize_linear_exact_batch", algo_bytes);
-    hipLaunchKernelGGL(resize_exact_batch_kernel, dim3(total_tiles), dim3(256), 0, ctx->stream, d_items, n);
-    return check_launch("resize_linear_exact_batch");
-}
-
-// ---------------------------------------------------------------------------------------------
-// BlocksCompensator::apply (next row N1, the reference's default "gain_blocks" compensator): the small fp32 gain map is
-// interpolated to the image size exactly as cv::resize(INTER_LINEAR) does for CV_32F — fp32 throughout, horizontal
-// S[s] * a0 + S[s+1] * a1 (S[s] alone at the right end), vertical R0 * b0 + R1 * b1 with the rows clamped, no FMA — and
-// multiplied in with cv::multiply's fp32 product + cvRound + saturation.  Fused: the full-size gain map never exists.
-// Tables (host, double -> float as upstream): x = (s, bits of f), y likewise (s may be -1).
-// ---------------------------------------------------------------------------------------------
-namespace {
-struct BlockGainK {
-    uint8_t* img; long long stride; int w, h;
-    const float* gmap; long long gstride; int gw, gh, gc;  // gstride in floats; gc = 1 (one map) or 3 (BGR maps, interleaved)
-    const int2* xt; const int2* yt;
-};
-STX_DEV float gain_hrow(const BlockGainK& P, int row, int sx, int ch, float a0, float a1)
-{
-    const float* r = P.gmap + (long long)row * P.gstride + ch;
-    if (sx >= P.gw - 1) return r[sx * P.gc];
-    return stxd::fadd(stxd::fmul(r[sx * P.gc], a0), stxd::fmul(r[(sx + 1) * P.gc], a1));
-}
-__global__ __launch_bounds__(256) void block_gain_kernel(BlockGainK P)
-{
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= P.w || y >= P.h) return;
-    const int2 tx = P.xt[x], ty = P.yt[y];
-    const float a1 = __int_as_float(tx.y), a0 = stxd::fsub(1.f, a1), b1 = __int_as_float(ty.y), b0 = stxd::fsub(1.f, b1);
-    const int r0 = min(max(ty.x, 0), P.gh - 1), r1 = min(max(ty.x + 1, 0), P.gh - 1);
-    uint8_t* p = P.img + (long long)y * P.stride + x * 3;
-    float g = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        if (c == 0 || P.gc == 3)
-            g = stxd::fadd(stxd::fmul(gain_hrow(P, r0, tx.x, c, a0, a1), b0), stxd::fmul(gain_hrow(P, r1, tx.x, c, a0, a1), b1));
-        p[c] = (uint8_t)min(max(stxd::cv_round(stxd::fmul((float)p[c], g)), 0), 255);
-    }
-}
-}  // namespace
-
-int stx_launch_block_gain(stx_ctx* ctx, stx_buf* img, const stx_buf* gmap, const int* d_xt, const int* d_yt)
-{
-    BlockGainK K;
-    K.img = img->ptr; K.stride = (long long)img->stride; K.w = img->w; K.h = img->h;
-    K.gmap = (const float*)gmap->ptr; K.gstride = (long long)(gmap->stride / sizeof(float)); K.gw = gmap->w; K.gh = gmap->h;
-    K.gc = gmap->c;
-    K.xt = (const int2*)d_xt; K.yt = (const int2*)d_yt;
-    StxProfScope prof(ctx, "block_gain_apply", 6.0 * img->w * img->h);
-    hipLaunchKernelGGL(block_gain_kernel, dim3((img->w + 63) / 64, (img->h + 3) / 4), dim3(256), 0, ctx->stream, K);
-    return check_launch("block_gain_apply");
-}
-
-// ---------------------------------------------------------------------------------------------
-// The same product for all images of a panorama in two launches, at HBM rate (stx_block_gain_apply_batch).  cv::resize(INTER_LINEAR)
-// is separable and rounds each pass to fp32, so the horizontal pass is made ONCE per gain-map row: H[r][x] = S[r][s] a0 + S[r][s+1] a1
-// for every column x of the image (gain_rows_kernel: gh x w floats per image, a few hundred KB, L2 resident; the coefficient set-up
-// f = (float)((x + 0.5) scale - 0.5) runs on the device in IEEE double, operation for operation the host loop of linear_f32_table).
-// The product pass then needs two 16-byte reads of H per 4 pixels and row: g = H[r0][x] b0 + H[r1][x] b1, cvRound(p g) saturated.
-// One lane = 4 pixels (three dwords in, three out), one wavefront = 256 pixels of a row, 4 rows one after the other.
-// An image may be the rectangle at (x0, y0) of a larger warped image (full_w x full_h: StitchJob's seam-cell crops): the gain map is
-// laid over the FULL image, as BlocksCompensator::apply lays it over the whole warped image.
-// ---------------------------------------------------------------------------------------------
-namespace {
-constexpr int GAIN_BATCH = 16;
-struct BlockGain4K {
-    uint8_t* img; long long stride; int w, h;          // the (sub-)image, whole rows of the library's own buffers (4-pixel groups)
-    int x0, y0, full_w, full_h;                        // its place in the full warped image
-    const float* gmap; long long gstride; int gw, gh;  // gstride in floats
-    double xscale, yscale;                             // 1 / (full / gain-map size), host double
-    float* H; long long hstride;                       // [gh][hstride] floats x GC; hstride = w rounded up to 4 (x GC)
-    int2* yt;                                          // [h]: (source row, bits of the fraction)
-    int fast;                                          // host-proved: every gain finite and below 2^31 / 255 (no product leaves int range)
-};
-struct BlockGainBatchK { BlockGain4K k[GAIN_BATCH]; };
-
-STX_DEV void gain_coeff(int d, double scale, int src_n, bool clamp, int& sidx, float& f)
-{
-    f = (float)(((double)d + 0.5) * scale - 0.5);
-    sidx = (int)floorf(f);
-    f = stxd::fsub(f, (float)sidx);
-    if (clamp) {
-        if (sidx < 0) { sidx = 0; f = 0.f; }
-        else if (sidx >= src_n - 1) { sidx = src_n - 1; f = 0.f; }
-    }
-}
-
-template <int GC>
-__global__ __launch_bounds__(256) void gain_rows_kernel(BlockGainBatchK B)
-{
-    const BlockGain4K& P = B.k[blockIdx.z];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (blockIdx.y == 0) {  // row table
-        if (i < P.h) {
-            int sy; float f;
-            gain_coeff(P.y0 + i, P.yscale, P.gh, false, sy, f);
-            P.yt[i] = make_int2(sy, __float_as_int(f));
-        }
-        return;
-    }
-    const int r = blockIdx.y - 1;  // gain-map row
-    // the columns w .. round_up4(w) - 1 of the row pitch are written too (the gain of the last column): the consumers read a row in
-    // groups of 4 and multiply the image's ROW PADDING with what stands there — scratch left as it was made those padding bytes differ
-    // from run to run
-    const int wpad = (P.w + 3) & ~3;
-    if (r >= P.gh || i >= wpad) return;
-    int sx; float a1;
-    gain_coeff(P.x0 + min(i, P.w - 1), P.xscale, P.gw, true, sx, a1);
-    const float a0 = stxd::fsub(1.f, a1);
-    const float* row = P.gmap + (long long)r * P.gstride;
-#pragma unroll
-    for (int c = 0; c < GC; c++) {
-        float v;
-        if (sx >= P.gw - 1) v = row[sx * GC + c];
-        else v = stxd::fadd(stxd::fmul(row[sx * GC + c], a0), stxd::fmul(row[(sx + 1) * GC + c], a1));
-        P.H[(long long)r * P.hstride + (long long)i * GC + c] = v;
-    }
-}
-
-// cvRound(p g) saturated to u8 into byte `sel` of `old`: v_cvt_pk_u8_f32 is the round-half-even of cvRound AND the saturation
-template <bool FAST>
-STX_DEV uint32_t gain_px(uint32_t old, int sel, float p, float g)
-{
-    float v = stxd::fmul(p, g);
-    if (!FAST) v = v < 2147483648.f ? v : 0.f;  // cvRound's INT_MIN for NaN / out-of-range products saturates to 0
-    return __builtin_amdgcn_cvt_pk_u8_f32(v, (uint32_t)sel, old);  // rounds to nearest even and saturates itself: tools/ubench/cvt_pk_u8.hip
-}
-
-template <int GC, bool FAST>
-__global__ __launch_bounds__(256) void block_gain4_kernel(BlockGainBatchK B)
-{
-    const BlockGain4K& P = B.k[blockIdx.z];
-    const int x4 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (x4 >= P.w) return;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int y = blockIdx.y * 16 + wv * 4 + j;
-        if (y >= P.h) break;
-        const int2 ty = P.yt[y];
-        const float b1 = __int_as_float(ty.y), b0 = stxd::fsub(1.f, b1);
-        const int r0 = min(max(ty.x, 0), P.gh - 1), r1 = min(max(ty.x + 1, 0), P.gh - 1);
-        const float* h0 = P.H + (long long)r0 * P.hstride + (long long)x4 * GC;
-        const float* h1 = P.H + (long long)r1 * P.hstride + (long long)x4 * GC;
-        float g[4 * GC];
-#pragma unroll
-        for (int q = 0; q < GC; q++) {
-            const float4 u = reinterpret_cast<const float4*>(h0)[q], v = reinterpret_cast<const float4*>(h1)[q];
-            g[4 * q + 0] = stxd::fadd(stxd::fmul(u.x, b0), stxd::fmul(v.x, b1));
-            g[4 * q + 1] = stxd::fadd(stxd::fmul(u.y, b0), stxd::fmul(v.y, b1));
-            g[4 * q + 2] = stxd::fadd(stxd::fmul(u.z, b0), stxd::fmul(v.z, b1));
-            g[4 * q + 3] = stxd::fadd(stxd::fmul(u.w, b0), stxd::fmul(v.w, b1));
-        }
-        uint32_t* p = reinterpret_cast<uint32_t*>(P.img + (long long)y * P.stride + (long long)x4 * 3);
-        uint32_t d[3] = {p[0], p[1], p[2]}, o[3] = {0u, 0u, 0u};
-#pragma unroll
-        for (int k = 0; k < 12; k++) {  // byte k of the 12: pixel k / 3, channel k % 3
-            const float pv = (float)((d[k >> 2] >> (8 * (k & 3))) & 255u);
-            o[k >> 2] = gain_px<FAST>(o[k >> 2], k & 3, pv, GC == 1 ? g[k / 3] : g[k]);
-        }
-        p[0] = o[0]; p[1] = o[1]; p[2] = o[2];
-    }
-}
-}  // namespace
-
-// H rows + row tables of n rectangles (see stx_launch_block_gain_batch); imgs may be null (a consumer that multiplies the gain in itself)
-static void fill_gain_k(BlockGain4K& K, stx_buf* img, int w, int h, const stx_buf* gmap, const int* q, float* H, void* yt, int fast)
-{
-    K.img = img ? img->ptr : nullptr; K.stride = img ? (long long)img->stride : 0; K.w = w; K.h = h;
-    K.full_w = q ? q[0] : w; K.full_h = q ? q[1] : h;
-    K.x0 = q ? q[2] : 0; K.y0 = q ? q[3] : 0;
-    K.gmap = (const float*)gmap->ptr; K.gstride = (long long)(gmap->stride / sizeof(float));
-    K.gw = gmap->w; K.gh = gmap->h;
-    K.xscale = 1.0 / ((double)K.full_w / (double)K.gw);
-    K.yscale = 1.0 / ((double)K.full_h / (double)K.gh);
-    K.H = H; K.hstride = (long long)((w + 3) & ~3) * gmap->c;
-    K.yt = (int2*)yt;
-    K.fast = fast;
-}
-
-static void launch_gain_rows(stx_ctx* ctx, const BlockGainBatchK& B, int m, int gc)
-{
-    int mt = 0, mgh = 0;
-    double rows_bytes = 0.0;
-    for (int i = 0; i < m; i++) {
-        mt = std::max(mt, std::max(B.k[i].w, B.k[i].h));
-        mgh = std::max(mgh, B.k[i].gh);
-        rows_bytes += 4.0 * gc * B.k[i].gh * B.k[i].w + 8.0 * B.k[i].h;
-    }
-    StxProfScope prof(ctx, "block_gain_rows", rows_bytes);
-    const dim3 grid((mt + 255) / 256, mgh + 1, m);
-    if (gc == 1) hipLaunchKernelGGL(gain_rows_kernel<1>, grid, dim3(256), 0, ctx->stream, B);
-    else hipLaunchKernelGGL(gain_rows_kernel<3>, grid, dim3(256), 0, ctx->stream, B);
-}
-
-int stx_launch_gain_rows(stx_ctx* ctx, int n, const int* wh, const stx_buf* const* gmaps, const int* full_wh_xy0, float* const* Hs,
-                         void* const* yts)
-{
-    for (int base = 0; base < n; base += GAIN_BATCH) {
-        const int m = std::min(GAIN_BATCH, n - base);
-        BlockGainBatchK B;
-        memset(&B, 0, sizeof(B));
-        for (int i = 0; i < m; i++) {
-            const int g = base + i;
-            fill_gain_k(B.k[i], nullptr, wh[2 * g], wh[2 * g + 1], gmaps[g], full_wh_xy0 ? full_wh_xy0 + 4 * g : nullptr, Hs[g], yts[g], 1);
-        }
-        launch_gain_rows(ctx, B, m, gmaps[base]->c);
-    }
-    return check_launch("block_gain_rows");
-}
-
-// Hs / yts: per image device scratch (gh x hstride x gc floats, h int2), carved by the caller from one allocation
-int stx_launch_block_gain_batch(stx_ctx* ctx, int n, stx_buf* const* imgs, const stx_buf* const* gmaps, const int* full_wh_xy0,
-                                float* const* Hs, void* const* yts, const int* fast)
-{
-    for (int base = 0; base < n; base += GAIN_BATCH) {
-        const int m = std::min(GAIN_BATCH, n - base);
-        const int gc = gmaps[base]->c;
-        BlockGainBatchK B;
-        memset(&B, 0, sizeof(B));
-        int mw = 0, mh = 0;
-        bool all_fast = true;
-        double bytes = 0.0;
-        for (int i = 0; i < m; i++) {
-            const int g = base + i;
-            fill_gain_k(B.k[i], imgs[g], imgs[g]->w, imgs[g]->h, gmaps[g], full_wh_xy0 ? full_wh_xy0 + 4 * g : nullptr, Hs[g], yts[g], fast[g]);
-            all_fast = all_fast && fast[g];
-            mw = std::max(mw, B.k[i].w); mh = std::max(mh, B.k[i].h);
-            bytes += 6.0 * B.k[i].w * B.k[i].h;
-        }
-        launch_gain_rows(ctx, B, m, gc);
-        StxProfScope prof(ctx, "block_gain_apply", bytes);
-        const dim3 grid((mw + 255) / 256, (mh + 15) / 16, m);
-        if (gc == 1 && all_fast) hipLaunchKernelGGL((block_gain4_kernel<1, true>), grid, dim3(256), 0, ctx->stream, B);
-        else if (gc == 1) hipLaunchKernelGGL((block_gain4_kernel<1, false>), grid, dim3(256), 0, ctx->stream, B);
-        else if (all_fast) hipLaunchKernelGGL((block_gain4_kernel<3, true>), grid, dim3(256), 0, ctx->stream, B);
-        else hipLaunchKernelGGL((block_gain4_kernel<3, false>), grid, dim3(256), 0, ctx->stream, B);
-    }
-    return check_launch("block_gain_apply");
+    return stx_check_launch("no_gather");
 }

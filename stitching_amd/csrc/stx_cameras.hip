@@ -183,8 +183,7 @@ int stx_launch_affine_normal_equations(stx_ctx* ctx, int n_edges, const int* d_e
     if (start) STX_HIP(hipEventRecord(start, ctx->stream));
     hipLaunchKernelGGL(affine_normal_equations_kernel, dim3(n_edges), dim3(RAY_WG), 0, ctx->stream, d_edge_cams, d_offsets, d_pts, d_variants,
                        d_out);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return stx_fail(STX_ERR_HIP, "affine_normal_equations launch failed: %s", hipGetErrorString(err));
+    STX_TRY(stx_check_launch("affine_normal_equations"));
     if (stop) STX_HIP(hipEventRecord(stop, ctx->stream));
     return STX_OK;
 }
@@ -196,8 +195,7 @@ int stx_launch_ray_normal_equations(stx_ctx* ctx, int n_edges, const int* d_edge
     if (start) STX_HIP(hipEventRecord(start, ctx->stream));
     hipLaunchKernelGGL(ray_normal_equations_kernel, dim3(n_edges), dim3(RAY_WG), 0, ctx->stream, d_edge_cams, d_offsets, d_pts, d_variants,
                        d_out);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return stx_fail(STX_ERR_HIP, "ray_normal_equations launch failed: %s", hipGetErrorString(err));
+    STX_TRY(stx_check_launch("ray_normal_equations"));
     if (stop) STX_HIP(hipEventRecord(stop, ctx->stream));
     return STX_OK;
 }

@@ -26,13 +26,6 @@ constexpr int CS_BACK = 64;                    // rows per walk-back step
 constexpr int CS_BACK_W = 2 * CS_BACK - 1;     // columns the walk can reach in them
 constexpr uint32_t CS_SENTINEL = 0xFFFFFFFFu;
 
-int cs_check_launch(const char* what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return stx_fail(STX_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
-    return STX_OK;
-}
-
 __device__ inline uint32_t cs_cost(const StxColorSeamPair& P, int r, int t)
 {
     const int x = P.vertical ? t : r, y = P.vertical ? r : t;
@@ -178,9 +171,9 @@ int stx_launch_color_seam_level(stx_ctx* ctx, const StxColorSeamPair* d_pairs, i
         else if (max_cross <= 4 * CS_WG) cs_launch_dp<4, 4>(ctx, Q, np);
         else if (max_cross <= 8 * CS_WG) cs_launch_dp<8, 2>(ctx, Q, np);
         else cs_launch_dp<16, 1>(ctx, Q, np);
-        STX_TRY(cs_check_launch("color_seam_dp"));
+        STX_TRY(stx_check_launch("color_seam_dp"));
     }
     StxProfScope prof(ctx, "color_seam_apply", 0.0);
     hipLaunchKernelGGL(color_seam_apply_kernel, dim3((unsigned)((max_area + CS_WG - 1) / CS_WG), np), dim3(CS_WG), 0, ctx->stream, Q);
-    return cs_check_launch("color_seam_apply");
+    return stx_check_launch("color_seam_apply");
 }

@@ -33,13 +33,6 @@ constexpr int CROP_ROWS_GRID = 2048;       // workgroups of the row stage (grid-
 constexpr int CROP_LDS_MAX_W = 4864;       // rows up to this width keep heights + two pointer arrays in LDS (57 KiB + 5 KiB static)
 constexpr int CROP_BATCH = 8;
 
-int crop_check_launch(const char* what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return stx_fail(STX_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
-    return STX_OK;
-}
-
 struct CropMask { const uint8_t* p; long long stride; int w, h; };
 
 __device__ inline bool crop_on(const CropMask& M, int x, int y) { return M.p[(long long)y * M.stride + x] != 0; }
@@ -340,35 +333,35 @@ STX_EXPORT int stx_crop_lir(stx_ctx* ctx, const stx_buf* mask, int out_xywh[4], 
     {
         StxProfScope prof(ctx, "crop_runs", (double)N * 5);
         hipLaunchKernelGGL(crop_runs_kernel, dim3((H + CROP_WG / 64 - 1) / (CROP_WG / 64)), dim3(CROP_WG), 0, ctx->stream, M, d_lab);
-        STX_TRY(crop_check_launch("crop_runs"));
+        STX_TRY(stx_check_launch("crop_runs"));
     }
     {
         StxProfScope prof(ctx, "crop_merge", (double)N * 2);
         hipLaunchKernelGGL(crop_merge_kernel, px, dim3(CROP_WG), 0, ctx->stream, M, d_lab);
-        STX_TRY(crop_check_launch("crop_merge"));
+        STX_TRY(stx_check_launch("crop_merge"));
     }
     {
         StxProfScope prof(ctx, "crop_count", (double)N * 5);
         hipLaunchKernelGGL(crop_count_kernel, px, dim3(CROP_WG), 0, ctx->stream, M, (const int*)d_lab, d_res);
-        STX_TRY(crop_check_launch("crop_count"));
+        STX_TRY(stx_check_launch("crop_count"));
     }
     // the labels are dead from here: their buffer holds v
     int* d_v = d_lab;
     {
         StxProfScope prof(ctx, "crop_cols", (double)N * 5);
         hipLaunchKernelGGL(crop_cols_kernel, dim3((W + CROP_WG - 1) / CROP_WG), dim3(CROP_WG), 0, ctx->stream, M, d_v);
-        STX_TRY(crop_check_launch("crop_cols"));
+        STX_TRY(stx_check_launch("crop_cols"));
     }
     {
         CropRowsK K{d_v, W, H, (int*)scratch->get(), (CropBest*)best->get()};
         StxProfScope prof(ctx, "crop_rows", (double)N * 4);
         hipLaunchKernelGGL(crop_rows_kernel, dim3(grid), dim3(CROP_WG), in_lds ? sizeof(int) * 3 * (size_t)W : 0, ctx->stream, K);
-        STX_TRY(crop_check_launch("crop_rows"));
+        STX_TRY(stx_check_launch("crop_rows"));
     }
     {
         StxProfScope prof(ctx, "crop_reduce", (double)H * sizeof(CropBest));
         hipLaunchKernelGGL(crop_reduce_kernel, dim3(1), dim3(CROP_WG), 0, ctx->stream, (const CropBest*)best->get(), H, d_res);
-        STX_TRY(crop_check_launch("crop_reduce"));
+        STX_TRY(stx_check_launch("crop_reduce"));
     }
     if (out_info) STX_HIP(hipEventRecord(X.ev[1], ctx->stream));
     int h_res[8] = {0};

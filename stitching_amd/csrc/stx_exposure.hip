@@ -18,13 +18,6 @@ namespace {
 
 constexpr int EXP_WG = 256;
 
-int exp_check_launch(const char* what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return stx_fail(STX_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
-    return STX_OK;
-}
-
 struct ExpStatsK {
     const StxExpImg* imgs;
     const StxExpJob* jobs;
@@ -134,7 +127,7 @@ int stx_launch_exposure_stats(stx_ctx* ctx, const StxExpImg* d_imgs, const StxEx
     K.imgs = d_imgs; K.jobs = d_jobs; K.sqrt_tab = d_sqrt; K.out_i = d_out_i; K.out_d = d_out_d; K.mode = mode;
     StxProfScope prof(ctx, "exposure_stats", algo_bytes);
     hipLaunchKernelGGL(exposure_stats_kernel, dim3(njobs), dim3(EXP_WG), 0, ctx->stream, K);
-    return exp_check_launch("exposure_stats");
+    return stx_check_launch("exposure_stats");
 }
 
 int stx_launch_exposure_block_mul(stx_ctx* ctx, const StxExpBlockMul* d_tab, int n, int max_pixels)
@@ -145,5 +138,5 @@ int stx_launch_exposure_block_mul(stx_ctx* ctx, const StxExpBlockMul* d_tab, int
     const int gx = std::min(64, std::max(1, (max_pixels + EXP_WG - 1) / EXP_WG));
     StxProfScope prof(ctx, "exposure_block_mul", 0.0);
     hipLaunchKernelGGL(exposure_block_mul_kernel, dim3(gx, n), dim3(EXP_WG), 0, ctx->stream, K);
-    return exp_check_launch("exposure_block_mul");
+    return stx_check_launch("exposure_block_mul");
 }

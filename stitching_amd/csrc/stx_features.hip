@@ -13,13 +13,6 @@
 
 namespace {
 
-int feat_check_launch(const char* what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return stx_fail(STX_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
-    return STX_OK;
-}
-
 // the last item whose first tile is <= tile (uniform over the workgroup: scalar loads)
 #define FEAT_FIND(items, n, tile, first, out)                     \
     do {                                                          \
@@ -303,14 +296,14 @@ int stx_launch_feat_grey(stx_ctx* ctx, const StxFeatImage* d_imgs, int n, int ti
 {
     StxProfScope prof(ctx, "feat_grey", algo_bytes);
     hipLaunchKernelGGL(feat_grey_kernel, dim3(tiles), dim3(256), 0, ctx->stream, d_imgs, n);
-    return feat_check_launch("feat_grey");
+    return stx_check_launch("feat_grey");
 }
 
 int stx_launch_feat_blur(stx_ctx* ctx, const StxFeatLevel* d_levels, int n, int tiles, double algo_bytes)
 {
     StxProfScope prof(ctx, "feat_blur", algo_bytes);
     hipLaunchKernelGGL(feat_blur_kernel, dim3(tiles), dim3(512), 0, ctx->stream, d_levels, n);
-    return feat_check_launch("feat_blur");
+    return stx_check_launch("feat_blur");
 }
 
 int stx_launch_feat_score(stx_ctx* ctx, const StxFeatLevel* d_levels, int n, int tiles, int threshold, unsigned long long* d_cand,
@@ -318,7 +311,7 @@ int stx_launch_feat_score(stx_ctx* ctx, const StxFeatLevel* d_levels, int n, int
 {
     StxProfScope prof(ctx, "feat_score", algo_bytes);
     hipLaunchKernelGGL(feat_score_kernel, dim3(tiles), dim3(256), 0, ctx->stream, d_levels, n, threshold, d_cand, d_counts);
-    return feat_check_launch("feat_score");
+    return stx_check_launch("feat_score");
 }
 
 int stx_launch_feat_select(stx_ctx* ctx, const StxFeatSel* d_sel, int n, const unsigned long long* d_cand, unsigned long long* d_tmp,
@@ -326,7 +319,7 @@ int stx_launch_feat_select(stx_ctx* ctx, const StxFeatSel* d_sel, int n, const u
 {
     StxProfScope prof(ctx, "feat_select", 0.0);
     hipLaunchKernelGGL(feat_select_kernel, dim3(n), dim3(256), 0, ctx->stream, d_sel, d_cand, d_tmp, d_keys, d_item);
-    return feat_check_launch("feat_select");
+    return stx_check_launch("feat_select");
 }
 
 int stx_launch_feat_describe(stx_ctx* ctx, const StxFeatLevel* d_levels, int nl, const unsigned long long* d_keys, const int* d_item, int total,
@@ -335,5 +328,5 @@ int stx_launch_feat_describe(stx_ctx* ctx, const StxFeatLevel* d_levels, int nl,
     StxProfScope prof(ctx, "feat_describe", (double)total * (709 + 512 + 36));
     hipLaunchKernelGGL(feat_describe_kernel, dim3((total + 3) / 4), dim3(256), 0, ctx->stream, d_levels, nl, d_keys, d_item, total, d_cxcy,
                        d_patterns, d_bins, d_desc);
-    return feat_check_launch("feat_describe");
+    return stx_check_launch("feat_describe");
 }

@@ -34,6 +34,14 @@ int stx_fail(int code, const char* fmt, ...);
                             #call, hipGetErrorString(e_), __FILE__, __LINE__);                             \
     } while (0)
 
+// after a kernel launch (or a run of them): the launch error, if any, as "<what> launch failed: ..."
+inline int stx_check_launch(const char* what)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return stx_fail(STX_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
+    return STX_OK;
+}
+
 #define STX_TRY(call)           \
     do {                        \
         int rc_ = (call);       \
@@ -269,7 +277,7 @@ struct MbLevelK;
 int stx_launch_mb_level(stx_ctx* ctx, const MbLevelK& K, double algo_bytes);
 int stx_launch_mb_coarse(stx_ctx* ctx, const MbLevelK& K_level_Bm2, double algo_bytes);  // levels B, B-1, B-2 in one launch
 
-// pointwise exposure gain (next row N1) --------------------------------------------------------------
+// pointwise exposure gain (next row N1; stx_gain.hip) --------------------------------------------------------------
 int stx_launch_gain_apply(stx_ctx* ctx, stx_buf* img, const float g[3]);
 int block_gain_check(stx_ctx* ctx, const stx_buf* img, const stx_buf* gain_map);  // img may be null: the map alone
 int stx_launch_block_gain(stx_ctx* ctx, stx_buf* img, const stx_buf* gmap, const int* d_xt, const int* d_yt);
@@ -376,7 +384,7 @@ int stx_launch_ray_normal_equations(stx_ctx* ctx, int n_edges, const int* d_edge
 // the same sums of the affine-partial residual; d_variants: 72 doubles per camera
 int stx_launch_affine_normal_equations(stx_ctx* ctx, int n_edges, const int* d_edge_cams, const long long* d_offsets, const double* d_pts,
                                        const double* d_variants, double* d_out, hipEvent_t start, hipEvent_t stop);
-// cv::resize(INTER_LINEAR_EXACT) u8 (next rows N2 / N3); d_xt / d_yt: device tables of (offset, coeff1 | interior << 16)
+// cv::resize(INTER_LINEAR_EXACT) u8 (next rows N2 / N3; stx_resize.hip); d_xt / d_yt: device tables of (offset, coeff1 | interior << 16)
 int stx_launch_resize_exact(stx_ctx* ctx, const stx_buf* src, stx_buf* dst, const int* d_xt, const int* d_yt, bool dilate,
                             const stx_buf* andmask);
 // the same for n images in one launch: device descriptors, one per image; the grid is the flat list of their STX_RESIZE_TW x
@@ -394,7 +402,7 @@ int stx_launch_seam_resize_batch(stx_ctx* ctx, int n, const stx_buf* const* seam
 // SeamFinder.resize of n images as ONE launch (coefficients made in the kernel, dilation in LDS); full_wh_xy0 as stx_seam_mask_resize_batch_sub
 int stx_launch_seam_resize_lds(stx_ctx* ctx, int n, const stx_buf* const* seams, const stx_buf* const* masks, stx_buf* const* dsts,
                                const int* full_wh_xy0, bool* done);
-// image-strip sharding: pack the columns [x0, x0 + w) of n images + masks into n flat buffers (one launch per 16 strips)
+// image-strip sharding (stx_strips.hip): pack the columns [x0, x0 + w) of n images + masks into n flat buffers (one launch per 16 strips)
 int stx_launch_strip_pack(stx_ctx* ctx, int n, const stx_buf* const* imgs, const stx_buf* const* masks, const int* x0, const int* w,
                           stx_buf* const* dsts, const size_t* si, const size_t* sm, bool mask_bits);
 int stx_launch_strip_bits_expand(stx_ctx* ctx, int n, const uint8_t* const* bits, const size_t* sm, stx_buf* const* masks);

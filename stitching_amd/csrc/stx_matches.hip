@@ -21,13 +21,6 @@
 
 namespace {
 
-int match_check_launch(const char* what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return stx_fail(STX_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
-    return STX_OK;
-}
-
 // ---- two nearest neighbours ----------------------------------------------------------------------------------------------------------
 // LDS: the train descriptors pass through an LDS tile; else every lane loads them from memory at the same address (wave-uniform loads,
 // which the compiler turns into scalar loads): STX_MATCH_TRAIN=uniform, kept for the measurement in profiles/matches.json
@@ -346,7 +339,7 @@ int stx_launch_match_2nn(stx_ctx* ctx, const StxMatchJob* d_jobs, int njobs, int
     StxProfScope prof(ctx, "match_2nn", compares * 32.0);
     if (lds) hipLaunchKernelGGL(match_2nn_kernel<true>, dim3(blocks), dim3(STX_MATCH_NN_WG), 0, ctx->stream, d_jobs, njobs, d_desc, d_nn);
     else hipLaunchKernelGGL(match_2nn_kernel<false>, dim3(blocks), dim3(STX_MATCH_NN_WG), 0, ctx->stream, d_jobs, njobs, d_desc, d_nn);
-    return match_check_launch("match_2nn");
+    return stx_check_launch("match_2nn");
 }
 
 int stx_launch_match_union(stx_ctx* ctx, const StxMatchPair* d_pairs, int np, const uint2* d_nn, const double* d_pts, int ratio_T,
@@ -355,7 +348,7 @@ int stx_launch_match_union(stx_ctx* ctx, const StxMatchPair* d_pairs, int np, co
     StxProfScope prof(ctx, "match_union", 0.0);
     hipLaunchKernelGGL(match_union_kernel, dim3(np), dim3(256), 0, ctx->stream, d_pairs, d_nn, d_pts, (unsigned)ratio_T, d_counts, d_matches,
                        d_xyuv);
-    return match_check_launch("match_union");
+    return stx_check_launch("match_union");
 }
 
 int stx_launch_match_ransac(stx_ctx* ctx, const StxMatchPair* d_pairs, int np, const int* d_counts, const double* d_xyuv, int iters,
@@ -380,7 +373,7 @@ int stx_launch_match_ransac(stx_ctx* ctx, const StxMatchPair* d_pairs, int np, c
     default:
         return stx_fail(STX_ERR_INVALID, "unknown match model %d", model);
     }
-    return match_check_launch("match_ransac");
+    return stx_check_launch("match_ransac");
 }
 
 int stx_launch_match_pick(stx_ctx* ctx, const StxMatchPair* d_pairs, int np, const int* d_counts, const double* d_xyuv, int iters,
@@ -403,5 +396,5 @@ int stx_launch_match_pick(stx_ctx* ctx, const StxMatchPair* d_pairs, int np, con
     default:
         return stx_fail(STX_ERR_INVALID, "unknown match model %d", model);
     }
-    return match_check_launch("match_pick");
+    return stx_check_launch("match_pick");
 }

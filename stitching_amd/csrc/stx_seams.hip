@@ -21,13 +21,6 @@ constexpr int SEAM_STEP = 64 * SEAM_PX;    // pixels per wavefront step
 constexpr int SEAM_BIG = 1 << 28;
 constexpr int SEAM_SAT = 8192;
 
-int seam_check_launch(const char* what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return stx_fail(STX_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
-    return STX_OK;
-}
-
 __device__ inline uint8_t seam_px(const uint8_t* m, long long stride, int w, int h, int x, int y)
 {
     return (x >= 0 && y >= 0 && x < w && y < h) ? m[(long long)y * stride + x] : (uint8_t)0;
@@ -179,10 +172,10 @@ int stx_launch_seam_level(stx_ctx* ctx, const StxSeamPair* d_pairs, int np, int 
         SeamRowsK K{d_pairs, d_arena};
         StxProfScope prof(ctx, "seam_rows", algo_bytes);
         hipLaunchKernelGGL(seam_rows_kernel, dim3((max_rows + SEAM_WG / 64 - 1) / (SEAM_WG / 64), np), dim3(SEAM_WG), 0, ctx->stream, K);
-        STX_TRY(seam_check_launch("seam_rows"));
+        STX_TRY(stx_check_launch("seam_rows"));
     }
     SeamColsK K{d_pairs, d_arena};
     StxProfScope prof(ctx, "seam_cols", 0.0);
     hipLaunchKernelGGL(seam_cols_kernel, dim3((max_cols + SEAM_WG - 1) / SEAM_WG, np), dim3(SEAM_WG), 0, ctx->stream, K);
-    return seam_check_launch("seam_cols");
+    return stx_check_launch("seam_cols");
 }

@@ -36,13 +36,6 @@ constexpr int LU_NB = 32;       // pivots per step
 constexpr int LU_T = 64;        // tile edge of the trailing update
 constexpr int LU_PANEL_WG = 1024;
 
-int lu_check_launch(const char* what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return stx_fail(STX_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
-    return STX_OK;
-}
-
 // the larger magnitude, among equals the smaller row: what the ascending strict-> search of the host finds
 __device__ inline void lu_better(double& v, int& i, double ov, int oi)
 {
@@ -277,7 +270,7 @@ int stx_lu_device(stx_ctx* ctx, int n, const StxLuEntry* ent, size_t count, doub
         STX_HIP(hipMemcpyAsync(d_ent.get(), ent, count * sizeof(StxLuEntry), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(lu_scatter_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, A, lda, (const StxLuEntry*)d_ent.get(),
                            (long long)count);
-        STX_TRY(lu_check_launch("lu_scatter"));
+        STX_TRY(stx_check_launch("lu_scatter"));
     }
     for (int k0 = 0; k0 < n; k0 += LU_NB) {
         hipLaunchKernelGGL(lu_panel_kernel, dim3(1), dim3(LU_PANEL_WG), 0, st, A, lda, n, k0, piv, info);
@@ -289,10 +282,10 @@ int stx_lu_device(stx_ctx* ctx, int n, const StxLuEntry* ent, size_t count, doub
             hipLaunchKernelGGL(lu_trail_kernel, dim3((right + LU_T - 1) / LU_T, (below + LU_T - 1) / LU_T), dim3(256), 0, st, A, lda, n, Nc, k0,
                                (const int*)info);
     }
-    STX_TRY(lu_check_launch("lu elimination"));
+    STX_TRY(stx_check_launch("lu elimination"));
     if (out) STX_HIP(hipEventRecord(E.ev[1], st));
     hipLaunchKernelGGL(lu_count_kernel, dim3((n + 3) / 4), dim3(256), 0, st, (const double*)A, lda, n, (int*)d_cnt.get());
-    STX_TRY(lu_check_launch("lu_count"));
+    STX_TRY(stx_check_launch("lu_count"));
     std::vector<int> cnt(n);
     int h_info = 0;
     STX_HIP(hipMemcpyAsync(cnt.data(), d_cnt.get(), sizeof(int) * n, hipMemcpyDeviceToHost, st));
@@ -316,7 +309,7 @@ int stx_lu_device(stx_ctx* ctx, int n, const StxLuEntry* ent, size_t count, doub
     STX_HIP(hipMemcpyAsync(d_off.get(), off.data(), sizeof(long long) * (n + 1), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(lu_fill_kernel, dim3((n + 3) / 4), dim3(256), 0, st, (const double*)A, lda, n, (const long long*)d_off.get(),
                        (int*)d_cols.get(), (double*)d_vals.get(), (double*)d_b.get());
-    STX_TRY(lu_check_launch("lu_fill"));
+    STX_TRY(stx_check_launch("lu_fill"));
     std::vector<int> cols(nnz);
     std::vector<double> vals(nnz);
     STX_HIP(hipMemcpyAsync(cols.data(), d_cols.get(), sizeof(int) * nnz, hipMemcpyDeviceToHost, st));

@@ -1344,8 +1344,7 @@ int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, cons
         }
     }
     tab.reset();  // stream-ordered reuse
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return stx_fail(STX_ERR_HIP, "warp kernel launch failed: %s", hipGetErrorString(e));
+    STX_TRY(stx_check_launch("warp kernel"));
     if (kept && make_tables) kept->type = TYPE;
     return STX_OK;
 }
@@ -1379,9 +1378,7 @@ int launch_general(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, co
         default: return stx_fail(STX_ERR_INVALID, "no per-pixel kernel for projector family %d", K.family);
         }
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return stx_fail(STX_ERR_HIP, "warp kernel launch failed: %s", hipGetErrorString(e));
-    return STX_OK;
+    return stx_check_launch("warp kernel");
 }
 
 void fill_warpk(const StxWarpLaunch& L, WarpK* Kp, double* bytes)

@@ -249,6 +249,9 @@ int stx_warp_batch_with_rois(stx_ctx* ctx, int type, float scale, int n, const f
 int stx_warp_mask(stx_ctx* ctx, int type, float scale, const float K[9], const float R[9], int w, int h,
                   stx_buf** out_mask, int out_xywh[4]);
 
+/* the widest image the feather blender takes (stx_blend_feed) */
+#define STX_FEATHER_MAX_WIDTH 32768
+
 /* ---- Blender ------------------------------------------------------------------------
  * stx_result_roi    <- stitching/blender.py:24    cv.detail.resultRoi(corners, sizes)
  * stx_blend_create  <- stitching/blender.py:27-38 Blender_createDefault(NO) | detail_MultiBandBlender()
@@ -258,7 +261,10 @@ int stx_warp_mask(stx_ctx* ctx, int type, float scale, const float K[9], const f
  *                      img: u8x3 (converted on load) or s16x3; mask u8x1.  DEFERRED for all three kinds: the blender
  *                      keeps a reference to img and mask and reads them in stx_blend_finish (one gather over the
  *                      panorama), so the two buffers must not be modified between feed and finish (OpenCV consumes
- *                      them inside feed)
+ *                      them inside feed).  Limit of the feather blender, checked before anything is allocated or
+ *                      launched (STX_ERR_INVALID): an image of at most STX_FEATHER_MAX_WIDTH columns — the row pass of
+ *                      its distance transform keeps a row in LDS, 2 bytes per column; the refused feed leaves the
+ *                      blender as it was
  * stx_blend_finish  <- stitching/blender.py:43-48 blender.blend() + cv.convertScaleAbs(result)
  *                      returns the u8x3 panorama and the u8 mask; consumes the blender
  *                      (a second finish is STX_ERR_STATE; OpenCV releases dst_ in blend). */

@@ -1210,6 +1210,10 @@ int stx_launch_feather_weights(stx_ctx* ctx, const FeatherImg* d_imgs, const Fea
         max_w = std::max(max_w, h_imgs[i].w); max_h = std::max(max_h, h_imgs[i].h); max_chunks = std::max(max_chunks, h_imgs[i].n_chunks);
         px += (double)h_imgs[i].w * h_imgs[i].h;
     }
+    // row pass, LDS: 2 bytes per pixel and row, at most 64 KB per workgroup (1 / 2 / 4 rows; stx_internal.h).  Every image of the
+    // table passed stx_feather_refuse_width in stx_blend_feed_ex, so there is at least one row
+    const int lds_pitch = stx_feather_lds_pitch(max_w);
+    const int rows = stx_feather_rows_per_block(max_w);
     {
         StxProfScope prof(ctx, "feather_dt_cols", px * (1 + 0.25 + 2));
         hipLaunchKernelGGL(dt_col_summary_batch_kernel, dim3((max_w + 255) / 256, max_chunks, n), dim3(64), 0, ctx->stream, d_imgs);
@@ -1218,9 +1222,6 @@ int stx_launch_feather_weights(stx_ctx* ctx, const FeatherImg* d_imgs, const Fea
     }
     {
         StxProfScope prof(ctx, "feather_dt_rows", px * (2 + 2));
-        // LDS: 2 bytes per pixel and row, at most 64 KB per workgroup (1 / 2 / 4 rows)
-        const int lds_pitch = ((max_w + 511) / 512) * 64;  // 16-byte slots per row
-        const int rows = lds_pitch * 16 * 4 <= 65536 ? 4 : (lds_pitch * 16 * 2 <= 65536 ? 2 : 1);
         hipLaunchKernelGGL(dt_rows_batch_kernel, dim3((max_h + rows - 1) / rows, n), dim3(256), (size_t)lds_pitch * 16 * rows, ctx->stream,
                            d_imgs, rows, lds_pitch);
     }

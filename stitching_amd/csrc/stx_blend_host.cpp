@@ -371,6 +371,8 @@ STX_EXPORT int stx_blend_feed_ex(stx_blender* b, const stx_buf* img, const stx_b
     if (tlx < b->rx || tly < b->ry || tlx + img->w > ux || tly + img->h > uy)
         return stx_fail(STX_ERR_INVALID, "feed: image at (%d,%d) size %dx%d leaves the prepared roi (%d,%d,%d,%d)", tlx, tly,
                         img->w, img->h, b->rx, b->ry, ux - b->rx, uy - b->ry);
+    // the row pass of the feather blender's distance transform holds a whole row in LDS (stx_internal.h: stx_feather_rows_per_block)
+    if (b->kind == STX_BLEND_FEATHER) STX_TRY(stx_feather_refuse_width(img->w));
     if (order < 0) order = b->next_order;
     b->next_order = std::max(b->next_order, order + 1);
     if (b->kind == STX_BLEND_MULTIBAND) return mb_feed(b, img, mask, tlx, tly, order);

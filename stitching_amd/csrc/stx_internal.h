@@ -411,6 +411,25 @@ int stx_launch_strip_bits_expand(stx_ctx* ctx, int n, const uint8_t* const* bits
 // sharded feather blender sizes its halo by it (stx_debug_feather_dist_cap -> distributed.FEATHER_DIST_CAP, checked by a host test)
 constexpr int STX_FEATHER_DIST_CAP = 8192;
 constexpr int STX_DT_RC = 64;  // rows per chunk of the distance transform's column pass (stx_blend.hip: DT_RC)
+// dt_rows_batch_kernel keeps a row's forward sweep in LDS, one 16-byte slot per 8 pixels over whole 512-pixel steps (2 bytes per column),
+// and a workgroup takes 4, 2 or 1 rows, whichever fits STX_FEATHER_LDS_BYTES.  0 rows: the image is too wide for the kernel —
+// stx_blend_feed_ex refuses it with stx_feather_refuse_width, so the launcher never meets one.  The widest image with a row per
+// workgroup is STX_FEATHER_MAX_WIDTH (include/stitching_amd.h), which the assertion below holds to this arithmetic
+constexpr int STX_FEATHER_LDS_BYTES = 65536;
+constexpr int stx_feather_lds_pitch(int w) { return ((w + 511) / 512) * 64; }  // 16-byte slots per row
+constexpr int stx_feather_rows_per_block(int w)
+{
+    return stx_feather_lds_pitch(w) * 16 * 4 <= STX_FEATHER_LDS_BYTES ? 4
+         : stx_feather_lds_pitch(w) * 16 * 2 <= STX_FEATHER_LDS_BYTES ? 2
+         : stx_feather_lds_pitch(w) * 16 <= STX_FEATHER_LDS_BYTES ? 1 : 0;
+}
+static_assert(stx_feather_rows_per_block(STX_FEATHER_MAX_WIDTH) == 1 && stx_feather_rows_per_block(STX_FEATHER_MAX_WIDTH + 1) == 0, "feather width limit");
+// STX_OK, or the refusal of an image w columns wide: the one text for the limit
+inline int stx_feather_refuse_width(int w)
+{
+    if (stx_feather_rows_per_block(w) > 0) return STX_OK;
+    return stx_fail(STX_ERR_INVALID, "feed: the feather blender takes images up to %d columns wide, this one has %d", STX_FEATHER_MAX_WIDTH, w);
+}
 // feather blender as a deferred gather: device table of the fed images, in feed order
 struct FeatherImg {
     const uint8_t* img; long long istride; int is_s16;

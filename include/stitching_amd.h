@@ -522,6 +522,16 @@ int stx_ray_problem_eval(stx_ray_problem* problem, int n_cams, const double* var
  * stx_ray_problem_eval.  Multiplies, adds and subtractions only.  tests/numpy_affine.py is the contract, in the bits of all 45 sums
  * (DESIGN.md section 18).  variants[n_cams * 72] -> out[45 e]; out_info and the refusals as stx_ray_problem_eval's. */
 int stx_affine_problem_eval(stx_ray_problem* problem, int n_cams, const double* variants, double* out, double out_info[4]);
+/* The normal equations of CameraSolver's reprojection adjustment (model="reproj"; the project's own, not cv.detail.BundleAdjusterReproj),
+ * on a problem made by stx_ray_problem_create from centred points.  A camera has 7 parameters — focal f, the principal point's offset
+ * (cx, cy) from the image centre, the aspect a, a Rodrigues vector — and 15 variants of 18 doubles {P = R K^-1, Q = K R^T, row-major},
+ * K = [[f, 0, cx], [0, f a, cy], [0, 0, 1]]: its parameters, then + and - 1e-3 on each of the seven (made by the caller).  Per match
+ * X = P_i (x, y, 1), Y = Q_j X, the residual (u - Y0 / Y2, v - Y1 / Y2) in image j's pixels (IEEE divide, no case of its own for
+ * Y2 <= 0) and its 2 x 14 Jacobian by central differences over the variants; per edge E = sum r.r, g[14] = sum J^T r and the upper
+ * triangle B[105] of sum J^T J, row-major, in the same order of summation as stx_ray_problem_eval.  tests/numpy_reproj.py is the
+ * contract, in the bits of all 120 sums.  variants[n_cams * 270] -> out[120 e]; an edge without matches gives
+ * 120 zeros; out_info and the refusals as stx_ray_problem_eval's. */
+int stx_reproj_problem_eval(stx_ray_problem* problem, int n_cams, const double* variants, double* out, double out_info[4]);
 int stx_ray_problem_free(stx_ray_problem* problem);
 /* stx_resize_linear_exact <- stitching/images.py:122-124 cv.resize(img, size, interpolation=cv.INTER_LINEAR_EXACT) (u8x1 / u8x3:
  *                            the final-resolution resize of Images.resize, next row N3)

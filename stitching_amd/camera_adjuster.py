@@ -2,12 +2,15 @@
 
 Without `solver=` it is the reference's class: the name picks cv.detail's BundleAdjusterRay / Reproj / AffinePartial / NoBundleAdjuster —
 OpenCV's, on the host.  With `solver=CameraSolver()` the cameras are refined by the project's own ray adjustment on the device.  That
-adjustment answers to no name here: "ray" stays cv2's; "reproj" has no counterpart, "affine" goes with a solver only where that solver's
-own `model` is "affine", and no refinement mask other than "xxxxx" has one (all of focal and rotation move; the principal point and the
-aspect are not parameters).
+adjustment answers to no name here: "ray" stays cv2's; "affine" and "reproj" go with a solver only where that solver's own `model` is
+"affine" or "reproj".  A refinement mask other than "xxxxx" goes with a solver of the model "reproj" alone, whose parameters include
+the principal point and the aspect (CameraSolver(model="reproj"): the project's own reprojection adjustment, not
+cv.detail.BundleAdjusterReproj); it is handed to the solver's adjust with every call.  The rotation and the affine solver move all of
+their parameters and refuse any other mask.
 """
 import numpy as np
 
+from .camera_estimation import free_parameters
 from .stitching_error import StitchingError
 
 
@@ -33,13 +36,13 @@ class CameraAdjuster:
         self.solver = solver
         self.adjuster = None
         self.kind, self.confidence_threshold = adjuster, confidence_threshold
+        self.refinement_mask = refinement_mask
         if solver is not None:
-            if adjuster == "reproj" or (adjuster == "affine" and getattr(solver, "model", None) != "affine"):
+            if adjuster in ("reproj", "affine") and getattr(solver, "model", None) != adjuster:
                 raise StitchingError(f'the "{adjuster}" camera adjuster has no counterpart in the solver: it adjusts rays')
             if adjuster not in self.CAMERA_ADJUSTER_CHOICES:
                 raise StitchingError(f"unknown camera adjuster {adjuster!r}")
-            if refinement_mask != self.DEFAULT_REFINEMENT_MASK:
-                raise StitchingError(f'the solver moves focal and rotation of every camera: refinement mask "xxxxx" only, got {refinement_mask!r}')
+            self.set_refinement_mask(refinement_mask)
             return
         cv = _cv()
         choices = {"ray": cv.detail_BundleAdjusterRay, "reproj": cv.detail_BundleAdjusterReproj,
@@ -50,8 +53,11 @@ class CameraAdjuster:
 
     def set_refinement_mask(self, refinement_mask):
         if self.solver is not None:
-            if refinement_mask != self.DEFAULT_REFINEMENT_MASK:
+            if getattr(self.solver, "model", None) == "reproj":
+                free_parameters(refinement_mask)  # five of "x" / "_", or refused
+            elif refinement_mask != self.DEFAULT_REFINEMENT_MASK:
                 raise StitchingError(f'the solver moves focal and rotation of every camera: refinement mask "xxxxx" only, got {refinement_mask!r}')
+            self.refinement_mask = refinement_mask
             return
         cells = np.zeros((3, 3), np.uint8)
         for k, (r, c) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2))):
@@ -63,6 +69,9 @@ class CameraAdjuster:
         if self.solver is not None:
             if self.kind == "no":
                 return estimated_cameras
+            if getattr(self.solver, "model", None) == "reproj":
+                return self.solver.adjust(features, pairwise_matches, estimated_cameras, conf_thresh=float(self.confidence_threshold),
+                                          refinement_mask=self.refinement_mask)
             return self.solver.adjust(features, pairwise_matches, estimated_cameras, conf_thresh=float(self.confidence_threshold))
         ok, refined = self.adjuster.apply(features, pairwise_matches, estimated_cameras)
         if not ok:

@@ -16,6 +16,11 @@ With model="affine" the same solver registers scans and flat tiles: a camera is 
 image pixels to the panorama plane, focal = 1, ppx = ppy = 0, as the affine warper takes it), estimated along the same spanning tree
 and refined as a similarity (a, b, tx, ty) by the same Levenberg-Marquardt loop over a residual in pixels; tests/numpy_affine.py is
 that contract and DESIGN.md section 18 the description.
+
+With model="reproj" the registration is the rotation model's except for the adjustment: 7 parameters per camera (focal, the principal
+point, the aspect, the Rodrigues vector) over the reprojection error in pixels, 120 sums per edge from one launch of a (edges, 3) grid,
+and a refinement mask that holds focal, principal point or aspect where they started; tests/numpy_reproj.py is that contract and
+DESIGN.md section 19 the description.
 """
 import ctypes as C
 import math
@@ -30,7 +35,8 @@ from .match_estimation import centred_points, level0_points
 from .stitching_error import StitchingError, StitchingWarning
 
 STEP = 1e-3  # of the central differences, on every parameter
-MODELS = ("rotation", "affine")
+MODELS = ("rotation", "affine", "reproj")
+FULL_MASK = "xxxxx"  # the refinement mask under which every parameter moves
 _UNSET = object()  # a wave_correct that was not passed: "horiz" for rotations, "no" for the affine model
 WAVE_KINDS = ("horiz", "vert", "no")
 NO_MATCH_MESSAGE = ("No match exceeds the given confidence threshold. Do your images have enough overlap and common features? If yes, "
@@ -38,7 +44,16 @@ NO_MATCH_MESSAGE = ("No match exceeds the given confidence threshold. Do your im
 NOT_ALL_MESSAGE = ("Not all images are included in the final panorama. If this is not intended, use the 'matches_graph_dot_file' "
                    "parameter to analyze your matches. You might want to lower the 'confidence_threshold' or try another 'detector' to "
                    "include all your images.")
-_TRI = np.triu_indices(8)
+_TRI = {4: np.triu_indices(8), 7: np.triu_indices(14)}  # parameters per camera -> the upper triangle of an edge's block
+_MASK_CELL = (0, 2, 4, 3)  # focal, ppx, ppy, aspect -> their characters of a refinement mask (1 is the skew, which is no parameter)
+
+
+def free_parameters(mask):
+    """the indices 0 .. 6 of the reprojection model's parameters (focal, ppx, ppy, aspect, rx, ry, rz) that move under a refinement mask,
+    ascending; the rotation always does"""
+    if not isinstance(mask, str) or len(mask) != 5 or any(ch not in "x_" for ch in mask):
+        raise StitchingError(f"refinement mask {mask!r}: five characters, each 'x' (refined) or '_' (held)")
+    return [k for k in range(4) if mask[_MASK_CELL[k]] == "x"] + [4, 5, 6]
 
 
 # ---- subset ------------------------------------------------------------------------------------------------------------------------------
@@ -286,6 +301,36 @@ def similarity_variants(params):
     return out
 
 
+def reproj_variants(params):
+    """(n, 15, 18) float64 for params (n, 7) rows focal, cx, cy, aspect, rx, ry, rz (cx, cy: the principal point relative to the image
+    centre): per camera its parameters, then + and - STEP on each of the seven (+ before -); a variant is P = R(r') K'^-1 and
+    Q = K' R(r')^T, row-major, K' = [[f, 0, cx], [0, f a, cy], [0, 0, 1]], in the contract's order of operations."""
+    params = np.ascontiguousarray(params, np.float64).reshape(-1, 7)
+    n = len(params)
+    shifts = np.zeros((15, 7), np.float64)
+    for k in range(7):
+        shifts[1 + 2 * k, k], shifts[2 + 2 * k, k] = STEP, -STEP
+    out = np.zeros((n, 15, 18), np.float64)
+    with np.errstate(all="ignore"):
+        moved = params[:, None, :] + shifts[None, :, :]
+        f, cx, cy, a = (moved[:, :, k] for k in range(4))
+        fa = f * a
+        s0, s1, t0, t1 = 1.0 / f, 1.0 / fa, -(cx / f), -(cy / fa)
+        R = np.zeros((n, 15, 3, 3), np.float64)
+        for c in range(n):
+            for v in range(15):
+                R[c, v] = rotation_matrix(moved[c, v, 4:])
+        P, Q = out[:, :, :9].reshape(n, 15, 3, 3), out[:, :, 9:].reshape(n, 15, 3, 3)
+        for c in range(3):
+            P[:, :, c, 0] = R[:, :, c, 0] * s0
+            P[:, :, c, 1] = R[:, :, c, 1] * s1
+            P[:, :, c, 2] = (R[:, :, c, 0] * t0 + R[:, :, c, 1] * t1) + R[:, :, c, 2]
+            Q[:, :, 0, c] = f * R[:, :, c, 0] + cx * R[:, :, c, 2]
+            Q[:, :, 1, c] = fa * R[:, :, c, 1] + cy * R[:, :, c, 2]
+            Q[:, :, 2, c] = R[:, :, c, 2]
+    return out
+
+
 # ---- the ray problem on the device ---------------------------------------------------------------------------------------------------------
 def ray_edges(matches, n, conf_thresh):
     """the pairs i < j whose confidence is above conf_thresh, ascending"""
@@ -313,7 +358,8 @@ class RayProblem:
     as a context manager: the handle must go before its context does."""
 
     def __init__(self, edges, offsets, xyuv, ctx=None, model="rotation"):
-        """model "affine": the edges are the same; an evaluation takes (n, 9, 8) similarity variants (stx_affine_problem_eval)"""
+        """model "affine": the edges are the same; an evaluation takes (n, 9, 8) similarity variants (stx_affine_problem_eval); model
+        "reproj": (n, 15, 18) variants, 120 sums an edge (stx_reproj_problem_eval)"""
         self.ctx = ctx or get_context()
         self.model = model
         self.n_edges = len(edges)
@@ -327,13 +373,17 @@ class RayProblem:
         self.info = None
 
     def evaluate(self, variants):
-        """(n, 9, 10) variants -> (e, 45) float64 sums E, g[8], B[36] of every edge; one launch, one wait"""
+        """(n, 9, 10) variants -> (e, 45) float64 sums E, g[8], B[36] of every edge ("reproj": (n, 15, 18) -> (e, 120), E, g[14], B[105]);
+        one launch, one wait"""
         variants = np.ascontiguousarray(variants, np.float64)
         if self.model == "affine" and (variants.ndim != 3 or variants.shape[1:] != (9, 8)):
             raise StitchingError(f"variants of shape {variants.shape}: the affine adjustment takes (cameras, 9, 8)")
-        out, info = np.zeros((self.n_edges, 45), np.float64), np.zeros(4, np.float64)
+        if self.model == "reproj" and (variants.ndim != 3 or variants.shape[1:] != (15, 18)):
+            raise StitchingError(f"variants of shape {variants.shape}: the reprojection adjustment takes (cameras, 15, 18)")
+        out, info = np.zeros((self.n_edges, 120 if self.model == "reproj" else 45), np.float64), np.zeros(4, np.float64)
         dp = C.POINTER(C.c_double)
-        entry = self.ctx._lib.stx_affine_problem_eval if self.model == "affine" else self.ctx._lib.stx_ray_problem_eval
+        entry = {"affine": self.ctx._lib.stx_affine_problem_eval, "reproj": self.ctx._lib.stx_reproj_problem_eval}.get(
+            self.model, self.ctx._lib.stx_ray_problem_eval)
         _lib.check(entry(self._h, int(variants.shape[0]), variants.ctypes.data_as(dp), out.ctypes.data_as(dp), info.ctypes.data_as(dp)))
         self.info = {"edges": int(info[0]), "matches": int(info[1]), "device_ms": float(info[2]), "device_ms_with_copy": float(info[3])}
         return out
@@ -350,16 +400,18 @@ class RayProblem:
         self.free()
 
 
-def assemble_system(n, edges, sums):
-    """E, g (4n,), A (4n, 4n) from the (e, 45) sums of the edges, added in ascending order; each 8 x 8 block mirrored to its lower half"""
-    A, g, E = np.zeros((4 * n, 4 * n), np.float64), np.zeros(4 * n, np.float64), 0.0
+def assemble_system(n, edges, sums, width=4):
+    """E, g (4n,), A (4n, 4n) from the (e, 45) sums of the edges, added in ascending order; each 8 x 8 block mirrored to its lower half.
+    width = 7 (the reprojection model): 7n unknowns from (e, 120) sums, blocks of 14 x 14"""
+    w, tri = width, _TRI[width]
+    A, g, E = np.zeros((w * n, w * n), np.float64), np.zeros(w * n, np.float64), 0.0
     for (i, j), row in zip(edges, sums):
-        block = np.zeros((8, 8), np.float64)
-        block[_TRI] = row[9:]
-        block.T[_TRI] = row[9:]
-        at = np.r_[4 * i:4 * i + 4, 4 * j:4 * j + 4]
+        block = np.zeros((2 * w, 2 * w), np.float64)
+        block[tri] = row[1 + 2 * w:]
+        block.T[tri] = row[1 + 2 * w:]
+        at = np.r_[w * i:w * i + w, w * j:w * j + w]
         A[np.ix_(at, at)] += block
-        g[at] += row[1:9]
+        g[at] += row[1:1 + 2 * w]
         E = E + row[0]
     return E, g, A
 
@@ -411,18 +463,26 @@ class CameraSolver:
     the spanning tree (R is the 3 x 3 map from image pixels to the panorama plane, focal = 1, ppx = ppy = 0); adjust refines a
     similarity a, b, tx, ty per camera over the residual (u, v) - T_j^-1 T_i (x, y) in pixels, one launch a step as well; there is no
     wave correction (a wave_correct that is not passed means "no", "horiz" and "vert" are refused).  tests/numpy_affine.py is that
-    contract; DESIGN.md section 18."""
+    contract; DESIGN.md section 18.
+
+    model="reproj" (frames cropped off-centre, pixels that are not square): subset, estimate, correct and register are the rotation
+    model's; adjust refines focal, principal point, aspect and Rodrigues vector of every camera over the reprojection error
+    (u, v) - project(K_j R_j^T R_i K_i^-1 (x, y, 1)) in pixels, 120 sums an edge from one launch a step.  refinement_mask: five
+    characters "x" (refined) or "_" (held) in the reference's cell order — focal, skew (no parameter: ignored), ppx, aspect, ppy; held
+    parameters come back exactly as they went in, the rotation always moves.  It is the project's own algorithm, not
+    cv.detail.BundleAdjusterReproj.  tests/numpy_reproj.py is that contract; DESIGN.md section 19."""
 
     MAX_CAMERAS, MAX_MATCHES = _lib.RAY_MAX_CAMERAS, _lib.RAY_MAX_MATCHES
 
-    def __init__(self, conf_thresh=1.0, wave_correct=_UNSET, max_evals=100, model="rotation"):
+    def __init__(self, conf_thresh=1.0, wave_correct=_UNSET, max_evals=100, model="rotation", refinement_mask=FULL_MASK):
         if model not in MODELS:
             raise StitchingError(f"unknown camera model {model!r}: the solver takes {MODELS}")
+        self.model = model
+        self.refinement_mask = self._check_mask(refinement_mask)
         if wave_correct is _UNSET:
             wave_correct = "no" if model == "affine" else "horiz"
         elif model == "affine" and wave_correct in ("horiz", "vert"):
             raise StitchingError(f'the affine camera model has no wave correction: "no" only, got {wave_correct!r}')
-        self.model = model
         if wave_correct == "auto":
             raise StitchingError('wave correction "auto" is cv2\'s: the solver takes "horiz", "vert" or "no"')
         if wave_correct not in WAVE_KINDS:
@@ -471,7 +531,22 @@ class CameraSolver:
         return CameraParams(focal=1.0, aspect=1.0, ppx=0.0, ppy=0.0, R=np.asarray(T).astype(np.float32))
 
     def _variants(self, params):
-        return similarity_variants(params) if self.model == "affine" else camera_variants(params)
+        return {"affine": similarity_variants, "reproj": reproj_variants}.get(self.model, camera_variants)(params)
+
+    @property
+    def _width(self):
+        """parameters per camera"""
+        return 7 if self.model == "reproj" else 4
+
+    def _check_mask(self, mask):
+        """the mask, where this model has a counterpart for it"""
+        if self.model != "reproj":
+            if mask != FULL_MASK:
+                raise StitchingError(f'the {self.model} camera model moves all of its parameters: refinement mask "xxxxx" only, got {mask!r} '
+                                     '(model="reproj" holds focal, principal point or aspect)')
+            return mask
+        free_parameters(mask)
+        return mask
 
     def _check_count(self, n):
         if n > self.MAX_CAMERAS:
@@ -486,14 +561,15 @@ class CameraSolver:
         if evaluate is None:
             return problem.evaluate(variants)
         E, g, B = evaluate(params, variants)
-        return np.concatenate([np.asarray(E).reshape(-1, 1), np.asarray(g).reshape(-1, 8), np.asarray(B).reshape(-1, 36)], axis=1)
+        w = self._width
+        return np.concatenate([np.asarray(E).reshape(-1, 1), np.asarray(g).reshape(-1, 2 * w), np.asarray(B).reshape(-1, w * (2 * w + 1))], axis=1)
 
     def _check_params(self, params, n):
-        params = np.array(params, np.float64).reshape(-1, 4)
+        params = np.array(params, np.float64).reshape(-1, self._width)
         if len(params) != n:
             raise StitchingError(f"{len(params)} parameter rows for {n} cameras")
         if not np.isfinite(params).all():
-            what = "a, b, tx, ty" if self.model == "affine" else "focal and Rodrigues vector"
+            what = {"affine": "a, b, tx, ty", "reproj": "focal, principal point, aspect and Rodrigues vector"}.get(self.model, "focal and Rodrigues vector")
             raise StitchingError(f"camera adjustment needs finite parameters ({what} per camera)")
         return params
 
@@ -509,36 +585,51 @@ class CameraSolver:
 
     def normal_equations(self, features, matches, params, ctx=None):
         """E (e,), g (e, 8) and the upper triangle B (e, 36) of the normal equations of every edge (the pairs i < j with confidence above
-        conf_thresh, ascending) at params (n, 4) rows focal, rx, ry, rz (model "affine": a, b, tx, ty) — one launch on the device."""
+        conf_thresh, ascending) at params (n, 4) rows focal, rx, ry, rz (model "affine": a, b, tx, ty) — one launch on the device.  Model
+        "reproj": params (n, 7) rows focal, cx, cy, aspect, rx, ry, rz (cx, cy relative to the image centre) -> E (e,), g (e, 14), B (e, 105)."""
         features = list(features)
         params = self._check_params(params, len(features))
         edges, offsets, xyuv = self._problem(features, matches)
         with RayProblem(edges, offsets, xyuv, ctx, self.model) as problem:
             sums = problem.evaluate(self._variants(params))
             self.info = dict(problem.info, evaluations=1)
-        return sums[:, 0].copy(), sums[:, 1:9].copy(), sums[:, 9:].copy()
+        w = 2 * self._width
+        return sums[:, 0].copy(), sums[:, 1:1 + w].copy(), sums[:, 1 + w:].copy()
 
-    def adjust(self, features, matches, cameras, ctx=None, conf_thresh=None, evaluate=None):
-        """conf_thresh: in place of the solver's own, for this call.  evaluate(params, variants) -> (E, g, B) per edge: takes the device's place
+    def adjust(self, features, matches, cameras, ctx=None, conf_thresh=None, evaluate=None, refinement_mask=None):
+        """conf_thresh: in place of the solver's own, for this call; refinement_mask alike (model "reproj").  evaluate(params, variants) -> (E, g, B) per edge: takes the device's place
         (measurements and tests of the host steps); everything else, the rejection of steps to variants that are not finite included,
         is as with the device."""
         features, cameras = list(features), list(cameras)
         n = len(features)
         if len(cameras) != n:
             raise StitchingError(f"{len(cameras)} cameras for {n} images")
+        mask = self.refinement_mask if refinement_mask is None else self._check_mask(refinement_mask)
+        free = None
         if self.model == "affine":
             start = self._check_params([similarity_parameters(c.R) for c in cameras], n)
+        elif self.model == "reproj":
+            sizes = [f.img_size for f in features]
+            start = self._check_params([[c.focal, c.ppx - w0 / 2, c.ppy - h0 / 2, c.aspect] + list(rotation_vector(c.R))
+                                        for c, (w0, h0) in zip(cameras, sizes)], n)
+            if mask != FULL_MASK:
+                free = np.array([7 * c + k for c in range(n) for k in free_parameters(mask)])
         else:
             start = self._check_params([[c.focal] + list(rotation_vector(c.R)) for c in cameras], n)
         edges, offsets, xyuv = self._problem(features, matches, conf_thresh)
         if evaluate is not None:
-            params, info = self._levenberg_marquardt(None, evaluate, edges, start)
+            params, info = self._levenberg_marquardt(None, evaluate, edges, start, free)
         else:
             with RayProblem(edges, offsets, xyuv, ctx, self.model) as problem:
-                params, info = self._levenberg_marquardt(problem, None, edges, start)
+                params, info = self._levenberg_marquardt(problem, None, edges, start, free)
         info["edges"], info["matches"] = len(edges), int(offsets[-1])
+        if self.model == "reproj":
+            info["refinement_mask"], info["start"] = mask, start
         self.info = info
-        failed = ((params[:, 0] == 0) & (params[:, 1] == 0)).any() if self.model == "affine" else (params[:, 0] <= 0).any()
+        if self.model == "affine":
+            failed = ((params[:, 0] == 0) & (params[:, 1] == 0)).any()
+        else:
+            failed = (params[:, 0] <= 0).any() or (self.model == "reproj" and (params[:, 3] <= 0).any())
         if not np.isfinite(params).all() or failed:
             raise StitchingError("Camera parameters adjusting failed.")
         _, centre = spanning_tree(matches, n)
@@ -548,12 +639,22 @@ class CameraSolver:
             Ts = [similarity_matrix(p) for p in params]
             back = np.linalg.inv(Ts[centre])
             return [self._affine_camera(back @ T) for T in Ts]
+        if self.model == "reproj":
+            Rs = [rotation_matrix(p[4:7]) for p in params]
+            back = np.linalg.inv(Rs[centre])
+            out = []
+            for (w0, h0), p, R in zip(sizes, params, Rs):
+                out.append(CameraParams(focal=float(p[0]), aspect=float(p[3]), ppx=w0 / 2 + float(p[1]), ppy=h0 / 2 + float(p[2]),
+                                        R=(back @ R).astype(np.float32)))
+            return out
         Rs = [rotation_matrix(p[1:4]) for p in params]
         back = np.linalg.inv(Rs[centre])
         return [self._camera(f, float(p[0]), back @ R) for f, p, R in zip(features, params, Rs)]
 
-    def _levenberg_marquardt(self, problem, evaluate_sums, edges, p):
-        n = len(p)
+    def _levenberg_marquardt(self, problem, evaluate_sums, edges, p, free=None):
+        """free: the indices of the flat parameter vector that move (None: all of them); the rows and columns of the others are taken
+        out of the system, and they are never written"""
+        n, width = len(p), self._width
         info = {"evaluations": 1, "accepted": 0, "device_ms": 0.0, "device_ms_with_copy": 0.0}
 
         def evaluate(q):
@@ -563,7 +664,7 @@ class CameraSolver:
             if problem is not None:
                 info["device_ms"] += problem.info["device_ms"]
                 info["device_ms_with_copy"] += problem.info["device_ms_with_copy"]
-            return assemble_system(n, edges, sums)
+            return assemble_system(n, edges, sums, width)
 
         with np.errstate(all="ignore"):
             first = evaluate(p)
@@ -574,12 +675,17 @@ class CameraSolver:
             lam = 1e-3
             while info["evaluations"] < self.max_evals:
                 better = False
+                Af, gf = (A, g) if free is None else (A[np.ix_(free, free)], g[free])
                 try:
-                    step = np.linalg.solve(A + lam * np.diag(np.diag(A)), -g)
+                    step = np.linalg.solve(Af + lam * np.diag(np.diag(Af)), -gf)
                 except np.linalg.LinAlgError:
                     step = None
                 if step is not None:
-                    q = p + step.reshape(n, 4)
+                    if free is None:
+                        q = p + step.reshape(n, width)
+                    else:
+                        q = p.copy()
+                        q.reshape(-1)[free] = p.reshape(-1)[free] + step
                     moved = evaluate(q)
                     if moved is not None:
                         E2, g2, A2 = moved

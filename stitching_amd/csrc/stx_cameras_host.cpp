@@ -1,6 +1,7 @@
-// stx_cameras_host.cpp — host side of CameraSolver's ray bundle adjustment (the project's own solver, not cv.detail.BundleAdjusterRay):
+// stx_cameras_host.cpp — host side of CameraSolver's bundle adjustments (the project's own solver, not cv.detail.BundleAdjusterRay):
 // a problem handle that keeps the edges and their points on the device, and one evaluation of the normal equations per call
-// (stx_cameras.hip): upload of the variants, one launch, one wait.  tests/numpy_cameras.py is the contract; DESIGN.md section 17.
+// (stx_cameras.hip): upload of the variants, one launch, one wait.  tests/numpy_cameras.py is the contract; the
+// affine and the reprojection adjustment (tests/numpy_affine.py, tests/numpy_reproj.py; sections 18 and 19) evaluate on the same handle.
 #include <algorithm>
 #include <cmath>
 
@@ -34,8 +35,9 @@ STX_EXPORT int stx_ray_problem_create(stx_ctx* ctx, int n_edges, const int* edge
         STX_TRY(stx_dev_alloc(ctx, (size_t)n_edges * 2 * sizeof(int), &P->d_edge_cams));
         STX_TRY(stx_dev_alloc(ctx, ((size_t)n_edges + 1) * sizeof(long long), &P->d_offsets));
         STX_TRY(stx_dev_alloc(ctx, std::max<size_t>((size_t)total * 4 * sizeof(double), 8), &P->d_pts));
-        STX_TRY(stx_dev_alloc(ctx, (size_t)P->min_cams * 90 * sizeof(double), &P->d_variants));
-        STX_TRY(stx_dev_alloc(ctx, (size_t)n_edges * 45 * sizeof(double), &P->d_out));
+        // the blocks of an evaluation, sized for the widest of the three adjustments (the reprojection's: 270 doubles a camera, 120 sums an edge)
+        STX_TRY(stx_dev_alloc(ctx, (size_t)P->min_cams * STX_RAY_MAX_CAMERA_DOUBLES * sizeof(double), &P->d_variants));
+        STX_TRY(stx_dev_alloc(ctx, (size_t)n_edges * STX_RAY_MAX_SUMS * sizeof(double), &P->d_out));
         STX_HIP(hipMemcpyAsync(P->d_edge_cams.get(), edge_cams, (size_t)n_edges * 2 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
         STX_HIP(hipMemcpyAsync(P->d_offsets.get(), offsets, ((size_t)n_edges + 1) * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
         if (total > 0) STX_HIP(hipMemcpyAsync(P->d_pts.get(), pts, (size_t)total * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
@@ -50,11 +52,13 @@ STX_EXPORT int stx_ray_problem_create(stx_ctx* ctx, int n_edges, const int* edge
 namespace {
 using NormalEquationsLaunch = int (*)(stx_ctx*, int, const int*, const long long*, const double*, const double*, double*, hipEvent_t, hipEvent_t);
 
-// one evaluation of either adjustment: a camera's 9 variants are `width` doubles each (at most 10: the problem's block holds 90 a camera)
-int problem_eval(stx_ray_problem* P, const char* what, int width, NormalEquationsLaunch launch, int n_cams, const double* variants, double* out,
-                 double out_info[4])
+// one evaluation of any of the adjustments: a camera's `count` variants are `width` doubles each (at most STX_RAY_MAX_CAMERA_DOUBLES a
+// camera), an edge gets `sums` doubles (at most STX_RAY_MAX_SUMS)
+int problem_eval(stx_ray_problem* P, const char* what, int count, int width, int sums, NormalEquationsLaunch launch, int n_cams,
+                 const double* variants, double* out, double out_info[4])
 {
-    const size_t per_cam = (size_t)width * 9;
+    static_assert(15 * 18 <= STX_RAY_MAX_CAMERA_DOUBLES && 120 <= STX_RAY_MAX_SUMS, "the problem's blocks hold the widest adjustment");
+    const size_t per_cam = (size_t)width * count;
     if (!P) return stx_fail(STX_ERR_INVALID, "problem is null");
     if (out_info) std::fill(out_info, out_info + 4, 0.0);
     if (n_cams < P->min_cams || n_cams > STX_RAY_MAX_CAMERAS)
@@ -72,7 +76,7 @@ int problem_eval(stx_ray_problem* P, const char* what, int width, NormalEquation
     STX_HIP(hipMemcpyAsync(P->d_variants.get(), variants, (size_t)P->min_cams * per_cam * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     STX_TRY(launch(ctx, P->n_edges, (const int*)P->d_edge_cams.get(), (const long long*)P->d_offsets.get(), (const double*)P->d_pts.get(),
                    (const double*)P->d_variants.get(), (double*)P->d_out.get(), P->ev[1], P->ev[2]));
-    STX_HIP(hipMemcpyAsync(out, P->d_out.get(), (size_t)P->n_edges * 45 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    STX_HIP(hipMemcpyAsync(out, P->d_out.get(), (size_t)P->n_edges * sums * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     STX_HIP(hipEventRecord(P->ev[3], ctx->stream));
     STX_HIP(hipStreamSynchronize(ctx->stream));  // the one wait
     if (out_info) {
@@ -87,12 +91,17 @@ int problem_eval(stx_ray_problem* P, const char* what, int width, NormalEquation
 
 STX_EXPORT int stx_ray_problem_eval(stx_ray_problem* P, int n_cams, const double* variants, double* out, double out_info[4])
 {
-    return problem_eval(P, "ray", 10, stx_launch_ray_normal_equations, n_cams, variants, out, out_info);
+    return problem_eval(P, "ray", 9, 10, 45, stx_launch_ray_normal_equations, n_cams, variants, out, out_info);
 }
 
 STX_EXPORT int stx_affine_problem_eval(stx_ray_problem* P, int n_cams, const double* variants, double* out, double out_info[4])
 {
-    return problem_eval(P, "affine", 8, stx_launch_affine_normal_equations, n_cams, variants, out, out_info);
+    return problem_eval(P, "affine", 9, 8, 45, stx_launch_affine_normal_equations, n_cams, variants, out, out_info);
+}
+
+STX_EXPORT int stx_reproj_problem_eval(stx_ray_problem* P, int n_cams, const double* variants, double* out, double out_info[4])
+{
+    return problem_eval(P, "reprojection", 15, 18, 120, stx_launch_reproj_normal_equations, n_cams, variants, out, out_info);
 }
 
 STX_EXPORT int stx_ray_problem_free(stx_ray_problem* P)

@@ -370,6 +370,7 @@ int stx_launch_match_pick(stx_ctx* ctx, const StxMatchPair* d_pairs, int np, con
 // the edges of one adjustment, on the device for all its evaluations: cameras (i < j) per edge, the edges' first points (ascending,
 // first 0, n_edges + 1 entries), the points x, y, u, v; variants / out: the blocks every evaluation writes and reads
 constexpr int STX_RAY_LANES = 256;  // lanes of the ordered sum: the workgroup of ray_normal_equations
+constexpr int STX_RAY_MAX_CAMERA_DOUBLES = 270, STX_RAY_MAX_SUMS = 120;  // of the widest adjustment (the reprojection's): a camera's variants, an edge's sums
 struct stx_ray_problem {
     stx_ctx* ctx = nullptr;
     int n_edges = 0, min_cams = 0;  // min_cams: the largest camera an edge names, plus one
@@ -383,6 +384,9 @@ int stx_launch_ray_normal_equations(stx_ctx* ctx, int n_edges, const int* d_edge
                                     const double* d_variants, double* d_out, hipEvent_t start, hipEvent_t stop);
 // the same sums of the affine-partial residual; d_variants: 72 doubles per camera
 int stx_launch_affine_normal_equations(stx_ctx* ctx, int n_edges, const int* d_edge_cams, const long long* d_offsets, const double* d_pts,
+                                       const double* d_variants, double* d_out, hipEvent_t start, hipEvent_t stop);
+// E, g[14], B upper triangle[105] of the reprojection residual -> d_out[120 n_edges]; d_variants: 270 doubles per camera; grid (edges, 3)
+int stx_launch_reproj_normal_equations(stx_ctx* ctx, int n_edges, const int* d_edge_cams, const long long* d_offsets, const double* d_pts,
                                        const double* d_variants, double* d_out, hipEvent_t start, hipEvent_t stop);
 // cv::resize(INTER_LINEAR_EXACT) u8 (next rows N2 / N3; stx_resize.hip); d_xt / d_yt: device tables of (offset, coeff1 | interior << 16)
 int stx_launch_resize_exact(stx_ctx* ctx, const stx_buf* src, stx_buf* dst, const int* d_xt, const int* d_yt, bool dilate,

@@ -555,6 +555,46 @@ int stx_seam_mask_resize_batch_sub(stx_ctx* ctx, int n, const stx_buf* const* se
                                    const int* full_wh_xy0, stx_buf** outs);
 int stx_timelapse_frame(stx_ctx* ctx, const stx_buf* img, int tlx, int tly, const int dst_roi_xywh[4], stx_buf** out_frame);
 
+/* ---- device frame ingest: foreign device memory -> images of the library's own ----------------------------
+ * No counterpart in the reference (its frames are host arrays).  A frame that was born on the device — a decoder's NV12 surface, an
+ * upstream stage's RGB / BGRA, another framework's array — is COPIED or converted into a new image: the kernels rely on
+ * STX_BUF_FRONT_PAD readable bytes in front of every image the library allocates, which foreign memory does not promise, so a foreign
+ * pointer never becomes a stx_buf.  tests/numpy_ingest.py is the contract, byte for byte.
+ *
+ * format: STX_INGEST_RAW copies h rows of w * channels elements of `elem` (any image layout the library has, 1 .. 4 channels); the
+ * others are u8: BGR / GRAY copy, RGB reverses the channels, BGRA / RGBA drop alpha (RGBA reverses as well), NV12 (plane[0] = Y: h x w,
+ * plane[1] = interleaved U, V: ceil(h/2) rows of ceil(w/2) pairs) and I420 (plane[1] = U, plane[2] = V, ceil(h/2) x ceil(w/2) each) become
+ * u8x3 BGR.  Pixel (x, y) takes the chroma sample (x >> 1, y >> 1); with C = Y - 16 (limited range) or Y (full), D = U - 128,
+ * E = V - 128 and the 8-bit-fraction constants of `matrix` / `range`, in int32 with an arithmetic shift,
+ *   R = clip8((yk C + rv E + 128) >> 8), G = clip8((yk C - gu D - gv E + 128) >> 8), B = clip8((yk C + bu D + 128) >> 8).
+ * channels / elem describe plane[0]: 3 u8 for BGR / RGB, 4 u8 for BGRA / RGBA, 1 u8 for GRAY / NV12 / I420.  pitch: bytes per row.
+ *
+ * One call takes n frames of unequal sizes and formats and makes ONE launch.  Everything is checked before anything is allocated or
+ * launched (STX_ERR_INVALID, the context stays usable): every plane must be device memory of the context's device
+ * (hipPointerGetAttributes: host, pinned host, managed and other-device memory are refused) and lie, first byte to last, inside one
+ * allocation (hipMemGetAddressRange); pitch >= row bytes; format agrees with channels / elem; 1 <= w, h <= STX_INGEST_MAX_SIDE.
+ * has_stream != 0: the conversion is ordered after everything queued on producer_stream so far (an event recorded there, waited for by
+ * the context's stream: no host wait; 1 as a handle means the legacy default stream — the null stream —, 2 the per-thread default stream); 0: the caller vouches that the
+ * source is complete.  The call only queues work: the source must stay untouched until the context's stream has passed it
+ * (stx_ctx_sync).  The results carry no "mask holds only 0 / 255" flag: nothing is known about a foreign mask. */
+#define STX_INGEST_RAW 0
+#define STX_INGEST_BGR 1
+#define STX_INGEST_RGB 2
+#define STX_INGEST_BGRA 3
+#define STX_INGEST_RGBA 4
+#define STX_INGEST_GRAY 5
+#define STX_INGEST_NV12 6
+#define STX_INGEST_I420 7
+#define STX_INGEST_BT601 0
+#define STX_INGEST_BT709 1
+#define STX_INGEST_LIMITED 0
+#define STX_INGEST_FULL 1
+#define STX_INGEST_MAX_SIDE 32768
+/* one foreign frame: up to three planes of device memory, pitches in bytes */
+typedef struct { const void* plane[3]; long long pitch[3]; int w, h, channels, elem, format; } stx_foreign_frame;
+int stx_ingest(stx_ctx* ctx, int n, const stx_foreign_frame* frames, int matrix, int range, void* producer_stream, int has_stream,
+               stx_buf** out);
+
 /* ---- sharded multi-band blending: one process per GPU, one stx_blender per rank ------------------
  * No counterpart in the reference (it is single process, stitching/stitcher.py:247-254).  Every rank
  * prepares the same roi; rank g produces the columns [x0, x1) of the panorama (stx_blend_set_band).

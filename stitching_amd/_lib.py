@@ -49,6 +49,19 @@ RAY_MAX_CAMERAS, RAY_MAX_MATCHES = 1024, 131072
 CONTRIB_U8_BINARY = 1
 STRIP_MASK_BITS = 2
 
+# STX_INGEST_*: the pixel formats, matrices and ranges of stx_ingest, and the largest side of a frame
+INGEST_FORMATS = {None: 0, "bgr": 1, "rgb": 2, "bgra": 3, "rgba": 4, "gray": 5, "nv12": 6, "i420": 7}
+INGEST_MATRICES = {"bt601": 0, "bt709": 1}
+INGEST_RANGES = {"limited": 0, "full": 1}
+INGEST_MAX_SIDE = 32768
+
+
+class ForeignFrame(C.Structure):
+    """stx_foreign_frame: up to three planes of foreign device memory, pitches in bytes."""
+    _fields_ = [("plane", C.c_void_p * 3), ("pitch", C.c_longlong * 3), ("w", C.c_int), ("h", C.c_int), ("channels", C.c_int),
+                ("elem", C.c_int), ("format", C.c_int)]
+
+
 EXPORTS = (
     "stx_version stx_last_error stx_set_trig_mode stx_get_trig_mode stx_set_remap_mode stx_get_remap_mode stx_set_pyrdown_mode stx_get_pyrdown_mode stx_device_count stx_ctx_create stx_ctx_destroy stx_ctx_sync "
     "stx_host_alloc stx_host_free stx_buf_from_host stx_buf_from_host_async stx_buf_alloc stx_buf_to_host stx_buf_to_host_async stx_buf_view stx_buf_info stx_buf_device_ptr stx_buf_free "
@@ -56,7 +69,7 @@ EXPORTS = (
     "stx_gain_apply stx_block_gain_apply stx_block_gain_apply_batch stx_resize_linear_exact stx_resize_linear_exact_batch stx_seam_mask_resize stx_seam_mask_resize_batch stx_seam_mask_resize_batch_sub stx_timelapse_frame stx_result_roi stx_blend_create stx_blend_num_bands stx_blend_feed stx_blend_finish stx_blend_finish_ex "
     "stx_blend_destroy stx_blend_keep_weights stx_blend_use_weights stx_mb_weights_free stx_blend_set_band stx_blend_feed_ex stx_blend_contrib_rect stx_blend_export_contrib stx_blend_export_contribs "
     "stx_blend_build stx_blend_feed_contrib stx_blend_feed_contrib_ex stx_buf_flags stx_strip_rect stx_view_rect stx_strip_pack stx_strip_pack_batch stx_strip_pack_batch_ex stx_strip_bytes stx_strip_unpack stx_blend_feed_strips stx_comm_unique_id stx_comm_create stx_comm_exchange stx_comm_exchange_begin stx_comm_exchange_end stx_comm_exchange_begin_on stx_comm_exchange_end_on stx_comm_info stx_comm_destroy stx_prof_enable stx_prof_reset stx_prof_count stx_prof_get stx_mark stx_mark_elapsed_ms "
-    "stx_exposure_feed stx_exposure_stats stx_exposure_solve stx_set_exposure_solver stx_get_exposure_solver stx_exposure_feed_ex stx_exposure_solve_device stx_lu_solve_device stx_seam_find stx_seam_schedule stx_color_seam_find stx_crop_lir stx_features_detect stx_match_features stx_match_features_model stx_ray_problem_create stx_ray_problem_eval stx_affine_problem_eval stx_reproj_problem_eval stx_ray_problem_free "
+    "stx_exposure_feed stx_exposure_stats stx_exposure_solve stx_set_exposure_solver stx_get_exposure_solver stx_exposure_feed_ex stx_exposure_solve_device stx_lu_solve_device stx_seam_find stx_seam_schedule stx_color_seam_find stx_crop_lir stx_features_detect stx_match_features stx_match_features_model stx_ray_problem_create stx_ray_problem_eval stx_affine_problem_eval stx_reproj_problem_eval stx_ray_problem_free stx_ingest "
     "stx_debug_warp_maps stx_debug_feather_dist_cap stx_debug_blend_replayed stx_debug_warp_table_launches stx_debug_blend_uploads stx_debug_blend_mask_stored"  # include/stitching_amd_debug.h: test hooks, never called by the package's classes
 ).split()
 
@@ -194,6 +207,7 @@ def lib():
     L.stx_affine_problem_eval.argtypes = [vp, C.c_int, dp, dp, dp]
     L.stx_reproj_problem_eval.argtypes = [vp, C.c_int, dp, dp, dp]
     L.stx_ray_problem_free.argtypes = [vp]
+    L.stx_ingest.argtypes = [vp, C.c_int, C.POINTER(ForeignFrame), C.c_int, C.c_int, vp, C.c_int, vpp]
     L.stx_mark.argtypes = [vp, C.c_int]
     L.stx_mark_elapsed_ms.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_double)]
     for name in EXPORTS:

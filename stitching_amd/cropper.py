@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from .blender import Blender
-from .device import DeviceImage, as_device, get_context
+from .device import DeviceImage, as_device, get_context, is_foreign_device_array
 from .stitching_error import StitchingError
 
 INVALID_CONTOUR = ("Invalid Contour. Run with --no-crop (using the stitch interface), crop=false (using the stitcher class) or "
@@ -65,6 +65,8 @@ class Rectangle(namedtuple("Rectangle", "x y width height")):
 def largest_interior_rectangle(mask, ctx=None):
     """One stx_crop_lir call on a u8 mask (numpy, `.get()`-able or DeviceImage; numpy is uploaded once).  -> ((x, y, w, h),
     (foreground components, holes), device ms).  The rectangle is computed whatever the counts are."""
+    if is_foreign_device_array(mask):
+        mask = as_device(mask, ctx)
     if not isinstance(mask, DeviceImage):
         if not isinstance(mask, np.ndarray) and hasattr(mask, "get"):
             mask = mask.get()

@@ -400,6 +400,24 @@ struct StxResizeItem {
     double xscale, yscale;  // 1 / (dw / sw), 1 / (dh / sh) in double, as linear_exact_table takes them
 };
 int stx_launch_resize_exact_batch(stx_ctx* ctx, const StxResizeItem* d_items, int n, int total_tiles, double algo_bytes);
+// device frame ingest (stx_ingest.hip; host side in stx_ingest_host.cpp) -----------------------------------------------------------
+// A lane takes STX_INGEST_LANE_PX pixels of a row (RAW: as many 4-byte words of it; a row is then w BYTES), a workgroup 64 lanes x
+// STX_INGEST_ROWS row units; a row unit is two rows of the 4:2:0 formats (one chroma pair serves its 2 x 2 block), one row otherwise.
+// The grid is the flat list of the frames' tiles, as the batched resize's (tile0 ascending, first 0).
+constexpr int STX_INGEST_LANE_PX = 4, STX_INGEST_ROWS = 4, STX_INGEST_TW = 64 * STX_INGEST_LANE_PX;
+// kind: what the kernel does with a row (several STX_INGEST_* formats share one)
+enum { STX_INGEST_K_COPY = 0, STX_INGEST_K_PACK3, STX_INGEST_K_PACK4, STX_INGEST_K_NV12, STX_INGEST_K_I420 };
+// wide: bit p set = plane p is read in whole words (base and pitch multiples of 4 — 2 for the chroma planes of I420, read 2 bytes at a
+// time); clear = byte by byte.  Decided per frame on the host, so the branch is uniform over a workgroup.  The destination is an image
+// of the library's own: base and pitch are multiples of 64.
+struct StxIngestItem {
+    const uint8_t* p[3]; long long pitch[3]; uint8_t* dst; long long dstride;
+    int w, h;       // pixels; COPY: bytes of a row
+    int kind, wide, reverse;  // reverse: PACK3 / PACK4 swap the first and third channel
+    int tiles_x, tile0, pad_;
+};
+struct StxIngestCoef { int yoff, yk, rv, gu, gv, bu; };
+int stx_launch_ingest(stx_ctx* ctx, const StxIngestItem* d_items, int n, int total_tiles, const StxIngestCoef& coef, double algo_bytes);
 
 int stx_launch_seam_resize_batch(stx_ctx* ctx, int n, const stx_buf* const* seams, const stx_buf* const* masks, stx_buf* const* dsts,
                                  const int* const* d_xt, const int* const* d_yt, uint8_t* const* tmp, const size_t* tstride);

@@ -162,6 +162,14 @@ class DeviceImage:
         _lib.check(fn(ctx.handle, a.ctypes.data_as(C.c_void_p), a.strides[0], w, h, c, _ELEMS[a.dtype], C.byref(out)))
         return cls(ctx, out)
 
+    @classmethod
+    def from_device(cls, obj, format=None, matrix="bt709", range="limited", stream=None, wait=True, ctx=None):
+        """A foreign device frame (an object with `__cuda_array_interface__`, or the tuple of planes of nv12 / i420) -> a new image of
+        the library's own, copied or converted on the device: `stitching_amd.ingest.ingest`."""
+        from .ingest import ingest
+
+        return ingest(obj, format=format, matrix=matrix, range=range, stream=stream, wait=wait, ctx=ctx)
+
     # ---- numpy-like surface
     @property
     def shape(self):
@@ -221,6 +229,19 @@ class DeviceImage:
         _lib.check(self.ctx._lib.stx_buf_device_ptr(self._h, C.byref(p)))
         return p.value
 
+    @property
+    def __cuda_array_interface__(self):
+        """The image's memory for a GPU encoder or another framework (version 3), without a copy.  Shape and strides are the image's
+        own: rows are padded, and a crop view is exported with its parent's pitch.  The getter syncs the context, so the bytes are
+        complete and `stream` is None.  This object stays the owner: the consumer must keep it alive for as long as it uses the
+        memory.  The memory is handed out writable because some consumers refuse read-only arrays — but an image may be shared: the
+        panorama mask of a known rig is one buffer handed out by every run, and must be copied before it is written."""
+        self.ctx.sync()
+        size = self.dtype.itemsize
+        strides = (self.stride_bytes, size) if self.channels == 1 else (self.stride_bytes, self.channels * size, size)
+        return {"version": 3, "shape": self.shape, "typestr": self.dtype.str if size > 1 else "|u1", "strides": strides,
+                "data": (self.device_ptr(), False), "stream": None}
+
     def free(self):
         if self._h is not None:
             if self.ctx.handle:  # a closed context has already returned all of its device memory
@@ -237,13 +258,25 @@ class DeviceImage:
         return f"DeviceImage(shape={self.shape}, dtype={self.dtype}, device={self.ctx.device})"
 
 
+def is_foreign_device_array(a):
+    """An object of another framework that holds device memory (`__cuda_array_interface__`): as_device copies it on the device, so
+    it must not be passed through np.asarray first."""
+    return not isinstance(a, DeviceImage) and hasattr(a, "__cuda_array_interface__")
+
+
 def as_device(img, ctx=None, wait=True):
-    """numpy array, cv.UMat or DeviceImage -> DeviceImage on `ctx` (uploads when needed; wait: see DeviceImage.from_numpy).
+    """numpy array, cv.UMat, DeviceImage or foreign device array -> DeviceImage on `ctx` (uploads when needed; wait: see
+    DeviceImage.from_numpy).  An object with `__cuda_array_interface__` (a u8 BGR frame or a u8 mask of another framework) is copied on
+    the device, layout and bytes as they are (stitching_amd.ingest).
     A cv.UMat is what the reference's own classes hand on where cv2 produced one — the seam masks of `SeamFinder.resize`
     (stitching/seam_finder.py:37-43) reach `Blender.feed` that way when only Warper and Blender are switched — its array comes out of
     `.get()`."""
     if isinstance(img, DeviceImage):
         return img
+    if hasattr(img, "__cuda_array_interface__"):
+        from .ingest import ingest
+
+        return ingest(img, ctx=ctx, wait=wait)
     if not isinstance(img, np.ndarray) and hasattr(img, "get"):
         img = img.get()
     return DeviceImage.from_numpy(img, ctx, wait)

@@ -11,12 +11,14 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .device import DeviceImage, as_device, get_context
+from .device import DeviceImage, as_device, get_context, is_foreign_device_array
 from .stitching_error import StitchingError
 
 
 def _check_image(a, what, i):
-    """Shape / dtype check without a host copy of device images."""
+    """Shape / dtype check without a host copy of device images (a foreign device array becomes a DeviceImage on the device)."""
+    if is_foreign_device_array(a):
+        a = as_device(a)
     if isinstance(a, DeviceImage):
         ch, dt, hw = a.channels, a.dtype, (a.height, a.width)
     else:

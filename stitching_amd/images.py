@@ -203,8 +203,9 @@ class Images:
 
     @staticmethod
     def get_image_size(img):
-        """(width, height)"""
-        return (img.shape[1], img.shape[0])
+        """(width, height); a foreign device array that has no `.shape` of its own answers through `__cuda_array_interface__`"""
+        shape = img.shape if hasattr(img, "shape") else img.__cuda_array_interface__["shape"]
+        return (shape[1], shape[0])
 
     @staticmethod
     def resize_img_by_scaler(scaler, size, img, device_resident=None):

@@ -15,7 +15,7 @@ import numpy as np
 from . import _lib, config
 from .blender import Blender
 from .cropper import Cropper
-from .device import as_device, get_context
+from .device import as_device, get_context, is_foreign_device_array
 from .exposure_error_compensator import ExposureErrorCompensator
 from .images import Images
 from .seam_estimation import SeamEstimator
@@ -392,6 +392,12 @@ class StitchJob:
         return g, imgs
 
 
+def _seam_mask_input(m):
+    """A low-resolution seam mask as StitchJob takes it: a foreign device array as it is (as_device copies it on the device), anything
+    else as a host array."""
+    return m if is_foreign_device_array(m) else np.asarray(m.get() if hasattr(m, "get") else m)
+
+
 def compose(frames, cameras, warper_type="spherical", blender_type="multiband", blend_strength=Blender.DEFAULT_BLEND_STRENGTH,
             compensator=None, seam_masks=None, ctx=None, cropper=None, crop_aspect=1, camera_aspect=1):
     """The final-resolution half of Stitcher.stitch (stitching/stitcher.py:117-128) with every intermediate in HBM:
@@ -411,7 +417,7 @@ def compose(frames, cameras, warper_type="spherical", blender_type="multiband", 
     cropper, crop_aspect = _split_cropper(cropper, crop_aspect)
     if cropper is not None:
         if seam_masks is not None and blender_type == "multiband":
-            seam_masks = [np.asarray(m.get() if hasattr(m, "get") else m) for m in seam_masks]
+            seam_masks = [_seam_mask_input(m) for m in seam_masks]
         return StitchJob(frames, cameras, warper_type=warper_type, blender_type=blender_type, blend_strength=blend_strength, ctx=ctx,
                          seam_masks=seam_masks, compensator=compensator, cropper=cropper, crop_aspect=crop_aspect,
                          camera_aspect=camera_aspect).run()
@@ -419,7 +425,7 @@ def compose(frames, cameras, warper_type="spherical", blender_type="multiband", 
         # nothing between the warp and the blender needs whole images (the gain of a pixel depends on its position alone): warp,
         # compensate and feed only what the seam cells can reach
         return StitchJob(frames, cameras, warper_type=warper_type, blender_type=blender_type, blend_strength=blend_strength, ctx=ctx,
-                         seam_masks=[np.asarray(m.get() if hasattr(m, "get") else m) for m in seam_masks], compensator=compensator,
+                         seam_masks=[_seam_mask_input(m) for m in seam_masks], compensator=compensator,
                          camera_aspect=camera_aspect).run()
     prev = config.device_resident()
     config.set_device_resident(True)

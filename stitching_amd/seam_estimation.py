@@ -14,12 +14,15 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, config
-from .device import DeviceImage, as_device, get_context
+from .device import DeviceImage, as_device, get_context, is_foreign_device_array
 from .stitching_error import StitchingError
 
 
 def _size(a, what, i):
-    """(w, h) and the array (numpy or DeviceImage), without a host copy of device images."""
+    """(w, h) and the array (numpy or DeviceImage), without a host copy of device images (a foreign device array becomes a DeviceImage on
+    the device)."""
+    if is_foreign_device_array(a):
+        a = as_device(a)
     if isinstance(a, DeviceImage):
         return (a.width, a.height), a
     if not isinstance(a, np.ndarray) and hasattr(a, "get"):
@@ -98,6 +101,8 @@ class SeamEstimator:
 def _color_image(a, i):
     """u8 HxWx3 (numpy or DeviceImage) from what a caller hands a finder: u8 images, or the float32 images with integer values in
     0 .. 255 the reference's SeamFinder.find makes of them (stitching/seam_finder.py:33-35)."""
+    if is_foreign_device_array(a):
+        a = as_device(a)
     if isinstance(a, DeviceImage):
         if a.dtype != np.uint8 or a.channels != 3:
             raise StitchingError(f"image {i}: colour seams need u8 images with 3 channels, got {a.dtype} of shape {a.shape}")

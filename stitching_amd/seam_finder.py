@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, config
-from .device import DeviceImage, as_device, get_context
+from .device import DeviceImage, as_device, get_context, is_foreign_device_array
 from .seam_estimation import SeamEstimator
 from .stitching_error import StitchingError
 
@@ -106,7 +106,7 @@ class SeamFinder:
         size full_w x full_h and the result is that rectangle of the full result (x0 a multiple of 4)."""
         masks = list(masks)
         ctx = masks[0].ctx if masks and isinstance(masks[0], DeviceImage) else get_context()
-        host = lambda a: a if isinstance(a, DeviceImage) else np.asarray(a.get() if hasattr(a, "get") else a)  # noqa: E731
+        host = lambda a: a if isinstance(a, DeviceImage) or is_foreign_device_array(a) else np.asarray(a.get() if hasattr(a, "get") else a)  # noqa: E731
         s = [as_device(host(a), ctx) for a in seam_masks]
         m = [as_device(host(a), ctx) for a in masks]
         n = len(m)
@@ -177,9 +177,9 @@ class SeamFinder:
         """stitching/seam_finder.py:37-43 — returns the final-resolution seam mask for Blender.feed.  `seam_mask` may be
         what cv2's finders return (a cv.UMat: `.get()` is called), a numpy array or a DeviceImage."""
         ctx = mask.ctx if isinstance(mask, DeviceImage) else (seam_mask.ctx if isinstance(seam_mask, DeviceImage) else get_context())
-        if not isinstance(seam_mask, DeviceImage):
+        if not isinstance(seam_mask, DeviceImage) and not is_foreign_device_array(seam_mask):
             seam_mask = np.asarray(seam_mask.get() if hasattr(seam_mask, "get") else seam_mask)
-        if not isinstance(mask, DeviceImage):
+        if not isinstance(mask, DeviceImage) and not is_foreign_device_array(mask):
             mask = np.asarray(mask.get() if hasattr(mask, "get") else mask)
         s, m = as_device(seam_mask, ctx), as_device(mask, ctx)
         out = C.c_void_p()

@@ -196,55 +196,44 @@ int stx_warp(stx_ctx* ctx, int type, float scale, const float K[9], const float 
  * out_img / out_mask may each be NULL. */
 int stx_warp_image_and_mask(stx_ctx* ctx, int type, float scale, const float K[9], const float R[9],
                             const stx_buf* src, stx_buf** out_img, stx_buf** out_mask, int out_xywh[4]);
-/* batched form of the generator loops stitching/warper.py:39-41 (warp_images) and :54-56
- * (create_and_warp_masks) for n cameras of one warper: ROIs in one device pass, then ONE table launch and
- * ONE remap launch for all images (the per-image argument blocks travel as kernel arguments: no upload,
- * no host synchronisation).  out_imgs / out_masks are arrays of n handles (either may be NULL). */
-int stx_warp_batch(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s,
-                   const stx_buf* const* srcs, stx_buf** out_imgs, stx_buf** out_masks, int* out_xywh);
-/* stx_warp_batch over caller-given destination rectangles (x, y, w, h in warp coordinates, normally sub-rectangles of the
- * ROIs of stx_warp_rois): the pixels are exactly those of the full warp inside the rectangle.  For pipelines that know
- * which part of a warped image the blender can see (seam masks: stitching/stitcher.py:124 cuts every image down to its
- * seam cell AFTER warping all of it, :119-121). */
-int stx_warp_batch_rects(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s,
-                         const stx_buf* const* srcs, const int* rects_xywh, stx_buf** out_imgs, stx_buf** out_masks);
-/* stx_warp_batch[_rects] + the block gains of the exposure compensator in one call: the loops stitching/stitcher.py:119-123 (warp final
- * images, then compensator.apply on each) for the "gain_blocks" compensator.  gain_maps[i]: f32x1 (f32x3: channel_blocks) map of image i,
- * laid over its WHOLE warped image (BlocksCompensator::apply) also when rects_xywh names a rectangle of it; gain_flags as in
- * stx_block_gain_apply_batch.  The product happens in the warp kernel's epilogue when it can (tuned kernel, bounded f32x1 maps), else as
- * a second pass: out_imgs equal stx_block_gain_apply_batch(stx_warp_batch[_rects](...)) byte for byte either way.  rects_xywh may be NULL
- * (whole ROIs, returned in out_xywh). */
-int stx_warp_batch_gain(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s, const stx_buf* const* srcs,
-                        const int* rects_xywh, const stx_buf* const* gain_maps_f32, const int* gain_flags, stx_buf** out_imgs,
-                        stx_buf** out_masks, int* out_xywh);
-/* stx_warp_batch_rects / stx_warp_batch_gain for the panoramas of one rig: the per-column / per-row tables of the typed projectors (plane,
- * affine, cylindrical, spherical, mercator) follow from the cameras, the rectangles, the scale and the trig mode — never from the pixels —
- * so a handle keeps them between calls.  *tables = NULL on the first call: a handle is made and filled.  A later call with the handle
- * compares everything the table kernel reads (projector type and family; per image the rectangle, scale, trig mode, t[0..1] and the
- * products' factors k_rinv[1], [4], [7]) with the handle's record: equal -> no table kernel is launched and no table block allocated, the
- * warp reads the kept tables; any difference -> the tables are rebuilt into the handle in stream order and the record updated.  The library
- * decides, never the caller; the bytes are those of the plain calls either way.  The per-pixel projector families use no tables and
- * leave the handle empty.  rects_xywh is required (stx_warp_batch_with_rois_kept: the ROIs of the call).  A handle belongs to the context that made it: another context's is refused with
- * STX_ERR_INVALID.  stx_warp_tables_free gives the block back (stream-ordered: warps that read it may still be in flight). */
-int stx_warp_batch_rects_kept(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s, const stx_buf* const* srcs,
-                              const int* rects_xywh, stx_buf** out_imgs, stx_buf** out_masks, stx_warp_tables** tables);
-int stx_warp_batch_gain_kept(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s, const stx_buf* const* srcs,
-                             const int* rects_xywh, const stx_buf* const* gain_maps_f32, const int* gain_flags, stx_buf** out_imgs,
-                             stx_buf** out_masks, stx_warp_tables** tables);
-/* stx_warp_batch_with_rois that fills (or checks) a table handle on its way: the first panorama of a rig, whose ROIs become the
- * rectangles of the later stx_warp_batch_rects_kept / _gain_kept calls */
-int stx_warp_batch_with_rois_kept(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s, const stx_buf* const* srcs,
-                                  const stx_buf* const* gain_maps_f32_or_null, const int* gain_flags_or_null, stx_buf** out_imgs,
-                                  stx_buf** out_masks, int* out_xywh, stx_warp_tables** tables);
+/* stx_warp_batch: batched form of the generator loops stitching/warper.py:39-41 (warp_images) and :54-56 (create_and_warp_masks) for n
+ * cameras of one warper: ROIs in one device pass, then ONE table launch and ONE remap launch for all images (the per-image argument
+ * blocks travel as kernel arguments: no upload, no host synchronisation).  out_imgs / out_masks are arrays of n handles; either may be
+ * NULL, not both.  out_xywh (or NULL) receives the n rectangles warped: the ROIs, or rects_xywh echoed.  The options, each NULL / 0
+ * where absent; what breaks a rule below is refused with STX_ERR_INVALID before the device is touched:
+ *
+ * rects_xywh: caller-given destination rectangles (x, y, w, h in warp coordinates, normally sub-rectangles of the ROIs of
+ *   stx_warp_rois) instead of the ROIs: the pixels are exactly those of the full warp inside the rectangle.  For pipelines that know
+ *   which part of a warped image the blender can see (seam masks: stitching/stitcher.py:124 cuts every image down to its seam cell AFTER
+ *   warping all of it, :119-121).
+ * gain_maps, gain_flags: the block gains of the exposure compensator in the same call: the loops stitching/stitcher.py:119-123 (warp final
+ *   images, then compensator.apply on each) for the "gain_blocks" compensator.  gain_maps[i]: f32x1 (f32x3: channel_blocks) map of image
+ *   i, laid over its WHOLE warped image (BlocksCompensator::apply) also when rects_xywh names a rectangle of it, which must then lie
+ *   inside the ROI; gain_flags (or NULL) as in stx_block_gain_apply_batch.  The product happens in the warp kernel's epilogue when it can
+ *   (tuned kernel, bounded f32x1 maps), else as a second pass: out_imgs equal stx_block_gain_apply_batch over the images of the call
+ *   without gain_maps byte for byte either way.  Needs out_imgs.
+ * flags & STX_WARP_FRESH_ROIS: one panorama's warps, its ROI pass included: stitching/stitcher.py:188 (warp_rois) + :119-123 in ONE call.
+ *   The ROIs are computed by this call (never taken from the cache of earlier calls: a panorama pays for its own ROI pass) and returned in
+ *   out_xywh; the host waits for them once, inside the call, by polling stamps the ROI kernel writes into pinned memory, and launches the
+ *   warps right behind — the device idles for ~25 us at the head of a panorama instead of the ~145 us of stx_warp_rois + Python + a
+ *   second call (profiles/r05_latency.md).  Results equal stx_warp_rois + the call without the flag byte for byte.  Needs out_xywh and no
+ *   rects_xywh; other bits of flags are refused.
+ * tables: for the panoramas of one rig.  The per-column / per-row tables of the typed projectors (plane, affine, cylindrical, spherical,
+ *   mercator) follow from the cameras, the rectangles, the scale and the trig mode — never from the pixels — so a handle keeps them
+ *   between calls.  *tables = NULL on the first call: a handle is made and filled; a call that fails leaves it NULL.  A later call with
+ *   the handle compares everything the table kernel reads (projector type and family; per image the rectangle, scale, trig mode, t[0..1]
+ *   and the products' factors k_rinv[1], [4], [7]) with the handle's record: equal -> no table kernel is launched and no table block
+ *   allocated, the warp reads the kept tables; any difference -> the tables are rebuilt into the handle in stream order and the record
+ *   updated.  The library decides, never the caller; the bytes are those of the calls without a handle either way.  The per-pixel
+ *   projector families use no tables and leave the handle empty.  Kept tables belong to given rectangles: rects_xywh, or
+ *   STX_WARP_FRESH_ROIS on the first panorama of a rig, whose ROIs become the rects_xywh of the later calls.  A handle belongs to the
+ *   context that made it: another context's is refused.  stx_warp_tables_free gives the block back (stream-ordered: warps that read it
+ *   may still be in flight). */
+#define STX_WARP_FRESH_ROIS 1
+int stx_warp_batch(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s, const stx_buf* const* srcs,
+                   const int* rects_xywh, const stx_buf* const* gain_maps_f32, const int* gain_flags, int flags, stx_buf** out_imgs,
+                   stx_buf** out_masks, int* out_xywh, stx_warp_tables** tables);
 int stx_warp_tables_free(stx_warp_tables* t);
-/* One panorama's warps, its ROI pass included: stitching/stitcher.py:188 (warp_rois) + :119-123 in ONE call.  The ROIs are computed by this
- * call (never taken from the cache of earlier calls: a panorama pays for its own ROI pass) and returned in out_xywh; the host waits for them
- * once, inside the call, by polling stamps the ROI kernel writes into pinned memory, and launches the warps right behind — the device idles
- * for ~25 us at the head of a panorama instead of the ~145 us of stx_warp_rois + Python + stx_warp_batch (profiles/r05_latency.md).
- * gain_maps / gain_flags: as in stx_warp_batch_gain, or NULL.  Results equal stx_warp_rois + stx_warp_batch[_gain] byte for byte. */
-int stx_warp_batch_with_rois(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s, const stx_buf* const* srcs,
-                             const stx_buf* const* gain_maps_f32_or_null, const int* gain_flags_or_null, stx_buf** out_imgs,
-                             stx_buf** out_masks, int* out_xywh);
 /* stitching/warper.py:58-68 without allocating the 255-filled source (size only) */
 int stx_warp_mask(stx_ctx* ctx, int type, float scale, const float K[9], const float R[9], int w, int h,
                   stx_buf** out_mask, int out_xywh[4]);
@@ -319,17 +308,15 @@ int stx_mb_weights_free(stx_mb_weights* w);
  *                        "gain" / "channel" compensators (GainCompensator::apply, ChannelsCompensator::apply =
  *                        cv::multiply(image, gain): fp32 product, cvRound, saturate to u8), in place on the warped image
  *                        between warp and feed (stitching/stitcher.py:123,219-221).  The block compensators
- *                        ("gain_blocks", "channel_blocks") are stx_block_gain_apply below.
+ *                        ("gain_blocks", "channel_blocks") are stx_block_gain_apply_batch below.
  * stx_timelapse_frame <- stitching/timelapser.py:36-52 timelapser.process(img, mask, corner) + getDst():
  *                        zero frame of the roi given to initialize(), the image pasted at its corner. */
 int stx_gain_apply(stx_ctx* ctx, stx_buf* img_u8x3, const float gains_bgr[3]);
 /* the reference's default compensator "gain_blocks": BlocksCompensator::apply = cv::resize(gain map, image size,
  * INTER_LINEAR) [fp32] + cv::multiply, fused (the full-size gain map is never stored); gain_map is f32x1, or f32x3 (BGR
- * maps, interleaved) for "channel_blocks" (BlocksChannelsCompensator) */
-int stx_block_gain_apply(stx_ctx* ctx, stx_buf* img_u8x3, const stx_buf* gain_map_f32);
-/* the same for all n images of a panorama (the generator loop stitching/stitcher.py:219-221): two launches per 16 images, gain maps
- * resident on the device.  full_wh_xy0 (or NULL) = {full_w, full_h, x0, y0} per image: imgs[i] is the rectangle at (x0, y0) of a warped
- * image of size full_w x full_h (a seam-cell crop, stx_warp_batch_rects) and the gain map is laid over the FULL image, as
+ * maps, interleaved) for "channel_blocks" (BlocksChannelsCompensator).  For all n images of a panorama (the generator loop
+ * stitching/stitcher.py:219-221): two launches per 16 images, gain maps resident on the device.  full_wh_xy0 (or NULL) = {full_w, full_h, x0, y0} per image: imgs[i] is the rectangle at (x0, y0) of a warped
+ * image of size full_w x full_h (a seam-cell crop: stx_warp_batch with rects_xywh) and the gain map is laid over the FULL image, as
  * BlocksCompensator::apply does — the rectangle's bytes equal those of the whole image compensated and then cut.
  * flags (or NULL): STX_GAIN_MAP_BOUNDED per image — the caller has checked that every gain of the map is finite and below 2^31 / 255. */
 #define STX_GAIN_MAP_BOUNDED 1
@@ -344,14 +331,11 @@ int stx_block_gain_apply_batch(stx_ctx* ctx, int n, stx_buf* const* imgs_u8x3, c
 #define STX_EXPOSURE_GAIN_BLOCKS 2
 #define STX_EXPOSURE_CHANNELS 3
 #define STX_EXPOSURE_CHANNELS_BLOCKS 4
-/* The whole feed of n u8x3 images and their u8x1 masks (pixels count where both masks are 255) at corners_xy.  Gains go to
+/* stx_exposure_feed_ex (declared below, with its solver argument): the whole feed of n u8x3 images and their u8x1 masks (pixels count where both masks are 255) at corners_xy.  Gains go to
  * out_gains image after image: gain 1 value, channels 3 (BGR), gain_blocks bh x bw fp32 map values (filtered as getMatGains returns
  * them), channels_blocks bh x bw x 3, with bw = ceil(w / block_size), bh = ceil(h / block_size).  *inout_count: capacity of
  * out_gains in values; out_gains NULL: only writes the count needed (no GPU work).  The images are never modified.
- * out_info (or NULL): {units, pair jobs, device statistics ms (HIP events, all feeds), host assembly + solve + filter ms}. */
-int stx_exposure_feed(stx_ctx* ctx, int kind, int n, const stx_buf* const* imgs_u8x3, const stx_buf* const* masks_u8,
-                      const int* corners_xy, int block_size, int nr_feeds, double* out_gains, long long* inout_count,
-                      double out_info[4]);
+ * The device statistics ms of out_info are HIP events over all feeds. */
 /* The statistics of the first feed alone, per pair job: units (a, b) with a <= b, the count c of pixels both masks hold 255 in,
  * and the sums of norms over them ({sum_a, sum_b} for the gain kinds; {B, G, R of a, B, G, R of b} for the channel kinds: six
  * values per job either way).  out_ab NULL: only writes *inout_jobs (the pair enumeration runs, no GPU work). */
@@ -374,14 +358,14 @@ int stx_exposure_solve(int m, int npairs, const int* pairs_ij, const double* n_i
  * there is no fall-back to the host.  A singular system fails with STX_ERR_INVALID, "exposure system is singular at row %d".
  * Which one to pick: the device from a few thousand unknowns on (DESIGN.md section 9 has the measured table); below, the host.
  *
- * The solver of stx_exposure_feed is a process-wide mode: STX_EXPOSURE_SOLVER_HOST (default) or _DEVICE; STITCHING_AMD_EXPOSURE_SOLVER
+ * The solver of a feed is a process-wide mode: STX_EXPOSURE_SOLVER_HOST (default) or _DEVICE; STITCHING_AMD_EXPOSURE_SOLVER
  * (host | device) sets the start-up value.  stx_exposure_feed_ex takes it per call (STX_EXPOSURE_SOLVER_DEFAULT: the mode). */
 #define STX_EXPOSURE_SOLVER_DEFAULT (-1)
 #define STX_EXPOSURE_SOLVER_HOST 0
 #define STX_EXPOSURE_SOLVER_DEVICE 1
 int stx_set_exposure_solver(int mode);
 int stx_get_exposure_solver(void);
-/* stx_exposure_feed with the solver given.  out_info (or NULL): {units, pair jobs, device statistics ms, assembly + solve + filter ms
+/* The feed, with the solver given.  out_info (or NULL): {units, pair jobs, device statistics ms, assembly + solve + filter ms
  * (wall clock: with the device solver it covers the device elimination and the host tail), the solver used, device elimination ms (HIP
  * events), compaction + copy + back substitution ms, non-zeros of U — the last three summed over the solves, 0 with the host solver}. */
 int stx_exposure_feed_ex(stx_ctx* ctx, int kind, int n, const stx_buf* const* imgs_u8x3, const stx_buf* const* masks_u8,
@@ -600,7 +584,7 @@ int stx_ingest(stx_ctx* ctx, int n, const stx_foreign_frame* frames, int matrix,
  * prepares the same roi; rank g produces the columns [x0, x1) of the panorama (stx_blend_set_band).
  * An image fed on rank o whose 2^bands-aligned feed rectangle reaches another rank's columns is
  * exported there as a CONTRIBUTION: per pyramid level the products (short)(L*W) and the weights W
- * over a strip (stx_blend_export_contrib -> RCCL send/recv -> stx_blend_feed_contrib).  Integer sums
+ * over a strip (stx_blend_export_contrib -> RCCL send/recv -> stx_blend_feed_contrib_ex).  Integer sums
  * are order independent and `order` (the global feed index) fixes the fp32 weight-sum order, so the
  * assembled panorama is bit-identical to the single-GPU result.  DESIGN.md §6. */
 int stx_blend_set_band(stx_blender* b, int x0, int x1);
@@ -619,7 +603,6 @@ int stx_blend_export_contribs(stx_blender* b, int n, const int* orders, const in
 /* build the pyramids of every image fed so far now (they are otherwise built at the first export / blend()):
  * a sharded rank calls it for its interior images while its strips are still in flight */
 int stx_blend_build(stx_blender* b);
-int stx_blend_feed_contrib(stx_blender* b, int order, const int rect_xywh[4], const stx_buf* packed);
 /* flags travel with a strip over the caller's control plane.  STX_CONTRIB_U8_BINARY: the strip was exported from
  * a u8 image whose mask holds only 0 / 255 (then its products are L or 0 and its weights 0.f or 1.f, and the
  * receiver may keep the packed 16-bit level-0 kernel).  stx_buf_flags reads it off an exported strip (or a mask:
@@ -645,10 +628,8 @@ int stx_view_rect(const stx_blender* b, int img_w, int img_h, int tlx, int tly, 
 int stx_strip_rect(const stx_blender* b, int img_w, int img_h, int tlx, int tly, int band_x0, int band_x1, int out_x0x1[2],
                    size_t* out_bytes);
 int stx_strip_pack(stx_ctx* ctx, const stx_buf* img, const stx_buf* mask, int x0, int x1, stx_buf** out_packed);
-/* all strips a rank owes in one call (one copy kernel per 16 strips); x0 multiples of 8, whole image buffers (no views) */
-int stx_strip_pack_batch(stx_ctx* ctx, int n, const stx_buf* const* imgs, const stx_buf* const* masks, const int* x0s, const int* x1s,
-                         stx_buf** out_packed);
-/* the same with flags (STX_STRIP_MASK_BITS); stx_strip_bytes: size of the flat buffer of a w x h strip under these flags */
+/* all strips a rank owes in one call (one copy kernel per 16 strips); x0 multiples of 8, whole image buffers (no views); flags: 0 or
+ * STX_STRIP_MASK_BITS; stx_strip_bytes: size of the flat buffer of a w x h strip under these flags */
 int stx_strip_pack_batch_ex(stx_ctx* ctx, int n, const stx_buf* const* imgs, const stx_buf* const* masks, const int* x0s, const int* x1s,
                             int flags, stx_buf** out_packed);
 int stx_strip_bytes(int w, int h, int flags, size_t* out_bytes);
@@ -658,24 +639,18 @@ int stx_blend_feed_strips(stx_blender* b, int n, const stx_buf* const* packed, c
 int stx_strip_unpack(const stx_buf* packed, int w, int h, int flags, stx_buf** out_img, stx_buf** out_mask);
 
 /* ---- RCCL strip exchange over xGMI ---------------------------------------------------------------
- * One communicator per rank (one process per GPU).  stx_comm_exchange issues every send / receive
- * of one step as a single RCCL group on the context's HIP stream: it is ordered after the kernels
- * that filled the send buffers and before the kernels that read the receive buffers.  The unique id
- * (128 bytes, from rank 0) travels over the caller's control plane. */
+ * One communicator per rank (one process per GPU).  An exchange issues every send / receive of one step as a
+ * single RCCL group: it is ordered after the kernels that filled the send buffers and before the kernels that
+ * read the receive buffers.  The unique id (128 bytes, from rank 0) travels over the caller's control plane. */
 typedef struct stx_comm stx_comm;
 int stx_comm_unique_id(unsigned char out[128]);
 int stx_comm_create(stx_ctx* ctx, int nranks, int rank, const unsigned char id[128], stx_comm** out);
-int stx_comm_exchange(stx_comm* comm, int n_ops, const int* peers, const int* is_send, void* const* dev_ptrs,
-                      const size_t* bytes);
-/* split form: _begin issues the group on the communicator's own stream, ordered after everything queued so far
- * on the context stream; kernels queued on the context stream between _begin and _end (warps and pyramids of
- * images that send nothing) overlap with the transfer; _end orders the context stream after the transfer.
- * The buffers must stay alive until _end has been called. */
-int stx_comm_exchange_begin(stx_comm* comm, int n_ops, const int* peers, const int* is_send, void* const* dev_ptrs,
-                            const size_t* bytes);
-int stx_comm_exchange_end(stx_comm* comm);
-/* same, for a context other than the one the communicator was created on (same device): one communicator serves
- * several panoramas in flight on different streams; their exchanges are serialised on the communicator's stream */
+/* _begin_on issues the group on the communicator's own stream, ordered after everything queued so far on the stream
+ * of context `on`; kernels queued on that stream between _begin_on and _end_on (warps and pyramids of images that
+ * send nothing) overlap with the transfer; _end_on orders the context stream after the transfer.  The buffers must
+ * stay alive until _end_on has been called.  `on`: the communicator's own context or another one of the same device:
+ * one communicator serves several panoramas in flight on different streams; their exchanges are serialised on the
+ * communicator's stream */
 int stx_comm_exchange_begin_on(stx_comm* comm, stx_ctx* on, int n_ops, const int* peers, const int* is_send,
                                void* const* dev_ptrs, const size_t* bytes);
 int stx_comm_exchange_end_on(stx_comm* comm, stx_ctx* on);

@@ -62,16 +62,120 @@ class ForeignFrame(C.Structure):
                 ("elem", C.c_int), ("format", C.c_int)]
 
 
-EXPORTS = (
-    "stx_version stx_last_error stx_set_trig_mode stx_get_trig_mode stx_set_remap_mode stx_get_remap_mode stx_set_pyrdown_mode stx_get_pyrdown_mode stx_device_count stx_ctx_create stx_ctx_destroy stx_ctx_sync "
-    "stx_host_alloc stx_host_free stx_buf_from_host stx_buf_from_host_async stx_buf_alloc stx_buf_to_host stx_buf_to_host_async stx_buf_view stx_buf_info stx_buf_device_ptr stx_buf_free "
-    "stx_warp_roi stx_warp_rois stx_warp stx_warp_image_and_mask stx_warp_batch stx_warp_batch_rects stx_warp_batch_gain stx_warp_batch_rects_kept stx_warp_batch_gain_kept stx_warp_tables_free stx_warp_batch_with_rois stx_warp_batch_with_rois_kept stx_warp_mask "
-    "stx_gain_apply stx_block_gain_apply stx_block_gain_apply_batch stx_resize_linear_exact stx_resize_linear_exact_batch stx_seam_mask_resize stx_seam_mask_resize_batch stx_seam_mask_resize_batch_sub stx_timelapse_frame stx_result_roi stx_blend_create stx_blend_num_bands stx_blend_feed stx_blend_finish stx_blend_finish_ex "
-    "stx_blend_destroy stx_blend_keep_weights stx_blend_use_weights stx_mb_weights_free stx_blend_set_band stx_blend_feed_ex stx_blend_contrib_rect stx_blend_export_contrib stx_blend_export_contribs "
-    "stx_blend_build stx_blend_feed_contrib stx_blend_feed_contrib_ex stx_buf_flags stx_strip_rect stx_view_rect stx_strip_pack stx_strip_pack_batch stx_strip_pack_batch_ex stx_strip_bytes stx_strip_unpack stx_blend_feed_strips stx_comm_unique_id stx_comm_create stx_comm_exchange stx_comm_exchange_begin stx_comm_exchange_end stx_comm_exchange_begin_on stx_comm_exchange_end_on stx_comm_info stx_comm_destroy stx_prof_enable stx_prof_reset stx_prof_count stx_prof_get stx_mark stx_mark_elapsed_ms "
-    "stx_exposure_feed stx_exposure_stats stx_exposure_solve stx_set_exposure_solver stx_get_exposure_solver stx_exposure_feed_ex stx_exposure_solve_device stx_lu_solve_device stx_seam_find stx_seam_schedule stx_color_seam_find stx_crop_lir stx_features_detect stx_match_features stx_match_features_model stx_ray_problem_create stx_ray_problem_eval stx_affine_problem_eval stx_reproj_problem_eval stx_ray_problem_free stx_ingest "
-    "stx_debug_warp_maps stx_debug_feather_dist_cap stx_debug_blend_replayed stx_debug_warp_table_launches stx_debug_blend_uploads stx_debug_blend_mask_stored"  # include/stitching_amd_debug.h: test hooks, never called by the package's classes
-).split()
+WARP_FRESH_ROIS = 1
+
+_i, _f, _d, _u, _z = C.c_int, C.c_float, C.c_double, C.c_uint, C.c_size_t
+_vp, _vpp = C.c_void_p, C.POINTER(C.c_void_p)
+_fp, _ip, _dp, _llp = C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_longlong)
+_ubp, _zp = C.POINTER(C.c_ubyte), C.POINTER(C.c_size_t)
+
+# every export of include/stitching_amd.h and include/stitching_amd_debug.h, declared once: name -> argtypes ([]: takes nothing).
+# All return int but stx_last_error (const char*).
+PROTOTYPES = {
+    "stx_version": [],
+    "stx_last_error": [],
+    "stx_set_trig_mode": [_i],
+    "stx_get_trig_mode": [],
+    "stx_set_remap_mode": [_i],
+    "stx_get_remap_mode": [],
+    "stx_set_pyrdown_mode": [_i, _i],
+    "stx_get_pyrdown_mode": [_ip],
+    "stx_device_count": [_ip],
+    "stx_ctx_create": [_i, _vpp],
+    "stx_ctx_destroy": [_vp],
+    "stx_ctx_sync": [_vp],
+    "stx_host_alloc": [_z, _vpp],
+    "stx_host_free": [_vp],
+    "stx_buf_from_host": [_vp, _vp, _z, _i, _i, _i, _i, _vpp],
+    "stx_buf_from_host_async": [_vp, _vp, _z, _i, _i, _i, _i, _vpp],
+    "stx_buf_alloc": [_vp, _i, _i, _i, _i, _vpp],
+    "stx_buf_to_host": [_vp, _vp, _z],
+    "stx_buf_to_host_async": [_vp, _vp, _z],
+    "stx_buf_view": [_vp, _i, _i, _i, _i, _vpp],
+    "stx_buf_info": [_vp, C.POINTER(C.c_int64)],
+    "stx_buf_device_ptr": [_vp, _vpp],
+    "stx_buf_free": [_vp],
+    "stx_warp_roi": [_vp, _i, _f, _fp, _fp, _i, _i, _ip],
+    "stx_warp_rois": [_vp, _i, _f, _i, _fp, _fp, _ip, _ip],
+    "stx_warp": [_vp, _i, _f, _fp, _fp, _vp, _i, _i, _vpp, _ip],
+    "stx_warp_image_and_mask": [_vp, _i, _f, _fp, _fp, _vp, _vpp, _vpp, _ip],
+    "stx_warp_batch": [_vp, _i, _f, _i, _fp, _fp, _vpp, _ip, _vpp, _ip, _i, _vpp, _vpp, _ip, _vpp],
+    "stx_warp_tables_free": [_vp],
+    "stx_warp_mask": [_vp, _i, _f, _fp, _fp, _i, _i, _vpp, _ip],
+    "stx_gain_apply": [_vp, _vp, _fp],
+    "stx_block_gain_apply_batch": [_vp, _i, _vpp, _vpp, _ip, _ip],
+    "stx_resize_linear_exact": [_vp, _vp, _i, _i, _vpp],
+    "stx_resize_linear_exact_batch": [_vp, _i, _vpp, _ip, _vpp],
+    "stx_seam_mask_resize": [_vp, _vp, _vp, _vpp],
+    "stx_seam_mask_resize_batch": [_vp, _i, _vpp, _vpp, _vpp],
+    "stx_seam_mask_resize_batch_sub": [_vp, _i, _vpp, _vpp, _ip, _vpp],
+    "stx_timelapse_frame": [_vp, _vp, _i, _i, _ip, _vpp],
+    "stx_result_roi": [_i, _ip, _ip, _ip],
+    "stx_blend_create": [_vp, _i, _i, _f, _ip, _vpp],
+    "stx_blend_num_bands": [_vp, _ip],
+    "stx_blend_feed": [_vp, _vp, _vp, _i, _i],
+    "stx_blend_finish": [_vp, _vpp, _vpp],
+    "stx_blend_finish_ex": [_vp, _vpp, _vpp, _vpp],
+    "stx_blend_destroy": [_vp],
+    "stx_blend_keep_weights": [_vp, _vpp],
+    "stx_blend_use_weights": [_vp, _vp, _ip],
+    "stx_mb_weights_free": [_vp],
+    "stx_blend_set_band": [_vp, _i, _i],
+    "stx_blend_feed_ex": [_vp, _vp, _vp, _i, _i, _i],
+    "stx_blend_contrib_rect": [_vp, _i, _i, _i, _i, _i, _i, _ip, _zp],
+    "stx_blend_export_contrib": [_vp, _i, _i, _i, _vpp, _ip],
+    "stx_blend_export_contribs": [_vp, _i, _ip, _ip, _ip, _vpp, _ip],
+    "stx_blend_build": [_vp],
+    "stx_blend_feed_contrib_ex": [_vp, _i, _ip, _vp, _i],
+    "stx_buf_flags": [_vp, _ip],
+    "stx_strip_rect": [_vp, _i, _i, _i, _i, _i, _i, _ip, _zp],
+    "stx_view_rect": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _ip],
+    "stx_strip_pack": [_vp, _vp, _vp, _i, _i, _vpp],
+    "stx_strip_pack_batch_ex": [_vp, _i, _vpp, _vpp, _ip, _ip, _i, _vpp],
+    "stx_strip_bytes": [_i, _i, _i, _zp],
+    "stx_strip_unpack": [_vp, _i, _i, _i, _vpp, _vpp],
+    "stx_blend_feed_strips": [_vp, _i, _vpp, _ip, _ip, _ip, _ip, _ip, _i],
+    "stx_comm_unique_id": [_ubp],
+    "stx_comm_create": [_vp, _i, _i, _ubp, _vpp],
+    "stx_comm_exchange_begin_on": [_vp, _vp, _i, _ip, _ip, _vpp, _zp],
+    "stx_comm_exchange_end_on": [_vp, _vp],
+    "stx_comm_info": [_vp, _ip],
+    "stx_comm_destroy": [_vp],
+    "stx_prof_enable": [_vp, _i],
+    "stx_prof_reset": [_vp],
+    "stx_prof_count": [_vp, _ip],
+    "stx_prof_get": [_vp, _i, C.c_char_p, _i, C.POINTER(C.c_int64), _dp, _dp],
+    "stx_mark": [_vp, _i],
+    "stx_mark_elapsed_ms": [_vp, _i, _i, _dp],
+    "stx_exposure_stats": [_vp, _i, _i, _vpp, _vpp, _ip, _i, _llp, _ip, _llp, _dp],
+    "stx_exposure_solve": [_i, _i, _ip, _dp, _ubp, _dp],
+    "stx_set_exposure_solver": [_i],
+    "stx_get_exposure_solver": [],
+    "stx_exposure_feed_ex": [_vp, _i, _i, _vpp, _vpp, _ip, _i, _i, _i, _dp, _llp, _dp],
+    "stx_exposure_solve_device": [_vp, _i, _i, _ip, _dp, _ubp, _dp, _dp],
+    "stx_lu_solve_device": [_vp, _i, _dp, _dp, _dp, _dp],
+    "stx_seam_find": [_vp, _i, _i, _ip, _ip, _vpp, _vpp, _dp],
+    "stx_seam_schedule": [_i, _ip, _ip, _ip, _ip, _ip],
+    "stx_color_seam_find": [_vp, _i, _ip, _ip, _vpp, _vpp, _vpp, _dp],
+    "stx_crop_lir": [_vp, _vp, _ip, _ip, _dp],
+    "stx_features_detect": [_vp, _i, _vpp, _vpp, _i, _i, _i, _ip, _ip, _ip, _ip, C.POINTER(C.c_byte), _ip, _ip, _llp, _ubp, _dp],
+    "stx_match_features": [_vp, _i, _vpp, _ip, _vpp, _ip, _i, _i, _i, _d, _u, _ip, _ip, _ubp, _ip, _dp, _dp],
+    "stx_match_features_model": [_vp, _i, _vpp, _ip, _vpp, _ip, _i, _i, _i, _d, _u, _i, _ip, _ip, _ubp, _ip, _dp, _dp],
+    "stx_ray_problem_create": [_vp, _i, _ip, _llp, _dp, _vpp],
+    "stx_ray_problem_eval": [_vp, _i, _dp, _dp, _dp],
+    "stx_affine_problem_eval": [_vp, _i, _dp, _dp, _dp],
+    "stx_reproj_problem_eval": [_vp, _i, _dp, _dp, _dp],
+    "stx_ray_problem_free": [_vp],
+    "stx_ingest": [_vp, _i, C.POINTER(ForeignFrame), _i, _i, _vp, _i, _vpp],
+    # include/stitching_amd_debug.h: test hooks, never called by the package's classes
+    "stx_debug_warp_maps": [_vp, _i, _f, _fp, _fp, _i, _i, _i, _ip, _vpp, _vpp, _ip],
+    "stx_debug_feather_dist_cap": [],
+    "stx_debug_blend_replayed": [_vp, _ip],
+    "stx_debug_warp_table_launches": [_vp, _ip],
+    "stx_debug_blend_uploads": [_vp, _ip],
+    "stx_debug_blend_mask_stored": [_vp, _ip],
+}
+EXPORTS = tuple(PROTOTYPES)
 
 _lib = None
 
@@ -89,130 +193,10 @@ def lib():
         raise ImportError(f"{LIB_PATH} is missing: the HIP back end is not built ({build_hint()}). "
                           "stitching_amd has no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    vp, vpp = C.c_void_p, C.POINTER(C.c_void_p)
-    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
-    L.stx_version.restype = C.c_int
-    L.stx_last_error.restype = C.c_char_p
-    L.stx_set_trig_mode.argtypes = [C.c_int]
-    L.stx_get_trig_mode.restype = C.c_int
-    L.stx_set_remap_mode.argtypes = [C.c_int]
-    L.stx_get_remap_mode.restype = C.c_int
-    L.stx_set_pyrdown_mode.argtypes = [C.c_int, C.c_int]
-    L.stx_get_pyrdown_mode.argtypes = [C.POINTER(C.c_int)]
-    L.stx_get_pyrdown_mode.restype = C.c_int
-    L.stx_device_count.argtypes = [ip]
-    L.stx_ctx_create.argtypes = [C.c_int, vpp]
-    L.stx_ctx_destroy.argtypes = [vp]
-    L.stx_ctx_sync.argtypes = [vp]
-    L.stx_buf_from_host.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, vpp]
-    L.stx_buf_from_host_async.argtypes = L.stx_buf_from_host.argtypes
-    L.stx_buf_alloc.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vpp]
-    L.stx_host_alloc.argtypes = [C.c_size_t, vpp]
-    L.stx_host_free.argtypes = [vp]
-    L.stx_buf_to_host.argtypes = [vp, vp, C.c_size_t]
-    L.stx_buf_to_host_async.argtypes = [vp, vp, C.c_size_t]
-    L.stx_buf_view.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vpp]
-    L.stx_buf_info.argtypes = [vp, C.POINTER(C.c_int64)]
-    L.stx_buf_device_ptr.argtypes = [vp, vpp]
-    L.stx_buf_free.argtypes = [vp]
-    L.stx_warp_roi.argtypes = [vp, C.c_int, C.c_float, fp, fp, C.c_int, C.c_int, ip]
-    L.stx_warp_rois.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, fp, ip, ip]
-    L.stx_warp.argtypes = [vp, C.c_int, C.c_float, fp, fp, vp, C.c_int, C.c_int, vpp, ip]
-    L.stx_warp_image_and_mask.argtypes = [vp, C.c_int, C.c_float, fp, fp, vp, vpp, vpp, ip]
-    L.stx_warp_batch.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, fp, vpp, vpp, vpp, ip]
-    L.stx_warp_batch_rects.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, fp, vpp, ip, vpp, vpp]
-    L.stx_warp_batch_gain.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, fp, vpp, ip, vpp, ip, vpp, vpp, ip]
-    L.stx_warp_batch_rects_kept.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, fp, vpp, ip, vpp, vpp, vpp]
-    L.stx_warp_batch_gain_kept.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, fp, vpp, ip, vpp, ip, vpp, vpp, vpp]
-    L.stx_warp_tables_free.argtypes = [vp]
-    L.stx_warp_batch_with_rois_kept.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, fp, vpp, vpp, ip, vpp, vpp, ip, vpp]
-    L.stx_warp_batch_with_rois.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, fp, vpp, vpp, ip, vpp, vpp, ip]
-    L.stx_warp_mask.argtypes = [vp, C.c_int, C.c_float, fp, fp, C.c_int, C.c_int, vpp, ip]
-    L.stx_gain_apply.argtypes = [vp, vp, fp]
-    L.stx_block_gain_apply.argtypes = [vp, vp, vp]
-    L.stx_block_gain_apply_batch.argtypes = [vp, C.c_int, vpp, vpp, ip, ip]
-    L.stx_resize_linear_exact.argtypes = [vp, vp, C.c_int, C.c_int, vpp]
-    L.stx_resize_linear_exact_batch.argtypes = [vp, C.c_int, vpp, ip, vpp]
-    L.stx_seam_mask_resize.argtypes = [vp, vp, vp, vpp]
-    L.stx_seam_mask_resize_batch.argtypes = [vp, C.c_int, vpp, vpp, vpp]
-    L.stx_seam_mask_resize_batch_sub.argtypes = [vp, C.c_int, vpp, vpp, ip, vpp]
-    L.stx_timelapse_frame.argtypes = [vp, vp, C.c_int, C.c_int, ip, vpp]
-    L.stx_result_roi.argtypes = [C.c_int, ip, ip, ip]
-    L.stx_blend_create.argtypes = [vp, C.c_int, C.c_int, C.c_float, ip, vpp]
-    L.stx_blend_num_bands.argtypes = [vp, ip]
-    L.stx_blend_feed.argtypes = [vp, vp, vp, C.c_int, C.c_int]
-    L.stx_blend_finish.argtypes = [vp, vpp, vpp]
-    L.stx_blend_finish_ex.argtypes = [vp, vpp, vpp, vpp]
-    L.stx_blend_destroy.argtypes = [vp]
-    L.stx_blend_keep_weights.argtypes = [vp, vpp]
-    L.stx_blend_use_weights.argtypes = [vp, vp, ip]
-    L.stx_mb_weights_free.argtypes = [vp]
-    L.stx_blend_set_band.argtypes = [vp, C.c_int, C.c_int]
-    L.stx_blend_feed_ex.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int]
-    L.stx_blend_contrib_rect.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip,
-                                         C.POINTER(C.c_size_t)]
-    L.stx_blend_export_contrib.argtypes = [vp, C.c_int, C.c_int, C.c_int, vpp, ip]
-    L.stx_blend_export_contribs.argtypes = [vp, C.c_int, ip, ip, ip, vpp, ip]
-    L.stx_blend_build.argtypes = [vp]
-    L.stx_blend_feed_contrib.argtypes = [vp, C.c_int, ip, vp]
-    L.stx_blend_feed_contrib_ex.argtypes = [vp, C.c_int, ip, vp, C.c_int]
-    L.stx_buf_flags.argtypes = [vp, ip]
-    L.stx_strip_rect.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_size_t)]
-    L.stx_view_rect.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip]
-    L.stx_strip_pack.argtypes = [vp, vp, vp, C.c_int, C.c_int, vpp]
-    L.stx_strip_unpack.argtypes = [vp, C.c_int, C.c_int, C.c_int, vpp, vpp]
-    L.stx_strip_pack_batch.argtypes = [vp, C.c_int, vpp, vpp, ip, ip, vpp]
-    L.stx_strip_pack_batch_ex.argtypes = [vp, C.c_int, vpp, vpp, ip, ip, C.c_int, vpp]
-    L.stx_strip_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
-    L.stx_blend_feed_strips.argtypes = [vp, C.c_int, vpp, ip, ip, ip, ip, ip, C.c_int]
-    L.stx_comm_unique_id.argtypes = [C.POINTER(C.c_ubyte)]
-    L.stx_comm_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_ubyte), vpp]
-    L.stx_comm_exchange.argtypes = [vp, C.c_int, ip, ip, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-    L.stx_comm_exchange_begin.argtypes = [vp, C.c_int, ip, ip, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-    L.stx_comm_exchange_end.argtypes = [vp]
-    L.stx_comm_exchange_begin_on.argtypes = [vp, vp, C.c_int, ip, ip, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-    L.stx_comm_exchange_end_on.argtypes = [vp, vp]
-    L.stx_comm_info.argtypes = [vp, ip]
-    L.stx_comm_destroy.argtypes = [vp]
-    L.stx_prof_enable.argtypes = [vp, C.c_int]
-    L.stx_prof_reset.argtypes = [vp]
-    L.stx_prof_count.argtypes = [vp, ip]
-    L.stx_prof_get.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double),
-                               C.POINTER(C.c_double)]
-    L.stx_debug_blend_replayed.argtypes = [vp, ip]
-    L.stx_debug_warp_table_launches.argtypes = [vp, ip]
-    L.stx_debug_blend_uploads.argtypes = [vp, ip]
-    L.stx_debug_blend_mask_stored.argtypes = [vp, ip]
-    L.stx_debug_warp_maps.argtypes = [vp, C.c_int, C.c_float, fp, fp, C.c_int, C.c_int, C.c_int, ip, vpp, vpp, ip]
-    llp, dp = C.POINTER(C.c_longlong), C.POINTER(C.c_double)
-    L.stx_exposure_feed.argtypes = [vp, C.c_int, C.c_int, vpp, vpp, ip, C.c_int, C.c_int, dp, llp, dp]
-    L.stx_exposure_stats.argtypes = [vp, C.c_int, C.c_int, vpp, vpp, ip, C.c_int, llp, ip, llp, dp]
-    L.stx_exposure_solve.argtypes = [C.c_int, C.c_int, ip, dp, C.POINTER(C.c_ubyte), dp]
-    L.stx_set_exposure_solver.argtypes = [C.c_int]
-    L.stx_exposure_feed_ex.argtypes = [vp, C.c_int, C.c_int, vpp, vpp, ip, C.c_int, C.c_int, C.c_int, dp, llp, dp]
-    L.stx_exposure_solve_device.argtypes = [vp, C.c_int, C.c_int, ip, dp, C.POINTER(C.c_ubyte), dp, dp]
-    L.stx_lu_solve_device.argtypes = [vp, C.c_int, dp, dp, dp, dp]
-    L.stx_seam_find.argtypes = [vp, C.c_int, C.c_int, ip, ip, vpp, vpp, dp]
-    L.stx_seam_schedule.argtypes = [C.c_int, ip, ip, ip, ip, ip]
-    L.stx_color_seam_find.argtypes = [vp, C.c_int, ip, ip, vpp, vpp, vpp, dp]
-    L.stx_crop_lir.argtypes = [vp, vp, ip, ip, dp]
-    L.stx_features_detect.argtypes = [vp, C.c_int, vpp, vpp, C.c_int, C.c_int, C.c_int, ip, ip, ip, ip, C.POINTER(C.c_byte), ip, ip, llp,
-                                      C.POINTER(C.c_ubyte), dp]
-    L.stx_match_features.argtypes = [vp, C.c_int, vpp, ip, vpp, ip, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint, ip, ip,
-                                     C.POINTER(C.c_ubyte), ip, dp, dp]
-    L.stx_match_features_model.argtypes = [vp, C.c_int, vpp, ip, vpp, ip, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint, C.c_int, ip, ip,
-                                           C.POINTER(C.c_ubyte), ip, dp, dp]
-    L.stx_ray_problem_create.argtypes = [vp, C.c_int, ip, llp, dp, vpp]
-    L.stx_ray_problem_eval.argtypes = [vp, C.c_int, dp, dp, dp]
-    L.stx_affine_problem_eval.argtypes = [vp, C.c_int, dp, dp, dp]
-    L.stx_reproj_problem_eval.argtypes = [vp, C.c_int, dp, dp, dp]
-    L.stx_ray_problem_free.argtypes = [vp]
-    L.stx_ingest.argtypes = [vp, C.c_int, C.POINTER(ForeignFrame), C.c_int, C.c_int, vp, C.c_int, vpp]
-    L.stx_mark.argtypes = [vp, C.c_int]
-    L.stx_mark_elapsed_ms.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_double)]
-    for name in EXPORTS:
-        if name not in ("stx_version", "stx_last_error"):
-            getattr(L, name).restype = C.c_int
+    for name, argtypes in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.argtypes = argtypes
+        fn.restype = C.c_char_p if name == "stx_last_error" else C.c_int
     _lib = L
     return L
 

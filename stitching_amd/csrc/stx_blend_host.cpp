@@ -810,11 +810,6 @@ STX_EXPORT int stx_blend_build(stx_blender* b)
     return mb_ensure_pyramids(b);
 }
 
-STX_EXPORT int stx_blend_feed_contrib(stx_blender* b, int order, const int rect_xywh[4], const stx_buf* packed)
-{
-    return stx_blend_feed_contrib_ex(b, order, rect_xywh, packed, 0);
-}
-
 STX_EXPORT int stx_blend_feed_contrib_ex(stx_blender* b, int order, const int rect_xywh[4], const stx_buf* packed, int flags)
 {
     if (!b || !rect_xywh || !packed) return stx_fail(STX_ERR_INVALID, "null argument");

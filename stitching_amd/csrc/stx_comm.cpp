@@ -79,7 +79,7 @@ struct stx_comm {
     RcclComm comm;
     int nranks, rank;
     // exchanges run on their own stream so that independent kernels queued on the context stream after
-    // stx_comm_exchange_begin overlap with the transfer
+    // stx_comm_exchange_begin_on overlap with the transfer
     hipStream_t stream = nullptr;
     // one (ready, done) event pair per context that exchanges through this communicator: several panoramas in flight
     // each wait for their OWN transfer only
@@ -125,14 +125,6 @@ STX_EXPORT int stx_comm_info(const stx_comm* comm, int out[4])
     if (g_rccl.GetVersion) STX_RCCL(g_rccl.GetVersion(&out[2]));
     return STX_OK;
 }
-
-STX_EXPORT int stx_comm_exchange_begin(stx_comm* comm, int n_ops, const int* peers, const int* is_send, void* const* dev_ptrs,
-                                       const size_t* bytes)
-{
-    return stx_comm_exchange_begin_on(comm, comm ? comm->ctx : nullptr, n_ops, peers, is_send, dev_ptrs, bytes);
-}
-
-STX_EXPORT int stx_comm_exchange_end(stx_comm* comm) { return stx_comm_exchange_end_on(comm, comm ? comm->ctx : nullptr); }
 
 // `on`: the context (same device) whose stream produced the send buffers and will consume the receive buffers.
 // One communicator serves several contexts (panoramas in flight on different streams): their exchanges run one
@@ -186,13 +178,6 @@ STX_EXPORT int stx_comm_exchange_end_on(stx_comm* comm, stx_ctx* on)
     STX_HIP(hipStreamWaitEvent(on->stream, it->second.done, 0));
     it->second.in_flight = false;
     return STX_OK;
-}
-
-STX_EXPORT int stx_comm_exchange(stx_comm* comm, int n_ops, const int* peers, const int* is_send, void* const* dev_ptrs,
-                                 const size_t* bytes)
-{
-    STX_TRY(stx_comm_exchange_begin(comm, n_ops, peers, is_send, dev_ptrs, bytes));
-    return stx_comm_exchange_end(comm);
 }
 
 STX_EXPORT int stx_comm_destroy(stx_comm* comm)

@@ -454,18 +454,6 @@ STX_EXPORT int stx_exposure_stats(stx_ctx* ctx, int kind, int n, const stx_buf* 
     return STX_OK;
 }
 
-STX_EXPORT int stx_exposure_feed(stx_ctx* ctx, int kind, int n, const stx_buf* const* imgs, const stx_buf* const* masks,
-                                 const int* corners_xy, int block_size, int nr_feeds, double* out_gains, long long* inout_count,
-                                 double out_info[4])
-{
-    double info[8];
-    STX_TRY(stx_exposure_feed_ex(ctx, kind, n, imgs, masks, corners_xy, block_size, nr_feeds, STX_EXPOSURE_SOLVER_DEFAULT, out_gains,
-                                 inout_count, out_info ? info : nullptr));
-    if (out_info && out_gains)
-        for (int k = 0; k < 4; k++) out_info[k] = info[k];
-    return STX_OK;
-}
-
 STX_EXPORT int stx_exposure_feed_ex(stx_ctx* ctx, int kind, int n, const stx_buf* const* imgs, const stx_buf* const* masks,
                                     const int* corners_xy, int block_size, int nr_feeds, int solver, double* out_gains,
                                     long long* inout_count, double out_info[8])

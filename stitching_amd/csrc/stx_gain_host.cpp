@@ -1,5 +1,5 @@
 // stx_gain_host.cpp — host side of the exposure gains multiplied into warped images between warp and feed: one gain per image or
-// channel (stx_gain_apply) and block gain maps (stx_block_gain_apply*), with the coefficient tables of cv::resize(INTER_LINEAR).
+// channel (stx_gain_apply) and block gain maps (stx_block_gain_apply_batch), with the coefficient tables of cv::resize(INTER_LINEAR).
 // Kernels: stx_gain.hip.  Compiled with -ffp-contract=off: the tables restate OpenCV's baseline (non-FMA) evaluation order.
 #include <algorithm>
 #include <cmath>
@@ -121,10 +121,4 @@ STX_EXPORT int stx_block_gain_apply_batch(stx_ctx* ctx, int n, stx_buf* const* i
     std::vector<void*> yts(bi.size());
     for (size_t i = 0; i < bi.size(); i++) { Hs[i] = (float*)((uint8_t*)d.get() + offH[i]); yts[i] = (uint8_t*)d.get() + offY[i]; }
     return stx_launch_block_gain_batch(ctx, (int)bi.size(), bi.data(), bg.data(), sub.data(), Hs.data(), yts.data(), fast.data());
-}
-
-STX_EXPORT int stx_block_gain_apply(stx_ctx* ctx, stx_buf* img, const stx_buf* gain_map)
-{
-    if (!ctx) return stx_fail(STX_ERR_INVALID, "null argument");
-    return stx_block_gain_apply_batch(ctx, 1, &img, &gain_map, nullptr, nullptr);
 }

@@ -212,12 +212,12 @@ struct StxWarpLaunch {
     uint8_t* dmask; size_t dmask_stride;  // u8x1 or null
     int nearest_src;               // 1: out image = nearest sample of a u8x1 source (generic mask warp)
     int debug_maps = 0;            // stx_debug_warp_maps (test hook): dimg / dmask are f32 maps of x / y; 1: the kernel a warp would take, 2: the generic one
-    // fused exposure gain (stx_warp_batch_gain): device tables made by stx_launch_gain_rows for this destination rectangle; null: none
+    // fused exposure gain (stx_warp_batch with gain_maps): device tables made by stx_launch_gain_rows for this destination rectangle; null: none
     const float* gain_H = nullptr; long long gain_hstride = 0; const void* gain_yt = nullptr; int gain_gh = 0;
 };
 // typed projectors only (plane / affine / cylindrical / spherical / mercator), Q15 or float remap: what a fused gain needs
 bool stx_warp_fast_eligible(const StxWarpLaunch& L);
-// The column / row tables of one batched warp call of the typed projectors, kept between calls (stx_warp_batch_rects_kept): the device
+// The column / row tables of one batched warp call of the typed projectors, kept between calls (stx_warp_batch with tables): the device
 // block and, per image, everything warp_tables_kernel reads.  The launcher compares the record with the call in front of it and rebuilds
 // the tables into the handle on any difference: the decision is never the caller's.
 struct StxWarpTabRec { int family, dw, dh, tlx, tly, trig; float scale, t0, t1, kr1, kr4, kr7; };

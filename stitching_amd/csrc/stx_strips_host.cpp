@@ -153,12 +153,6 @@ static int strip_pack_batch_impl(stx_ctx* ctx, int n, const stx_buf* const* imgs
     return STX_OK;
 }
 
-STX_EXPORT int stx_strip_pack_batch(stx_ctx* ctx, int n, const stx_buf* const* imgs, const stx_buf* const* masks, const int* x0s,
-                                    const int* x1s, stx_buf** out_packed)
-{
-    return strip_pack_batch_impl(ctx, n, imgs, masks, x0s, x1s, 0, out_packed);
-}
-
 STX_EXPORT int stx_strip_pack_batch_ex(stx_ctx* ctx, int n, const stx_buf* const* imgs, const stx_buf* const* masks, const int* x0s,
                                        const int* x1s, int flags, stx_buf** out_packed)
 {
@@ -167,7 +161,7 @@ STX_EXPORT int stx_strip_pack_batch_ex(stx_ctx* ctx, int n, const stx_buf* const
 
 STX_EXPORT int stx_strip_pack(stx_ctx* ctx, const stx_buf* img, const stx_buf* mask, int x0, int x1, stx_buf** out_packed)
 {
-    return stx_strip_pack_batch(ctx, 1, &img, &mask, &x0, &x1, out_packed);
+    return strip_pack_batch_impl(ctx, 1, &img, &mask, &x0, &x1, 0, out_packed);
 }
 
 // the image and mask of received strips: views of the flat buffers (which they keep alive); with STX_STRIP_MASK_BITS the masks

@@ -82,7 +82,7 @@ struct WarpK {
     int remap;   // STX_REMAP_*: the interpolation model of the image samples; anything but Q15 runs the one-pixel-per-lane kernels
     int num_ok;  // host-proved: |numerators| <= 2^60 and finite tables, the per-lane magnitude test is skipped
     int z_one;   // host-proved (plane / affine): z = 1.f for every pixel, the quotients are the numerators
-    // Exposure gain in the epilogue (stx_warp_batch_gain: BlocksCompensator::apply fused, stitching/stitcher.py:123,219-221): the
+    // Exposure gain in the epilogue (stx_warp_batch with gain_maps: BlocksCompensator::apply fused, stitching/stitcher.py:123,219-221): the
     // horizontally interpolated rows of the gain map over this destination rectangle's columns (gain_rows_kernel: [g_gh][g_hstride] floats,
     // g_hstride = dw rounded up to 4) and the row table (source row, bits of the fraction) of its rows; null: no gain
     const float* g_H; long long g_hstride; const int2* g_yt; int g_gh;

@@ -221,20 +221,43 @@ static RoiKey make_key(int type, float scale, const float* K, const float* R, in
     return k;
 }
 
-static int roi_cached(stx_ctx* ctx, int type, float scale, const float* K, const float* R, int w, int h,
-                      const StxProjector& proj, int* out)
+static bool roi_cache_find(const RoiKey& key, int* out_xywh)
+{
+    if (!g_roi_cache) return false;
+    auto it = g_roi_cache->find(key);
+    if (it == g_roi_cache->end()) return false;
+    memcpy(out_xywh, it->second.data(), 16);
+    return true;
+}
+
+static void roi_cache_insert(const RoiKey& key, const int* xywh)
 {
     if (!g_roi_cache) g_roi_cache = new std::map<RoiKey, std::array<int, 4>>();
-    RoiKey key = make_key(type, scale, K, R, w, h);
-    auto it = g_roi_cache->find(key);
-    if (it != g_roi_cache->end()) {
-        memcpy(out, it->second.data(), 16);
-        return STX_OK;
-    }
-    int sz[2] = {w, h};
-    STX_TRY(rois_impl(ctx, 1, &proj, sz, out));
     if (g_roi_cache->size() > 8192) g_roi_cache->clear();
-    (*g_roi_cache)[key] = {out[0], out[1], out[2], out[3]};
+    (*g_roi_cache)[key] = {xywh[0], xywh[1], xywh[2], xywh[3]};
+}
+
+// ROIs for n projectors: cached ones as they are where use_cache allows, all missing ones in ONE device pass (one synchronisation);
+// what was computed enters the cache either way
+static int rois_cached(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s, const StxProjector* ps,
+                       const int* sizes_wh, bool use_cache, int* out_xywh)
+{
+    std::vector<RoiKey> keys(n);
+    std::vector<int> miss;
+    for (int i = 0; i < n; i++) {
+        keys[i] = make_key(type, scale, K9s + 9 * i, R9s + 9 * i, sizes_wh[2 * i], sizes_wh[2 * i + 1]);
+        if (!use_cache || !roi_cache_find(keys[i], out_xywh + 4 * i)) miss.push_back(i);
+    }
+    if (miss.empty()) return STX_OK;
+    const int m = (int)miss.size();
+    std::vector<StxProjector> mp(m);
+    std::vector<int> msz(2 * (size_t)m), mroi(4 * (size_t)m);
+    for (int j = 0; j < m; j++) { mp[j] = ps[miss[j]]; msz[2 * j] = sizes_wh[2 * miss[j]]; msz[2 * j + 1] = sizes_wh[2 * miss[j] + 1]; }
+    STX_TRY(rois_impl(ctx, m, mp.data(), msz.data(), mroi.data()));
+    for (int j = 0; j < m; j++) {
+        memcpy(out_xywh + 4 * miss[j], &mroi[4 * j], 16);
+        roi_cache_insert(keys[miss[j]], &mroi[4 * j]);
+    }
     return STX_OK;
 }
 
@@ -246,7 +269,8 @@ STX_EXPORT int stx_warp_roi(stx_ctx* ctx, int type, float scale, const float K[9
     StxProjector p;
     STX_TRY(stx_make_projector(type, scale, K, R, &p));
     if (w <= 0 || h <= 0) return stx_fail(STX_ERR_INVALID, "image size %dx%d", w, h);
-    return roi_cached(ctx, type, scale, K, R, w, h, p, out_xywh);
+    const int sz[2] = {w, h};
+    return rois_cached(ctx, type, scale, 1, K, R, &p, sz, true, out_xywh);
 }
 
 STX_EXPORT int stx_warp_rois(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s,
@@ -257,13 +281,32 @@ STX_EXPORT int stx_warp_rois(stx_ctx* ctx, int type, float scale, int n, const f
     STX_TRY(stx_set_device(ctx));
     std::vector<StxProjector> ps(n);
     for (int i = 0; i < n; i++) STX_TRY(stx_make_projector(type, scale, K9s + 9 * i, R9s + 9 * i, &ps[i]));
-    STX_TRY(rois_impl(ctx, n, ps.data(), sizes_wh, out_xywh));
-    if (!g_roi_cache) g_roi_cache = new std::map<RoiKey, std::array<int, 4>>();
-    if (g_roi_cache->size() > 8192) g_roi_cache->clear();
-    for (int i = 0; i < n; i++)
-        (*g_roi_cache)[make_key(type, scale, K9s + 9 * i, R9s + 9 * i, sizes_wh[2 * i], sizes_wh[2 * i + 1])] = {
-            out_xywh[4 * i], out_xywh[4 * i + 1], out_xywh[4 * i + 2], out_xywh[4 * i + 3]};
+    return rois_cached(ctx, type, scale, n, K9s, R9s, ps.data(), sizes_wh, false, out_xywh);  // always computed: the call IS the ROI pass
+}
+
+static int check_warp_rect(const int* r)
+{
+    if (r[2] <= 0 || r[3] <= 0 || (long long)r[2] * r[3] > (1ll << 33))
+        return stx_fail(STX_ERR_INVALID, "degenerate warp roi %dx%d (camera parameters?)", r[2], r[3]);
     return STX_OK;
+}
+
+// the launch of one image: destination rectangle `rect` of projector p; src may be null (mask only: sw x sh is all that is read of it),
+// dimg / dmask likewise
+static StxWarpLaunch warp_launch(const StxProjector& p, const int* rect, const stx_buf* src, int sw, int sh, const stx_buf* dimg,
+                                 const stx_buf* dmask)
+{
+    StxWarpLaunch L;
+    L.proj = p;
+    L.tlx = rect[0]; L.tly = rect[1]; L.dw = rect[2]; L.dh = rect[3];
+    L.src = src ? src->ptr : nullptr;
+    L.sw = sw; L.sh = sh;
+    L.sstride = src ? src->stride : 0;
+    L.src_channels = src ? src->c : 0;
+    L.nearest_src = 0;
+    L.dimg = dimg ? dimg->ptr : nullptr; L.dimg_stride = dimg ? dimg->stride : 0;
+    L.dmask = dmask ? dmask->ptr : nullptr; L.dmask_stride = dmask ? dmask->stride : 0;
+    return L;
 }
 
 static int warp_impl(stx_ctx* ctx, int type, float scale, const float* K, const float* R, const stx_buf* src, int sw,
@@ -273,27 +316,15 @@ static int warp_impl(stx_ctx* ctx, int type, float scale, const float* K, const 
     StxProjector p;
     STX_TRY(stx_make_projector(type, scale, K, R, &p));
     int roi[4];
-    STX_TRY(roi_cached(ctx, type, scale, K, R, sw, sh, p, roi));
-    if (roi[2] <= 0 || roi[3] <= 0 || (long long)roi[2] * roi[3] > (1ll << 33))
-        return stx_fail(STX_ERR_INVALID, "degenerate warp roi %dx%d (camera parameters?)", roi[2], roi[3]);
+    const int sz[2] = {sw, sh};
+    STX_TRY(rois_cached(ctx, type, scale, 1, K, R, &p, sz, true, roi));
+    STX_TRY(check_warp_rect(roi));
     StxBufRef bi, bm;
     if (want_img) STX_TRY(stx_buf_new(ctx, roi[2], roi[3], nearest_src ? 1 : 3, STX_U8, &bi));
     if (want_mask) STX_TRY(stx_buf_new(ctx, roi[2], roi[3], 1, STX_U8, &bm));
-    StxWarpLaunch L;
-    L.proj = p;
-    L.tlx = roi[0]; L.tly = roi[1]; L.dw = roi[2]; L.dh = roi[3];
-    L.src = src ? src->ptr : nullptr;
-    L.sw = sw; L.sh = sh;
-    L.sstride = src ? src->stride : 0;
-    L.src_channels = src ? src->c : 0;
+    // generic INTER_NEAREST warp of a u8x1 source: the "mask" path writes the image
+    StxWarpLaunch L = nearest_src ? warp_launch(p, roi, src, sw, sh, nullptr, bi.get()) : warp_launch(p, roi, src, sw, sh, bi.get(), bm.get());
     L.nearest_src = nearest_src ? 1 : 0;
-    if (nearest_src) {  // generic INTER_NEAREST warp of a u8x1 source: the "mask" path writes the image
-        L.dimg = nullptr; L.dimg_stride = 0;
-        L.dmask = bi->ptr; L.dmask_stride = bi->stride;
-    } else {
-        L.dimg = bi ? bi->ptr : nullptr; L.dimg_stride = bi ? bi->stride : 0;
-        L.dmask = bm ? bm->ptr : nullptr; L.dmask_stride = bm ? bm->stride : 0;
-    }
     STX_TRY(stx_launch_warp(ctx, L));
     if (bm) bm->mask_binary = 1;  // remapNearest of a 255-filled source with a constant-0 border
     if (out_img) *out_img = bi.release();
@@ -324,19 +355,52 @@ STX_EXPORT int stx_warp(stx_ctx* ctx, int type, float scale, const float K[9], c
     return STX_OK;
 }
 
-// rects: null -> the destination rectangle of image i is its ROI (found here, cached); else the caller's rectangle in warp
+// The tables of one batched call (include/stitching_amd.h: stx_warp_batch, `tables`): the caller's handle, or a fresh one that becomes
+// the caller's when the call succeeds and is given back when it fails — the handle of a failed call stays empty.
+struct WarpTablesSlot {
+    stx_warp_tables** slot;
+    std::unique_ptr<stx_warp_tables> fresh;
+    WarpTablesSlot(stx_ctx* ctx, stx_warp_tables** slot_) : slot(slot_)
+    {
+        if (slot && !*slot) {
+            fresh.reset(new stx_warp_tables());
+            fresh->ctx = ctx;
+        }
+    }
+    ~WarpTablesSlot()
+    {
+        if (fresh && fresh->block) { stx_set_device(fresh->ctx); stx_dev_free(fresh->ctx, fresh->block); }
+    }
+    stx_warp_tables* get() const { return fresh ? fresh.get() : (slot ? *slot : nullptr); }
+    int keep()
+    {
+        if (fresh) *slot = fresh.release();
+        return STX_OK;
+    }
+};
+
+// rects_xywh: null -> the destination rectangle of image i is its ROI (found here, cached); else the caller's rectangle in warp
 // coordinates (any sub-rectangle of the ROI gives exactly the ROI warp's pixels there: every pixel is mapped on its own)
-static int warp_batch_impl(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s,
-                           const stx_buf* const* srcs, const int* rects, stx_buf** out_imgs, stx_buf** out_masks, int* out_xywh,
-                           const stx_buf* const* gains = nullptr, const int* gflags = nullptr, bool fresh_rois = false,
-                           stx_warp_tables* kept = nullptr)
+STX_EXPORT int stx_warp_batch(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s,
+                              const stx_buf* const* srcs, const int* rects_xywh, const stx_buf* const* gain_maps, const int* gain_flags,
+                              int flags, stx_buf** out_imgs, stx_buf** out_masks, int* out_xywh, stx_warp_tables** tables)
 {
+    const bool fresh_rois = (flags & STX_WARP_FRESH_ROIS) != 0;
     if (!ctx || !K9s || !R9s || !srcs || n < 0) return stx_fail(STX_ERR_INVALID, "bad argument");
-    if (!out_imgs && !out_masks) return stx_fail(STX_ERR_INVALID, "nothing requested");
-    if (n == 0) return STX_OK;
+    if (!out_imgs && !out_masks) return stx_fail(STX_ERR_INVALID, "nothing requested: out_imgs and out_masks are both null");
+    if (gain_maps && !out_imgs) return stx_fail(STX_ERR_INVALID, "gains without images: gain_maps needs out_imgs");
+    if (flags & ~STX_WARP_FRESH_ROIS) return stx_fail(STX_ERR_INVALID, "unknown flags 0x%x", flags & ~STX_WARP_FRESH_ROIS);
+    if (fresh_rois && !out_xywh) return stx_fail(STX_ERR_INVALID, "STX_WARP_FRESH_ROIS needs out_xywh: the ROIs of the call are its result");
+    if (fresh_rois && rects_xywh) return stx_fail(STX_ERR_INVALID, "STX_WARP_FRESH_ROIS with rects_xywh: given rectangles need no ROI pass");
+    if (tables && !rects_xywh && !fresh_rois)
+        return stx_fail(STX_ERR_INVALID, "tables needs rects_xywh or STX_WARP_FRESH_ROIS: kept tables belong to given rectangles");
+    if (tables && *tables && (*tables)->ctx != ctx)
+        return stx_fail(STX_ERR_INVALID, "warp tables: the handle belongs to another context (no cross-stream use)");
+    WarpTablesSlot kept(ctx, tables);
+    if (n == 0) return kept.keep();
     STX_TRY(stx_set_device(ctx));
     std::vector<StxProjector> ps(n);
-    std::vector<int> rois(4 * (size_t)n), sizes(2 * (size_t)n);
+    std::vector<int> sizes(2 * (size_t)n);
     for (int i = 0; i < n; i++) {
         if (!srcs[i] || srcs[i]->elem != STX_U8 || srcs[i]->c != 3) return stx_fail(STX_ERR_INVALID, "warp source %d must be u8x3", i);
         // sources may live in another context of the same device (long-lived read-only inputs shared by several streams)
@@ -345,60 +409,29 @@ static int warp_batch_impl(stx_ctx* ctx, int type, float scale, int n, const flo
         sizes[2 * i] = srcs[i]->w;
         sizes[2 * i + 1] = srcs[i]->h;
     }
-    // ROIs: cached ones as they are, all missing ones in ONE device pass (one synchronisation)
-    if (!g_roi_cache) g_roi_cache = new std::map<RoiKey, std::array<int, 4>>();
-    std::vector<int> miss;
-    // with gains the ROI of every image is needed even under caller-given rectangles: the gain map lies over the WHOLE warped image
-    const bool need_rois = !rects || gains;
-    for (int i = 0; i < n && need_rois; i++) {
-        if (fresh_rois) { miss.push_back(i); continue; }  // the ROI pass belongs to this call (stx_warp_batch_with_rois)
-        auto it = g_roi_cache->find(make_key(type, scale, K9s + 9 * i, R9s + 9 * i, sizes[2 * i], sizes[2 * i + 1]));
-        if (it != g_roi_cache->end()) memcpy(&rois[4 * i], it->second.data(), 16);
-        else miss.push_back(i);
-    }
-    if (!miss.empty()) {
-        const int m = (int)miss.size();
-        std::vector<StxProjector> mp(m);
-        std::vector<int> msz(2 * (size_t)m), mroi(4 * (size_t)m);
-        for (int j = 0; j < m; j++) { mp[j] = ps[miss[j]]; msz[2 * j] = sizes[2 * miss[j]]; msz[2 * j + 1] = sizes[2 * miss[j] + 1]; }
-        STX_TRY(rois_impl(ctx, m, mp.data(), msz.data(), mroi.data()));
-        if (g_roi_cache->size() > 8192) g_roi_cache->clear();
-        for (int j = 0; j < m; j++) {
-            const int i = miss[j];
-            memcpy(&rois[4 * i], &mroi[4 * j], 16);
-            (*g_roi_cache)[make_key(type, scale, K9s + 9 * i, R9s + 9 * i, sizes[2 * i], sizes[2 * i + 1])] = {
-                mroi[4 * j], mroi[4 * j + 1], mroi[4 * j + 2], mroi[4 * j + 3]};
-        }
-    }
-    std::vector<int> full_rois;
-    if (gains) {
-        if (!out_imgs) return stx_fail(STX_ERR_INVALID, "gains without images");
-        full_rois = rois;
-        for (int i = 0; i < n; i++) STX_TRY(block_gain_check(ctx, nullptr, gains[i]));
-    }
-    if (rects) {
-        memcpy(rois.data(), rects, sizeof(int) * 4 * (size_t)n);
-        for (int i = 0; i < n && gains; i++) {
+    // with gains the ROI of every image is needed even under caller-given rectangles: the gain map lies over the WHOLE warped image.
+    // STX_WARP_FRESH_ROIS: the ROI pass belongs to this call, whatever the cache holds.
+    std::vector<int> full_rois(4 * (size_t)n);
+    if (!rects_xywh || gain_maps)
+        STX_TRY(rois_cached(ctx, type, scale, n, K9s, R9s, ps.data(), sizes.data(), !fresh_rois, full_rois.data()));
+    const std::vector<int> rois = rects_xywh ? std::vector<int>(rects_xywh, rects_xywh + 4 * (size_t)n) : full_rois;
+    if (gain_maps) {
+        for (int i = 0; i < n; i++) STX_TRY(block_gain_check(ctx, nullptr, gain_maps[i]));
+        for (int i = 0; i < n && rects_xywh; i++) {
             const int *r = &rois[4 * i], *f = &full_rois[4 * i];
             if (r[0] < f[0] || r[1] < f[1] || r[0] + r[2] > f[0] + f[2] || r[1] + r[3] > f[1] + f[3])
                 return stx_fail(STX_ERR_INVALID, "image %d: with gains the rectangle must lie inside the warp roi", i);
         }
     }
+
     std::vector<StxBufRef> bi(n), bm(n);
     std::vector<StxWarpLaunch> Ls(n);
     for (int i = 0; i < n; i++) {
         const int* roi = &rois[4 * i];
-        if (roi[2] <= 0 || roi[3] <= 0 || (long long)roi[2] * roi[3] > (1ll << 33))
-            return stx_fail(STX_ERR_INVALID, "degenerate warp roi %dx%d (camera parameters?)", roi[2], roi[3]);
+        STX_TRY(check_warp_rect(roi));
         if (out_imgs) STX_TRY(stx_buf_new(ctx, roi[2], roi[3], 3, STX_U8, &bi[i]));
         if (out_masks) STX_TRY(stx_buf_new(ctx, roi[2], roi[3], 1, STX_U8, &bm[i]));
-        StxWarpLaunch& L = Ls[i];
-        L.proj = ps[i];
-        L.tlx = roi[0]; L.tly = roi[1]; L.dw = roi[2]; L.dh = roi[3];
-        L.src = srcs[i]->ptr; L.sw = srcs[i]->w; L.sh = srcs[i]->h; L.sstride = srcs[i]->stride; L.src_channels = srcs[i]->c;
-        L.nearest_src = 0;
-        L.dimg = bi[i] ? bi[i]->ptr : nullptr; L.dimg_stride = bi[i] ? bi[i]->stride : 0;
-        L.dmask = bm[i] ? bm[i]->ptr : nullptr; L.dmask_stride = bm[i] ? bm[i]->stride : 0;
+        Ls[i] = warp_launch(ps[i], roi, srcs[i], srcs[i]->w, srcs[i]->h, bi[i].get(), bm[i].get());
     }
     // Exposure gains (BlocksCompensator::apply, stitching/stitcher.py:123,219-221).  Fused into the warp's epilogue when every image runs
     // the tuned kernel and every map is a bounded single-channel one: the warped bytes leave LDS already multiplied, the 6 bytes per
@@ -406,7 +439,7 @@ static int warp_batch_impl(stx_ctx* ctx, int type, float scale, int n, const flo
     std::vector<int> sub;
     StxDevBlock gscratch;
     bool fused = false;
-    if (gains) {
+    if (gain_maps) {
         for (int i = 0; i < n; i++) {
             sub.push_back(full_rois[4 * i + 2]); sub.push_back(full_rois[4 * i + 3]);
             sub.push_back(rois[4 * i] - full_rois[4 * i]); sub.push_back(rois[4 * i + 1] - full_rois[4 * i + 1]);
@@ -414,13 +447,13 @@ static int warp_batch_impl(stx_ctx* ctx, int type, float scale, int n, const flo
         static const bool no_fuse = getenv("STITCHING_AMD_NO_GAIN_FUSION") != nullptr;  // diagnostic: A/B against the separate pass
         fused = !no_fuse;
         for (int i = 0; i < n && fused; i++)
-            fused = gains[i]->c == 1 && gflags && (gflags[i] & STX_GAIN_MAP_BOUNDED) && stx_warp_fast_eligible(Ls[i]) &&
-                    (size_t)gains[i]->h * (size_t)Ls[i].dw < ((size_t)16 << 20);
+            fused = gain_maps[i]->c == 1 && gain_flags && (gain_flags[i] & STX_GAIN_MAP_BOUNDED) && stx_warp_fast_eligible(Ls[i]) &&
+                    (size_t)gain_maps[i]->h * (size_t)Ls[i].dw < ((size_t)16 << 20);
         if (fused) {
             std::vector<size_t> offH(n), offY(n);
             size_t bytes = 0;
             for (int i = 0; i < n; i++) {
-                offH[i] = bytes; bytes += align_up((size_t)gains[i]->h * ((Ls[i].dw + 3) & ~3) * sizeof(float), 256);
+                offH[i] = bytes; bytes += align_up((size_t)gain_maps[i]->h * ((Ls[i].dw + 3) & ~3) * sizeof(float), 256);
                 offY[i] = bytes; bytes += align_up((size_t)Ls[i].dh * 8, 256);
             }
             STX_TRY(stx_dev_alloc(ctx, bytes, &gscratch));
@@ -430,108 +463,21 @@ static int warp_batch_impl(stx_ctx* ctx, int type, float scale, int n, const flo
             for (int i = 0; i < n; i++) {
                 Hs[i] = (float*)((uint8_t*)gscratch.get() + offH[i]); yts[i] = (uint8_t*)gscratch.get() + offY[i];
                 wh[2 * i] = Ls[i].dw; wh[2 * i + 1] = Ls[i].dh;
-                Ls[i].gain_H = Hs[i]; Ls[i].gain_hstride = (Ls[i].dw + 3) & ~3; Ls[i].gain_yt = yts[i]; Ls[i].gain_gh = gains[i]->h;
+                Ls[i].gain_H = Hs[i]; Ls[i].gain_hstride = (Ls[i].dw + 3) & ~3; Ls[i].gain_yt = yts[i]; Ls[i].gain_gh = gain_maps[i]->h;
             }
-            STX_TRY(stx_launch_gain_rows(ctx, n, wh.data(), gains, sub.data(), Hs.data(), yts.data()));
+            STX_TRY(stx_launch_gain_rows(ctx, n, wh.data(), gain_maps, sub.data(), Hs.data(), yts.data()));
         }
     }
-    STX_TRY(stx_launch_warp_batch(ctx, Ls.data(), n, kept));
+    STX_TRY(stx_launch_warp_batch(ctx, Ls.data(), n, kept.get()));
     gscratch.reset();  // stream-ordered reuse
-    if (gains && !fused) STX_TRY(stx_block_gain_apply_batch(ctx, n, stx_buf_ptrs(bi).data(), gains, sub.data(), gflags));
+    if (gain_maps && !fused) STX_TRY(stx_block_gain_apply_batch(ctx, n, stx_buf_ptrs(bi).data(), gain_maps, sub.data(), gain_flags));
     for (int i = 0; i < n; i++) {
         if (bm[i]) bm[i]->mask_binary = 1;
         if (out_imgs) out_imgs[i] = bi[i].release();
         if (out_masks) out_masks[i] = bm[i].release();
     }
     if (out_xywh) memcpy(out_xywh, rois.data(), sizeof(int) * 4 * (size_t)n);
-    return STX_OK;
-}
-
-STX_EXPORT int stx_warp_batch(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s,
-                              const stx_buf* const* srcs, stx_buf** out_imgs, stx_buf** out_masks, int* out_xywh)
-{
-    return warp_batch_impl(ctx, type, scale, n, K9s, R9s, srcs, nullptr, out_imgs, out_masks, out_xywh);
-}
-
-STX_EXPORT int stx_warp_batch_rects(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s,
-                                    const stx_buf* const* srcs, const int* rects_xywh, stx_buf** out_imgs, stx_buf** out_masks)
-{
-    if (!rects_xywh) return stx_fail(STX_ERR_INVALID, "null argument");
-    return warp_batch_impl(ctx, type, scale, n, K9s, R9s, srcs, rects_xywh, out_imgs, out_masks, nullptr);
-}
-
-STX_EXPORT int stx_warp_batch_gain(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s, const stx_buf* const* srcs,
-                                   const int* rects_xywh_or_null, const stx_buf* const* gain_maps, const int* gain_flags, stx_buf** out_imgs,
-                                   stx_buf** out_masks, int* out_xywh_or_null)
-{
-    if (!gain_maps || !out_imgs) return stx_fail(STX_ERR_INVALID, "null argument");
-    return warp_batch_impl(ctx, type, scale, n, K9s, R9s, srcs, rects_xywh_or_null, out_imgs, out_masks, rects_xywh_or_null ? nullptr : out_xywh_or_null,
-                           gain_maps, gain_flags);
-}
-
-// ---- tables kept per rig (include/stitching_amd.h: stx_warp_batch_rects_kept) ----------------------------------------------------------
-// the handle of a call: the caller's, or a new one that becomes the caller's when the call succeeds
-static int warp_kept_call(stx_ctx* ctx, stx_warp_tables** tables, int (*call)(stx_warp_tables*, void*), void* args)
-{
-    if (!ctx || !tables) return stx_fail(STX_ERR_INVALID, "null argument");
-    if (*tables && (*tables)->ctx != ctx)
-        return stx_fail(STX_ERR_INVALID, "warp tables: the handle belongs to another context (no cross-stream use)");
-    stx_warp_tables* t = *tables;
-    std::unique_ptr<stx_warp_tables> fresh;
-    if (!t) {
-        fresh.reset(new stx_warp_tables());
-        fresh->ctx = ctx;
-        t = fresh.get();
-    }
-    const int rc = call(t, args);
-    if (rc != STX_OK) {
-        if (fresh && fresh->block) { stx_set_device(ctx); stx_dev_free(ctx, fresh->block); }
-        return rc;
-    }
-    if (fresh) *tables = fresh.release();
-    return STX_OK;
-}
-
-STX_EXPORT int stx_warp_batch_rects_kept(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s,
-                                         const stx_buf* const* srcs, const int* rects_xywh, stx_buf** out_imgs, stx_buf** out_masks,
-                                         stx_warp_tables** tables)
-{
-    if (!rects_xywh) return stx_fail(STX_ERR_INVALID, "null argument");
-    struct A { stx_ctx* ctx; int type; float scale; int n; const float *K, *R; const stx_buf* const* srcs; const int* rects; stx_buf **oi, **om; };
-    A a{ctx, type, scale, n, K9s, R9s, srcs, rects_xywh, out_imgs, out_masks};
-    return warp_kept_call(ctx, tables, [](stx_warp_tables* t, void* p) {
-        const A& a = *static_cast<A*>(p);
-        return warp_batch_impl(a.ctx, a.type, a.scale, a.n, a.K, a.R, a.srcs, a.rects, a.oi, a.om, nullptr, nullptr, nullptr, false, t);
-    }, &a);
-}
-
-STX_EXPORT int stx_warp_batch_gain_kept(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s,
-                                        const stx_buf* const* srcs, const int* rects_xywh, const stx_buf* const* gain_maps, const int* gain_flags,
-                                        stx_buf** out_imgs, stx_buf** out_masks, stx_warp_tables** tables)
-{
-    if (!rects_xywh || !gain_maps || !out_imgs) return stx_fail(STX_ERR_INVALID, "null argument");
-    struct A { stx_ctx* ctx; int type; float scale; int n; const float *K, *R; const stx_buf* const* srcs; const int* rects;
-               const stx_buf* const* gains; const int* gflags; stx_buf **oi, **om; };
-    A a{ctx, type, scale, n, K9s, R9s, srcs, rects_xywh, gain_maps, gain_flags, out_imgs, out_masks};
-    return warp_kept_call(ctx, tables, [](stx_warp_tables* t, void* p) {
-        const A& a = *static_cast<A*>(p);
-        return warp_batch_impl(a.ctx, a.type, a.scale, a.n, a.K, a.R, a.srcs, a.rects, a.oi, a.om, nullptr, a.gains, a.gflags, false, t);
-    }, &a);
-}
-
-STX_EXPORT int stx_warp_batch_with_rois_kept(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s,
-                                             const stx_buf* const* srcs, const stx_buf* const* gain_maps_or_null, const int* gain_flags_or_null,
-                                             stx_buf** out_imgs, stx_buf** out_masks, int* out_xywh, stx_warp_tables** tables)
-{
-    if (!out_xywh) return stx_fail(STX_ERR_INVALID, "null argument");
-    if (gain_maps_or_null && !out_imgs) return stx_fail(STX_ERR_INVALID, "gains without images");
-    struct A { stx_ctx* ctx; int type; float scale; int n; const float *K, *R; const stx_buf* const* srcs;
-               const stx_buf* const* gains; const int* gflags; stx_buf **oi, **om; int* xywh; };
-    A a{ctx, type, scale, n, K9s, R9s, srcs, gain_maps_or_null, gain_flags_or_null, out_imgs, out_masks, out_xywh};
-    return warp_kept_call(ctx, tables, [](stx_warp_tables* t, void* p) {
-        const A& a = *static_cast<A*>(p);
-        return warp_batch_impl(a.ctx, a.type, a.scale, a.n, a.K, a.R, a.srcs, nullptr, a.oi, a.om, a.xywh, a.gains, a.gflags, true, t);
-    }, &a);
+    return kept.keep();
 }
 
 STX_EXPORT int stx_warp_tables_free(stx_warp_tables* t)
@@ -550,15 +496,6 @@ STX_EXPORT int stx_debug_warp_table_launches(stx_ctx* ctx, int* out_launches)
     if (!ctx || !out_launches) return stx_fail(STX_ERR_INVALID, "null argument");
     *out_launches = ctx->warp_table_launches;
     return STX_OK;
-}
-
-STX_EXPORT int stx_warp_batch_with_rois(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s,
-                                        const stx_buf* const* srcs, const stx_buf* const* gain_maps_or_null, const int* gain_flags_or_null,
-                                        stx_buf** out_imgs, stx_buf** out_masks, int* out_xywh)
-{
-    if (!out_xywh) return stx_fail(STX_ERR_INVALID, "null argument");
-    if (gain_maps_or_null && !out_imgs) return stx_fail(STX_ERR_INVALID, "gains without images");
-    return warp_batch_impl(ctx, type, scale, n, K9s, R9s, srcs, nullptr, out_imgs, out_masks, out_xywh, gain_maps_or_null, gain_flags_or_null, true);
 }
 
 STX_EXPORT int stx_warp_image_and_mask(stx_ctx* ctx, int type, float scale, const float K[9], const float R[9],
@@ -592,20 +529,15 @@ STX_EXPORT int stx_debug_warp_maps(stx_ctx* ctx, int type, float scale, const fl
     StxProjector p;
     STX_TRY(stx_make_projector(type, scale, K, R, &p));
     int roi[4];
+    const int sz[2] = {w, h};
     if (rect_xywh) memcpy(roi, rect_xywh, 16);
-    else STX_TRY(roi_cached(ctx, type, scale, K, R, w, h, p, roi));
+    else STX_TRY(rois_cached(ctx, type, scale, 1, K, R, &p, sz, true, roi));
     if (roi[2] <= 0 || roi[3] <= 0 || (long long)roi[2] * roi[3] > (1ll << 30))
         return stx_fail(STX_ERR_INVALID, "degenerate warp roi %dx%d", roi[2], roi[3]);
     StxBufRef bx, by;
     STX_TRY(stx_buf_new(ctx, roi[2], roi[3], 1, STX_F32, &bx));
     STX_TRY(stx_buf_new(ctx, roi[2], roi[3], 1, STX_F32, &by));
-    StxWarpLaunch L;
-    L.proj = p;
-    L.tlx = roi[0]; L.tly = roi[1]; L.dw = roi[2]; L.dh = roi[3];
-    L.src = nullptr; L.sw = w; L.sh = h; L.sstride = 0; L.src_channels = 0;
-    L.nearest_src = 0;
-    L.dimg = bx->ptr; L.dimg_stride = bx->stride;
-    L.dmask = by->ptr; L.dmask_stride = by->stride;
+    StxWarpLaunch L = warp_launch(p, roi, nullptr, w, h, bx.get(), by.get());
     L.debug_maps = which;
     STX_TRY(stx_launch_warp(ctx, L));
     *out_xmap = bx.release();

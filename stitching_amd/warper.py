@@ -32,7 +32,7 @@ def _fp(a):
 
 class WarpTables:
     """Owns one stx_warp_tables: the column / row tables of a batched warp of the typed projectors, kept for the next panoramas of the
-    same rig (include/stitching_amd.h: stx_warp_batch_rects_kept).  A few KB per image.  The library fills it at the first call that
+    same rig (include/stitching_amd.h: stx_warp_batch, `tables`).  A few KB per image.  The library fills it at the first call that
     takes it and decides at every later one whether the tables still answer."""
 
     def __init__(self):
@@ -189,15 +189,15 @@ class Warper:
         rects: optional (x, y, w, h) per image in warp coordinates — only that rectangle of each warped image / mask is
         produced (pixel for pixel what the full warp holds there); the returned rois are then these rectangles.
         compensator: an ExposureErrorCompensator with block gains set ("gain_blocks" / "channel_blocks"): the warped images come back
-        compensated — stitching/stitcher.py:119-123 in one call (stx_warp_batch_gain: the product rides in the warp kernel's epilogue
+        compensated — stitching/stitcher.py:119-123 in one call (gain_maps of stx_warp_batch: the product rides in the warp kernel's epilogue
         when it can).  Equal to compensator.apply_all on the plain result, byte for byte.
         with_rois (no rects): the ROI pass is made by this call, on the device, whatever earlier calls have cached, and the warps are
-        launched right behind it from native code (stx_warp_batch_with_rois: a panorama's latency, see StitchJob.run).
+        launched right behind it from native code (STX_WARP_FRESH_ROIS: a panorama's latency, see StitchJob.run).
         camera_arrays: Warper.camera_arrays(cameras, aspect), for callers that keep it.
         masks=False (with rects): the images alone — no mask is written, None comes back in their place (a caller that kept the masks
         of an earlier call with the same cameras and rectangles: StitchJob).
         tables (with rects or with_rois): a WarpTables — the typed projectors' column / row tables are kept in it from call to call; the library
-        compares what they depend on and makes them again where anything differs (stx_warp_batch_rects_kept)."""
+        compares what they depend on and makes them again where anything differs (`tables` of stx_warp_batch)."""
         ctx = self._ctx()
         srcs = [self._source(img, ctx) for img in imgs]
         cameras = list(cameras)
@@ -213,47 +213,23 @@ class Warper:
             h_mask = None
         if tables is not None and rects is None and not with_rois:
             raise StitchingError("tables= needs rects or with_rois: kept tables belong to given rectangles")
-        rois = np.zeros((n, 4), np.int32)
         blocks = compensator is not None and compensator.compensator_type in ("gain_blocks", "channel_blocks")
         if blocks and compensator.gains is None:
             raise StitchingError("ExposureErrorCompensator.set_gains(gains) must be called before apply")
-        if with_rois and rects is None:
-            ga = fl = None
-            if blocks:
-                gm = [compensator._gain_map(i, ctx) for i in range(n)]
-                ga, fl = (C.c_void_p * n)(*[g[0]._h for g in gm]), (C.c_int * n)(*[g[1] for g in gm])
-                compensator = None
-            if tables is not None:
-                _lib.check(ctx._lib.stx_warp_batch_with_rois_kept(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src, ga,
-                                                                  fl, h_img, h_mask, rois.ctypes.data_as(C.POINTER(C.c_int)), tables._ref(ctx)))
-            else:
-                _lib.check(ctx._lib.stx_warp_batch_with_rois(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src, ga, fl,
-                                                             h_img, h_mask, rois.ctypes.data_as(C.POINTER(C.c_int))))
-        elif blocks:
+        ip = C.POINTER(C.c_int)
+        rois = np.zeros((n, 4), np.int32)
+        rects_p = gain_maps = gain_flags = None
+        if rects is not None:
+            rects = np.ascontiguousarray(np.asarray(rects, np.int32).reshape(n, 4))
+            rects_p = rects.ctypes.data_as(ip)
+        if blocks:
             gm = [compensator._gain_map(i, ctx) for i in range(n)]
-            ga, fl = (C.c_void_p * n)(*[g[0]._h for g in gm]), (C.c_int * n)(*[g[1] for g in gm])
-            rp = None
-            if rects is not None:
-                rois = np.ascontiguousarray(np.asarray(rects, np.int32).reshape(n, 4))
-                rp = rois.ctypes.data_as(C.POINTER(C.c_int))
-            if tables is not None:
-                _lib.check(ctx._lib.stx_warp_batch_gain_kept(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src, rp, ga,
-                                                             fl, h_img, h_mask, tables._ref(ctx)))
-            else:
-                _lib.check(ctx._lib.stx_warp_batch_gain(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src, rp, ga, fl,
-                                                        h_img, h_mask, None if rects is not None else rois.ctypes.data_as(C.POINTER(C.c_int))))
+            gain_maps, gain_flags = (C.c_void_p * n)(*[g[0]._h for g in gm]), (C.c_int * n)(*[g[1] for g in gm])
             compensator = None
-        elif rects is not None:
-            rois = np.ascontiguousarray(np.asarray(rects, np.int32).reshape(n, 4))
-            if tables is not None:
-                _lib.check(ctx._lib.stx_warp_batch_rects_kept(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src,
-                                                              rois.ctypes.data_as(C.POINTER(C.c_int)), h_img, h_mask, tables._ref(ctx)))
-            else:
-                _lib.check(ctx._lib.stx_warp_batch_rects(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src,
-                                                         rois.ctypes.data_as(C.POINTER(C.c_int)), h_img, h_mask))
-        else:
-            _lib.check(ctx._lib.stx_warp_batch(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src,
-                                               h_img, h_mask, rois.ctypes.data_as(C.POINTER(C.c_int))))
+        flags = _lib.WARP_FRESH_ROIS if with_rois and rects is None else 0
+        _lib.check(ctx._lib.stx_warp_batch(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src, rects_p, gain_maps,
+                                           gain_flags, flags, h_img, h_mask, rois.ctypes.data_as(ip),
+                                           None if tables is None else tables._ref(ctx)))
         d_imgs = [DeviceImage(ctx, C.c_void_p(h_img[i])) for i in range(n)]
         if compensator is not None:  # "gain" / "channel" (one launch per image) or "no": after the warp
             prev = config.device_resident()

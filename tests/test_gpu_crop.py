@@ -82,7 +82,7 @@ def test_crop_ignores_masks_without_a_cell(oracle, gpu_ctx):
 
 
 def test_warp_rects_and_seam_resize_rects_equal_the_whole(oracle, gpu_ctx):
-    """stx_warp_batch_rects / stx_seam_mask_resize_batch_sub: a rectangle of the output = that rectangle of the whole output"""
+    """stx_warp_batch with rects_xywh / stx_seam_mask_resize_batch_sub: a rectangle of the output = that rectangle of the whole output"""
     imgs, cams = helpers.small_ring(3, 640, 480, span=80.0)
     S.set_device_resident(True)
     try:

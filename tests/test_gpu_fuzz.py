@@ -93,7 +93,7 @@ def test_random_geometry_bit_exact(oracle, gpu_ctx, seed):
     assert g["pano"].shape == o["pano"].shape, tag
     assert np.array_equal(g["pmask"], o["pmask"]), tag
     assert np.array_equal(g["pano"], o["pano"]), (tag, int(np.count_nonzero(g["pano"] != o["pano"])))
-    # the one-call form (ROI pass polled from pinned memory, warps launched behind it: stx_warp_batch_with_rois) on the same geometry
+    # the one-call form (ROI pass polled from pinned memory, warps launched behind it: STX_WARP_FRESH_ROIS) on the same geometry
     w = S.Warper(c["wtype"])
     w.set_scale(c["cams"])
     bi, bm, rois = w.warp_images_and_masks(c["imgs"], c["cams"], c["aspect"], with_rois=True)
@@ -191,7 +191,7 @@ def test_random_crop_to_masks_bit_exact(oracle, gpu_ctx, seed):
 
 @pytest.mark.parametrize("seed", list(range(12 + EXTRA)))
 def test_random_gains_in_the_warp_epilogue_bit_exact(oracle, gpu_ctx, seed):
-    """stx_warp_batch_gain on geometries nobody hand-picked: random sizes (odd ones included: edge tiles of the epilogue), cameras from
+    """stx_warp_batch with gain_maps on geometries nobody hand-picked: random sizes (odd ones included: edge tiles of the epilogue), cameras from
     level to steeply pitched, random block-gain maps of random block sizes, whole ROIs and random rectangles of them, both remap models —
     always the oracle's warp followed by the oracle's block_gain_apply."""
     rng = np.random.default_rng(7000 + seed)

@@ -45,7 +45,7 @@ def test_warp_image_and_mask_bit_exact(oracle, gpu_ctx, wtype):
 
 @pytest.mark.parametrize("wtype", ["spherical", "cylindrical", "plane", "fisheye"])
 def test_roi_pass_and_warps_in_one_call(oracle, gpu_ctx, wtype):
-    """stx_warp_batch_with_rois (the ROI pass polled from pinned memory, the warps launched behind it) == the oracle's rois, images,
+    """stx_warp_batch with STX_WARP_FRESH_ROIS (the ROI pass polled from pinned memory, the warps launched behind it) == the oracle's rois, images,
     masks — twice, the second time with every ROI already in the cache of earlier calls (the pass must run again and agree)."""
     imgs, cams = helpers.small_ring(5, 431, 297, span=130.0 if wtype not in ("plane", "fisheye") else 50.0)
     g, o = S.Warper(wtype), oracle.Warper(wtype)

@@ -1,5 +1,5 @@
 """The column / row tables of the typed projectors kept per rig (stx_warp.hip: launch_typed with a stx_warp_tables handle;
-stx_warp_batch_rects_kept / stx_warp_batch_gain_kept / stx_warp_batch_with_rois_kept).  The tables follow from the cameras, the
+the `tables` argument of stx_warp_batch).  The tables follow from the cameras, the
 rectangles, the scale and the trig mode: a call whose record equals the handle's launches no table kernel and reads the kept block, any
 difference makes the tables again.  Every comparison is byte for byte with a call that takes no handle.
 include/stitching_amd_debug.h: stx_debug_warp_table_launches tells how many table kernels the last batched warp launched.

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """CPU only, plan geometry + the measured per-rank times of round 4: what would BASELINE config 3 (32 frames 4000x3000 on 8 GPUs) cost
 WITHOUT any xGMI traffic — every rank also stages the neighbour frames that reach its band (each GPU has its own PCIe link) and warps
-the sub-rectangles it needs itself (stx_warp_batch_rects), instead of receiving them as warped strips?  (VERDICT r4 item 6 ii.)
+the sub-rectangles it needs itself (stx_warp_batch with rects_xywh), instead of receiving them as warped strips?  (VERDICT r4 item 6 ii.)
 
 Today a strip costs its sender a pack pass, the busiest link 77.8 MB per panorama, and its receiver an unpack pass; the blend work of
 the receiver is the same either way (a strip is fed like an image of its own).  The zero-xGMI form trades the link for a redundant warp:

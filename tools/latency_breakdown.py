@@ -61,7 +61,7 @@ def main():
     for title, head, names in (
             ("ROI pass, then Python, then the warps (stx_warp_rois + stx_warp_batch)", separate,
              ["roi pass (launch + wait)", "Blender() + prepare", "warp call"]),
-            ("ROI pass and warps in one native call (stx_warp_batch_with_rois: what StitchJob.run does)", joined,
+            ("ROI pass and warps in one native call (stx_warp_batch with STX_WARP_FRESH_ROIS: what StitchJob.run does)", joined,
              ["roi pass + warp call", "Blender() + prepare"])):
         names = names + ["8 x feed", "blend call", "wait for the device"]
         acc = [[] for _ in names]

@@ -579,6 +579,41 @@ typedef struct { const void* plane[3]; long long pitch[3]; int w, h, channels, e
 int stx_ingest(stx_ctx* ctx, int n, const stx_foreign_frame* frames, int matrix, int range, void* producer_stream, int has_stream,
                stx_buf** out);
 
+/* ---- device frame emit: images of the library's own -> NV12 / I420 / RGBA ... in the caller's surfaces ------
+ * The mirror of stx_ingest, and like it without a counterpart in the reference.  tests/numpy_emit.py is the contract, byte for byte.
+ *
+ * An item is a source image `src` (a crop view included), a format (the STX_INGEST_* codes) and, optionally, an alpha image and a
+ * target.  STX_INGEST_RAW copies any image layout; the others take u8: BGR / GRAY copy (u8x3 / u8x1), RGB reverses the channels,
+ * BGRA / RGBA add a fourth byte — 255, or the byte of `alpha`, a u8x1 image of the source's size (the panorama mask) —, NV12
+ * (plane[0] = Y: h x w, plane[1] = interleaved U, V: ceil(h/2) rows of ceil(w/2) pairs) and I420 (plane[1] = U, plane[2] = V) are made
+ * from u8x3 BGR with the 16-bit-fraction constants of `matrix` / `range`, in int32 with an arithmetic shift:
+ *   Y = clip8(((kyb B + kyg G + kyr R + 32768) >> 16) + yoff) per pixel,
+ *   U = clip8(((kub SB + kug SG + kur SR + 131072) >> 18) + 128) per 2 x 2 block from the block's channel sums (coordinates clamped to
+ *   the image: an odd last column or row is replicated), V likewise.
+ *
+ * has_target != 0: plane[] / pitch[] (bytes) name the caller's memory, written in place, and the item's three slots of `out` stay null.
+ * has_target == 0: the planes are allocated and returned in out[3 i ..]: one image for the packed formats, Y (u8x1) and UV (u8x2) for
+ * NV12, Y, U, V (u8x1) for I420; unused slots are null.  `out` holds 3 n slots.
+ *
+ * One call takes n items of unequal sizes and formats and makes ONE launch.  Everything is checked before anything is allocated or
+ * launched (STX_ERR_INVALID with a message that names item and plane; the context stays usable): the source's layout agrees with the
+ * format; alpha is u8x1 of the source's size and only given with BGRA / RGBA; 1 <= w, h <= STX_INGEST_MAX_SIDE; every target plane is
+ * device memory of the context's device (host, pinned host, managed and other-device memory are refused) and lies, first byte to last,
+ * inside one allocation; row bytes <= pitch <= 2^40; no target plane's byte range overlaps another target plane of the call, or any
+ * source or alpha image of the call.  No byte outside the rows of a target plane is written.
+ * has_stream != 0: the launch is ordered after everything queued on consumer_stream so far (the consumer may still be reading the
+ * surface) and consumer_stream is ordered after the launch, both by events, without a host wait; 1 as a handle means the legacy
+ * default stream, 2 the per-thread default stream.  0: the caller vouches that the targets are free, and syncs the context
+ * (stx_ctx_sync) before it reads them. */
+typedef struct {
+    const stx_buf* src;
+    const stx_buf* alpha; /* or null */
+    int format, has_target;
+    void* plane[3];
+    long long pitch[3];
+} stx_emit_item;
+int stx_emit(stx_ctx* ctx, int n, const stx_emit_item* items, int matrix, int range, void* consumer_stream, int has_stream, stx_buf** out);
+
 /* ---- sharded multi-band blending: one process per GPU, one stx_blender per rank ------------------
  * No counterpart in the reference (it is single process, stitching/stitcher.py:247-254).  Every rank
  * prepares the same roi; rank g produces the columns [x0, x1) of the panorama (stx_blend_set_band).

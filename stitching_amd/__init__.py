@@ -20,6 +20,7 @@ from .feature_estimation import FeatureEstimator, ImageFeatures
 from .feature_matcher import FeatureMatcher
 from .match_estimation import MatchEstimator, MatchesInfo
 from .images import Images, MegapixDownscaler, MegapixScaler
+from .emit import emit, emit_all
 from .ingest import ingest, ingest_all, parse_cuda_array_interface
 from .pipeline import AffineComposer, ComposePlan, Composer
 from .seam_estimation import ColorSeamEstimator, SeamEstimator
@@ -32,7 +33,7 @@ from .warper import Warper
 __all__ = [
     "AffineComposer", "Blender", "CameraAdjuster", "CameraEstimator", "CameraParams", "CameraSolver", "ColorSeamEstimator", "ComposePlan", "Composer", "Context", "Cropper", "Rectangle", "DeviceImage", "ExposureErrorCompensator", "ExposureEstimator", "FeatureDetector", "FeatureEstimator", "FeatureMatcher", "ImageFeatures", "Images", "MatchEstimator", "MatchesInfo", "MegapixDownscaler", "MegapixScaler", "StitchingError", "StitchingWarning",
     "SeamEstimator", "SeamFinder", "Subsetter", "Timelapser", "Warper", "WaveCorrector", "resize_linear_exact", "resize_linear_exact_all",
-    "as_device", "ingest", "ingest_all", "parse_cuda_array_interface", "device_count", "pinned_empty", "device_resident", "get_context", "set_default_device", "set_device_resident", "set_trig_mode", "trig_mode", "set_remap_mode", "remap_mode", "set_pyrdown_mode", "pyrdown_mode",
+    "as_device", "emit", "emit_all", "ingest", "ingest_all", "parse_cuda_array_interface", "device_count", "pinned_empty", "device_resident", "get_context", "set_default_device", "set_device_resident", "set_trig_mode", "trig_mode", "set_remap_mode", "remap_mode", "set_pyrdown_mode", "pyrdown_mode",
     "set_exposure_estimator", "exposure_estimator", "set_exposure_solver", "exposure_solver", "set_seam_estimator", "seam_estimator",
 ]
 __version__ = "0.1.0"

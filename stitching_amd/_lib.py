@@ -62,6 +62,12 @@ class ForeignFrame(C.Structure):
                 ("elem", C.c_int), ("format", C.c_int)]
 
 
+class EmitItem(C.Structure):
+    """stx_emit_item: a source image, an optional alpha image, a format and an optional target of up to three planes."""
+    _fields_ = [("src", C.c_void_p), ("alpha", C.c_void_p), ("format", C.c_int), ("has_target", C.c_int), ("plane", C.c_void_p * 3),
+                ("pitch", C.c_longlong * 3)]
+
+
 WARP_FRESH_ROIS = 1
 
 _i, _f, _d, _u, _z = C.c_int, C.c_float, C.c_double, C.c_uint, C.c_size_t
@@ -167,6 +173,7 @@ PROTOTYPES = {
     "stx_reproj_problem_eval": [_vp, _i, _dp, _dp, _dp],
     "stx_ray_problem_free": [_vp],
     "stx_ingest": [_vp, _i, C.POINTER(ForeignFrame), _i, _i, _vp, _i, _vpp],
+    "stx_emit": [_vp, _i, C.POINTER(EmitItem), _i, _i, _vp, _i, _vpp],
     # include/stitching_amd_debug.h: test hooks, never called by the package's classes
     "stx_debug_warp_maps": [_vp, _i, _f, _fp, _fp, _i, _i, _i, _ip, _vpp, _vpp, _ip],
     "stx_debug_feather_dist_cap": [],

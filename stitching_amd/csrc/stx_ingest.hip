@@ -11,6 +11,7 @@
 // reaches past a plane's last byte, which is all the host has checked against the allocation.  The destination is an image of the
 // library's own (base and pitch multiples of 64): a full lane stores words, a tail lane the bytes of its pixels.
 #include "stx_internal.h"
+#include "stx_lane_io.h"
 
 namespace {
 // clip8(s >> 8) of the contract, clamped BEFORE the shift: min(max(s, 0), 65535) >> 8 is the same value for every int s (s < 0 -> 0,
@@ -18,48 +19,6 @@ namespace {
 // v_ashr_pk_u8_i32 for pairs of these bytes, and the MI355X then returned a wrong byte beside one that saturates (R = 255 for 198 next
 // to a clipped B; the same source run as host C++ is right): keep this form, and look for that instruction in the ISA after a change.
 __device__ __forceinline__ uint32_t shift_clip8(int s) { return (uint32_t)min(max(s, 0), 65535) >> 8; }
-
-// NW words from p: as words (p is 4-aligned and all 4 NW bytes belong to the lane), else the first nbytes, byte by byte (rest 0)
-template <int NW>
-__device__ __forceinline__ void load_words(const uint8_t* __restrict__ p, int nbytes, bool words, uint32_t (&s)[NW])
-{
-    if (words) {
-#pragma unroll
-        for (int i = 0; i < NW; i++) s[i] = ((const uint32_t*)p)[i];
-    } else {
-#pragma unroll
-        for (int i = 0; i < NW; i++) s[i] = 0u;
-#pragma unroll
-        for (int j = 0; j < NW * 4; j++)
-            if (j < nbytes) s[j >> 2] |= (uint32_t)p[j] << ((j & 3) * 8);
-    }
-}
-
-// two bytes at p (I420's chroma of four pixels): one 16-bit load where p is 2-aligned and both belong to the lane
-__device__ __forceinline__ uint32_t load_pair(const uint8_t* __restrict__ p, int nbytes, bool halves)
-{
-    if (halves) return *(const uint16_t*)p;
-    uint32_t v = p[0];
-    if (nbytes > 1) v |= (uint32_t)p[1] << 8;
-    return v;
-}
-
-template <int NW>
-__device__ __forceinline__ uint32_t byte_of(const uint32_t (&s)[NW], int j) { return (s[j >> 2] >> ((j & 3) * 8)) & 255u; }
-
-// NW words to d (4-aligned): all of them, or the first nbytes byte by byte
-template <int NW>
-__device__ __forceinline__ void store_words(uint8_t* __restrict__ d, const uint32_t (&o)[NW], int nbytes)
-{
-    if (nbytes == NW * 4) {
-#pragma unroll
-        for (int i = 0; i < NW; i++) ((uint32_t*)d)[i] = o[i];
-    } else {
-#pragma unroll
-        for (int j = 0; j < NW * 4; j++)
-            if (j < nbytes) d[j] = (uint8_t)byte_of(o, j);
-    }
-}
 
 // a row of bytes, 16 per lane
 __device__ __forceinline__ void copy_lane(const StxIngestItem& D, int xu, int y)

@@ -10,44 +10,47 @@ constexpr StxIngestCoef kCoef[2][2] = {{{16, 298, 409, 100, 208, 516}, {0, 256, 
                                        {{16, 298, 459, 55, 136, 541}, {0, 256, 403, 48, 120, 475}}};
 constexpr long long kMaxPitch = 1ll << 40;  // rows * pitch stays far inside 64 bits
 
-struct Plane { const uint8_t* p; long long pitch, row_bytes; int rows; };
+using Plane = StxForeignPlane;
 
-// the plane is device memory of the context's device and lies, first byte to last, inside one allocation
-int check_plane(const stx_ctx* ctx, int frame, int plane, const Plane& P)
+bool aligned(const Plane& P, int a) { return ((uintptr_t)P.p % (uintptr_t)a) == 0 && P.pitch % a == 0; }
+}  // namespace
+
+int stx_check_foreign_plane(const stx_ctx* ctx, const char* what, const char* item, int index, int plane, const StxForeignPlane& P,
+                            const char* host_hint)
 {
-    if (!P.p) return stx_fail(STX_ERR_INVALID, "ingest: frame %d plane %d is null", frame, plane);
+    if (!P.p) return stx_fail(STX_ERR_INVALID, "%s: %s %d plane %d is null", what, item, index, plane);
     if (P.pitch < P.row_bytes || P.pitch > kMaxPitch)
-        return stx_fail(STX_ERR_INVALID, "ingest: frame %d plane %d has a pitch of %lld bytes for rows of %lld", frame, plane, P.pitch, P.row_bytes);
+        return stx_fail(STX_ERR_INVALID, "%s: %s %d plane %d has a pitch of %lld bytes for rows of %lld", what, item, index, plane, P.pitch,
+                        P.row_bytes);
     hipPointerAttribute_t a;
     memset(&a, 0, sizeof(a));
     hipError_t e = hipPointerGetAttributes(&a, P.p);
     if (e != hipSuccess) (void)hipGetLastError();  // an unknown pointer is an answer, not a sticky error
     if (e != hipSuccess || a.type == hipMemoryTypeUnregistered || a.type == hipMemoryTypeHost)
-        return stx_fail(STX_ERR_INVALID, "ingest: frame %d plane %d (%p) is host memory: host arrays are uploaded with from_numpy", frame, plane,
-                        (const void*)P.p);
+        return stx_fail(STX_ERR_INVALID, "%s: %s %d plane %d (%p) is host memory: %s", what, item, index, plane, (const void*)P.p, host_hint);
     if (a.isManaged || a.type == hipMemoryTypeManaged)
-        return stx_fail(STX_ERR_INVALID, "ingest: frame %d plane %d (%p) is managed memory, which is not taken", frame, plane, (const void*)P.p);
+        return stx_fail(STX_ERR_INVALID, "%s: %s %d plane %d (%p) is managed memory, which is not taken", what, item, index, plane,
+                        (const void*)P.p);
     if (a.type != hipMemoryTypeDevice)
-        return stx_fail(STX_ERR_INVALID, "ingest: frame %d plane %d (%p) is not linear device memory", frame, plane, (const void*)P.p);
+        return stx_fail(STX_ERR_INVALID, "%s: %s %d plane %d (%p) is not linear device memory", what, item, index, plane, (const void*)P.p);
     if (a.device != ctx->device)
-        return stx_fail(STX_ERR_INVALID, "ingest: frame %d plane %d lives on device %d, the context on device %d", frame, plane, a.device, ctx->device);
+        return stx_fail(STX_ERR_INVALID, "%s: %s %d plane %d lives on device %d, the context on device %d", what, item, index, plane, a.device,
+                        ctx->device);
     hipDeviceptr_t base = nullptr;
     size_t size = 0;
     e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)P.p);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return stx_fail(STX_ERR_INVALID, "ingest: frame %d plane %d (%p) belongs to no allocation the runtime knows", frame, plane, (const void*)P.p);
+        return stx_fail(STX_ERR_INVALID, "%s: %s %d plane %d (%p) belongs to no allocation the runtime knows", what, item, index, plane,
+                        (const void*)P.p);
     }
     const unsigned long long first = (unsigned long long)(uintptr_t)P.p, end = (unsigned long long)(uintptr_t)base + size;
     const unsigned long long bytes = (unsigned long long)(P.rows - 1) * (unsigned long long)P.pitch + (unsigned long long)P.row_bytes;
     if (first < (unsigned long long)(uintptr_t)base || first >= end || bytes > end - first)
-        return stx_fail(STX_ERR_INVALID, "ingest: frame %d plane %d claims %llu bytes, its allocation holds %llu from there", frame, plane, bytes,
-                        first < end ? end - first : 0ull);
+        return stx_fail(STX_ERR_INVALID, "%s: %s %d plane %d claims %llu bytes, its allocation holds %llu from there", what, item, index, plane,
+                        bytes, first < end ? end - first : 0ull);
     return STX_OK;
 }
-
-bool aligned(const Plane& P, int a) { return ((uintptr_t)P.p % (uintptr_t)a) == 0 && P.pitch % a == 0; }
-}  // namespace
 
 STX_EXPORT int stx_ingest(stx_ctx* ctx, int n, const stx_foreign_frame* frames, int matrix, int range, void* producer_stream, int has_stream,
                           stx_buf** out)
@@ -84,7 +87,7 @@ STX_EXPORT int stx_ingest(stx_ctx* ctx, int n, const stx_foreign_frame* frames, 
             P[2] = Plane{(const uint8_t*)F.plane[2], F.pitch[2], cw, ch};
             np = 3;
         }
-        for (int p = 0; p < np; p++) STX_TRY(check_plane(ctx, i, p, P[p]));
+        for (int p = 0; p < np; p++) STX_TRY(stx_check_foreign_plane(ctx, "ingest", "frame", i, p, P[p], "host arrays are uploaded with from_numpy"));
         StxIngestItem& K = items[i];
         K = StxIngestItem{};
         for (int p = 0; p < np; p++) { K.p[p] = P[p].p; K.pitch[p] = P[p].pitch; }

@@ -418,6 +418,31 @@ struct StxIngestItem {
 };
 struct StxIngestCoef { int yoff, yk, rv, gu, gv, bu; };
 int stx_launch_ingest(stx_ctx* ctx, const StxIngestItem* d_items, int n, int total_tiles, const StxIngestCoef& coef, double algo_bytes);
+// one plane of foreign memory: `rows` rows of `row_bytes` bytes, `pitch` bytes apart
+struct StxForeignPlane { const uint8_t* p; long long pitch, row_bytes; int rows; };
+// the plane is device memory of the context's device and lies, first byte to last, inside one allocation; row_bytes <= pitch <= 2^40.
+// what / item name the caller in the message ("ingest" / "frame"), host_hint ends the message about host memory
+int stx_check_foreign_plane(const stx_ctx* ctx, const char* what, const char* item, int index, int plane, const StxForeignPlane& P,
+                            const char* host_hint);
+// device frame emit (stx_emit.hip; host side in stx_emit_host.cpp): the mirror of ingest, with its lane and tile geometry
+// (STX_INGEST_LANE_PX pixels of a row unit per lane — COPY: as many 4-byte words —, 64 lanes x STX_INGEST_ROWS row units per workgroup,
+// a row unit is two rows of the 4:2:0 formats) and the flat tile list.
+// kind: what the kernel does with a row unit
+enum { STX_EMIT_K_COPY = 0, STX_EMIT_K_REV3, STX_EMIT_K_ALPHA, STX_EMIT_K_NV12, STX_EMIT_K_I420 };
+// wide: which buffers are moved in whole words (base and pitch multiples of 4; 2 for the chroma planes of I420, stored 2 bytes at a
+// time), decided per item on the host so that the branch is uniform over a workgroup; a clear bit moves bytes.
+enum { STX_EMIT_WIDE_SRC = 1, STX_EMIT_WIDE_ALPHA = 2, STX_EMIT_WIDE_DST0 = 4 };  // plane p of the target: STX_EMIT_WIDE_DST0 << p
+struct StxEmitItem {
+    const uint8_t* src; long long sstride;
+    const uint8_t* alpha; long long astride;  // ALPHA: null = the alpha byte is 255
+    uint8_t* dst[3]; long long dpitch[3];
+    int w, h;       // pixels; COPY: bytes of a row
+    int kind, wide, reverse;  // reverse: ALPHA swaps the first and third channel
+    int tiles_x, tile0, pad_;
+};
+// the 16-bit-fraction constants of tests/numpy_emit.py in (B, G, R) order; yoff: 16 or 0
+struct StxEmitCoef { int ky[3], ku[3], kv[3], yoff; };
+int stx_launch_emit(stx_ctx* ctx, const StxEmitItem* d_items, int n, int total_tiles, const StxEmitCoef& coef, double algo_bytes);
 
 int stx_launch_seam_resize_batch(stx_ctx* ctx, int n, const stx_buf* const* seams, const stx_buf* const* masks, stx_buf* const* dsts,
                                  const int* const* d_xt, const int* const* d_yt, uint8_t* const* tmp, const size_t* tstride);

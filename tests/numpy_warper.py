@@ -169,11 +169,19 @@ def _sat16(a):
     return np.clip(a, -32768, 32767)
 
 
+def _cv_round(v):
+    """cvRound(float) as x86 compiles it (cvtss2si): round half to even; NaN and anything outside int32 give INT_MIN"""
+    v = np.asarray(v, np.float32).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        ok = (v >= -2147483648.0) & (v < 2147483648.0)
+        return np.where(ok, np.rint(np.where(ok, v, 0.0)), -2147483648.0).astype(np.int64)
+
+
 def remap_linear_reflect(src, xmap, ymap):
     """cv::remap(INTER_LINEAR, BORDER_REFLECT) on u8: 1/32-px positions (round half even), Q15 weights, + 16384 >> 15"""
     H, W = src.shape[:2]
-    sx = np.rint((xmap * F(32)).astype(np.float64)).astype(np.int64)
-    sy = np.rint((ymap * F(32)).astype(np.float64)).astype(np.int64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        sx, sy = _cv_round(xmap * F(32)), _cv_round(ymap * F(32))
     ix, iy = _sat16(sx >> 5), _sat16(sy >> 5)
     fx, fy = sx & 31, sy & 31
     x0, x1, y0, y1 = _reflect(ix, W), _reflect(ix + 1, W), _reflect(iy, H), _reflect(iy + 1, H)
@@ -186,8 +194,7 @@ def remap_linear_reflect(src, xmap, ymap):
 
 def remap_nearest_constant(src, xmap, ymap):
     H, W = src.shape[:2]
-    ix = _sat16(np.rint(xmap.astype(np.float64)).astype(np.int64))
-    iy = _sat16(np.rint(ymap.astype(np.float64)).astype(np.int64))
+    ix, iy = _sat16(_cv_round(xmap)), _sat16(_cv_round(ymap))
     inside = (ix >= 0) & (ix < W) & (iy >= 0) & (iy < H)
     out = np.zeros(xmap.shape + src.shape[2:], np.uint8)
     out[inside] = src[iy[inside], ix[inside]]

@@ -614,6 +614,36 @@ typedef struct {
 } stx_emit_item;
 int stx_emit(stx_ctx* ctx, int n, const stx_emit_item* items, int matrix, int range, void* consumer_stream, int has_stream, stx_buf** out);
 
+/* ---- lens rectification: distorted frames -> pinhole frames -------------------------------------------------
+ * No counterpart in the reference (it assumes pinhole cameras; a caller of it runs cv2.remap on the host).  tests/numpy_rectify.py is
+ * the contract, byte for byte; the device half of it is integer only.
+ *
+ * A lens map belongs to one camera: for a destination image dst_w x dst_h it holds, every STX_LENS_CELL destination pixels, the source
+ * coordinate (sx, sy) of that pixel in Q6 (int32, |value| <= 2^21) — nx = (dst_w + 15) / 16 + 1 nodes per row, ny = (dst_h + 15) / 16 + 1
+ * rows, node (i, j) at destination pixel (16 i, 16 j), the nodes past the right and bottom edge included; nodes_xy_q6 is ny x nx x 2.
+ * stx_lens_map_create copies the nodes to device memory once and returns when the caller's array is free again.
+ *
+ * Destination pixel (x, y), ax = x & 15, ay = y & 15, nodes N00 N10 / N01 N11 of its cell, per coordinate, in int32:
+ *   S = (16 - ay) ((16 - ax) N00 + ax N10) + ay ((16 - ax) N01 + ax N11);  q = (S + 256) >> 9 (arithmetic: Q5, floor);  i = q >> 5, f = q & 31
+ *   out = (w00 p00 + w10 p10 + w01 p01 + w11 p11 + 512) >> 10 per channel, w00 = (32 - fx)(32 - fy), w10 = fx (32 - fy), ...
+ * over the taps (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1).  A tap outside the source reads 0 (STX_RECTIFY_CONSTANT) or has
+ * its indices clamped (STX_RECTIFY_REPLICATE).  The mask is 255 where all four taps lie inside the source, else 0.
+ *
+ * stx_rectify takes n sources (u8, 1 or 3 channels, crop views included) of unequal sizes with one map each and makes ONE launch.
+ * out_imgs[i] is a new dst_w x dst_h image with the source's channels; with want_masks != 0 out_masks[i] is a new u8x1 mask (flagged as
+ * holding only 0 and 255), else out_masks may be null.  Everything is checked before anything is allocated or launched
+ * (STX_ERR_INVALID, the context stays usable): null handles, element type and channels, source size against the map's, sides in
+ * 1 .. STX_RECTIFY_MAX_SIDE, the node counts against (dst_w, dst_h), node values within +- 2^21, a map of another context, a source that spans 2^31 bytes or has a pitch of 2^24 (a view of a very wide parent). */
+#define STX_LENS_CELL 16
+#define STX_RECTIFY_CONSTANT 0
+#define STX_RECTIFY_REPLICATE 1
+#define STX_RECTIFY_MAX_SIDE 16384
+typedef struct stx_lens_map stx_lens_map;
+int stx_lens_map_create(stx_ctx* ctx, int dst_w, int dst_h, int src_w, int src_h, int nx, int ny, const int* nodes_xy_q6, stx_lens_map** out);
+int stx_lens_map_free(stx_lens_map* map);
+int stx_rectify(stx_ctx* ctx, int n, const stx_buf* const* srcs, const stx_lens_map* const* maps, int border, int want_masks,
+                stx_buf** out_imgs, stx_buf** out_masks);
+
 /* ---- sharded multi-band blending: one process per GPU, one stx_blender per rank ------------------
  * No counterpart in the reference (it is single process, stitching/stitcher.py:247-254).  Every rank
  * prepares the same roi; rank g produces the columns [x0, x1) of the panorama (stx_blend_set_band).

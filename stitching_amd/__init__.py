@@ -23,6 +23,7 @@ from .images import Images, MegapixDownscaler, MegapixScaler
 from .emit import emit, emit_all
 from .ingest import ingest, ingest_all, parse_cuda_array_interface
 from .pipeline import AffineComposer, ComposePlan, Composer
+from .rectify import LensMap, rectify, rectify_all
 from .seam_estimation import ColorSeamEstimator, SeamEstimator
 from .seam_finder import SeamFinder, resize_linear_exact, resize_linear_exact_all
 from .stitching_error import StitchingError, StitchingWarning
@@ -33,6 +34,7 @@ from .warper import Warper
 __all__ = [
     "AffineComposer", "Blender", "CameraAdjuster", "CameraEstimator", "CameraParams", "CameraSolver", "ColorSeamEstimator", "ComposePlan", "Composer", "Context", "Cropper", "Rectangle", "DeviceImage", "ExposureErrorCompensator", "ExposureEstimator", "FeatureDetector", "FeatureEstimator", "FeatureMatcher", "ImageFeatures", "Images", "MatchEstimator", "MatchesInfo", "MegapixDownscaler", "MegapixScaler", "StitchingError", "StitchingWarning",
     "SeamEstimator", "SeamFinder", "Subsetter", "Timelapser", "Warper", "WaveCorrector", "resize_linear_exact", "resize_linear_exact_all",
+    "LensMap", "rectify", "rectify_all",
     "as_device", "emit", "emit_all", "ingest", "ingest_all", "parse_cuda_array_interface", "device_count", "pinned_empty", "device_resident", "get_context", "set_default_device", "set_device_resident", "set_trig_mode", "trig_mode", "set_remap_mode", "remap_mode", "set_pyrdown_mode", "pyrdown_mode",
     "set_exposure_estimator", "exposure_estimator", "set_exposure_solver", "exposure_solver", "set_seam_estimator", "seam_estimator",
 ]

@@ -54,6 +54,10 @@ INGEST_FORMATS = {None: 0, "bgr": 1, "rgb": 2, "bgra": 3, "rgba": 4, "gray": 5, 
 INGEST_MATRICES = {"bt601": 0, "bt709": 1}
 INGEST_RANGES = {"limited": 0, "full": 1}
 INGEST_MAX_SIDE = 32768
+# STX_LENS_CELL, STX_RECTIFY_*: the spacing of a lens map's nodes, the borders of stx_rectify and the largest side of a frame
+LENS_CELL = 16
+RECTIFY_BORDERS = {"constant": 0, "replicate": 1}
+RECTIFY_MAX_SIDE = 16384
 
 
 class ForeignFrame(C.Structure):
@@ -174,6 +178,9 @@ PROTOTYPES = {
     "stx_ray_problem_free": [_vp],
     "stx_ingest": [_vp, _i, C.POINTER(ForeignFrame), _i, _i, _vp, _i, _vpp],
     "stx_emit": [_vp, _i, C.POINTER(EmitItem), _i, _i, _vp, _i, _vpp],
+    "stx_lens_map_create": [_vp, _i, _i, _i, _i, _i, _i, _ip, _vpp],
+    "stx_lens_map_free": [_vp],
+    "stx_rectify": [_vp, _i, _vpp, _vpp, _i, _i, _vpp, _vpp],
     # include/stitching_amd_debug.h: test hooks, never called by the package's classes
     "stx_debug_warp_maps": [_vp, _i, _f, _fp, _fp, _i, _i, _i, _ip, _vpp, _vpp, _ip],
     "stx_debug_feather_dist_cap": [],

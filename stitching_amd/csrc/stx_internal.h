@@ -443,6 +443,26 @@ struct StxEmitItem {
 // the 16-bit-fraction constants of tests/numpy_emit.py in (B, G, R) order; yoff: 16 or 0
 struct StxEmitCoef { int ky[3], ku[3], kv[3], yoff; };
 int stx_launch_emit(stx_ctx* ctx, const StxEmitItem* d_items, int n, int total_tiles, const StxEmitCoef& coef, double algo_bytes);
+// lens rectification (stx_rectify.hip; host side in stx_rectify_host.cpp) -------------------------------------
+// A wavefront owns one cell of the lens grid (STX_LENS_CELL x STX_LENS_CELL destination pixels: its four nodes are wave-uniform), a
+// lane STX_RECTIFY_LANE_PX pixels of one row of it; a workgroup is STX_RECTIFY_TW / STX_LENS_CELL cells side by side.  The grid is the
+// flat list of the images' tiles (tile0 ascending, first 0).
+constexpr int STX_RECTIFY_LANE_PX = 4, STX_RECTIFY_TW = 64, STX_RECTIFY_TH = 16;
+static_assert(STX_LENS_CELL * STX_LENS_CELL == 64 * STX_RECTIFY_LANE_PX && STX_RECTIFY_TH == STX_LENS_CELL, "a wavefront is one cell");
+// the nodes of one camera in device memory: (sx, sy) in Q6 per node, ny rows of nx
+struct stx_lens_map {
+    stx_ctx* ctx = nullptr;
+    int dst_w = 0, dst_h = 0, src_w = 0, src_h = 0, nx = 0, ny = 0;
+    StxDevBlock d_nodes;
+};
+struct StxRectifyItem {
+    const uint8_t* src; long long sstride;
+    uint8_t* dst; long long dstride;
+    uint8_t* mask; long long mstride;  // null: no mask wanted
+    const int2* nodes;
+    int nx, sw, sh, dw, dh, c, tiles_x, tile0;
+};
+int stx_launch_rectify(stx_ctx* ctx, const StxRectifyItem* d_items, int n, int total_tiles, int border, double algo_bytes);
 
 int stx_launch_seam_resize_batch(stx_ctx* ctx, int n, const stx_buf* const* seams, const stx_buf* const* masks, stx_buf* const* dsts,
                                  const int* const* d_xt, const int* const* d_yt, uint8_t* const* tmp, const size_t* tstride);

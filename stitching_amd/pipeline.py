@@ -18,6 +18,7 @@ from .cropper import Cropper
 from .device import as_device, get_context, is_foreign_device_array
 from .exposure_error_compensator import ExposureErrorCompensator
 from .images import Images
+from .rectify import lens_list, rectify_all
 from .seam_estimation import SeamEstimator
 from .seam_finder import DEVICE_SEAM_FINDERS, SeamFinder
 from .stitching_error import StitchingError, StitchingWarning
@@ -461,7 +462,17 @@ class ComposePlan:
         self.camera_aspect = images.get_ratio(R.MEDIUM, R.FINAL)
         self.lir_aspect = images.get_ratio(R.LOW, R.FINAL)
 
-    def check_frames(self, frames):
+    def check_frames(self, frames, lenses=None):
+        """frames: what the final-resolution half is given.  With lenses (one LensMap per frame) they are distorted frames: each must
+        have its lens's source size, and each lens must rectify to the size the plan was prepared for."""
+        if lenses is not None:
+            got = [Images.get_image_size(f) for f in frames]
+            if got != [lens.src_size for lens in lenses]:
+                raise StitchingError(f"the lenses were made for frames of sizes {[lens.src_size for lens in lenses]}, got {got}")
+            if [lens.dst_size for lens in lenses] != [tuple(z) for z in self.frame_sizes]:
+                raise StitchingError(f"the plan was prepared for frames of sizes {self.frame_sizes}, the lenses rectify to "
+                                     f"{[lens.dst_size for lens in lenses]}: same rig, same sizes")
+            return
         got = [Images.get_image_size(f) for f in frames]
         if got != [tuple(z) for z in self.frame_sizes]:
             raise StitchingError(f"the plan was prepared for frames of sizes {self.frame_sizes}, got {got}: same rig, same sizes")
@@ -519,14 +530,19 @@ class Composer:
     def _ctx(self):
         return self.ctx or get_context()
 
-    def prepare(self, images, cameras):
+    def prepare(self, images, cameras, lenses=None):
         """The low-resolution half -> ComposePlan.  The host waits for the device where a result decides what is launched next: the ROI
         pass of the warp, the cropper's rectangle, the gain solve (and the read-back of the seam masks for the multi-band blender's
-        seam-cell crops)."""
-        st, ctx = self.settings, self._ctx()
+        seam-cell crops).  lenses: one LensMap per image, or one for all — the images are then distorted frames and are rectified
+        first (stitching_amd.rectify); the plan is prepared from, and keeps, the rectified frames."""
         frames, cameras = list(images), list(cameras)
+        if lenses is not None:
+            lenses = lens_list(lenses, len(frames))
+        st, ctx = self.settings, self._ctx()
         if len(frames) != len(cameras):
             raise StitchingError("need one camera per image")
+        if lenses is not None:
+            frames = rectify_all(frames, lenses, ctx=ctx)
         frames = [as_device(f, ctx) for f in frames]  # on THIS context: every later stage follows its images' context
         imgs_obj = Images.of(frames, st["medium_megapix"], st["low_megapix"], st["final_megapix"])
         R = Images.Resolution
@@ -561,9 +577,17 @@ class Composer:
             config.set_device_resident(prev)
         return ComposePlan(imgs_obj, frames, cameras, warper.scale, cropper, compensator, seam_masks, host, corners, sizes)
 
-    def run(self, plan, images=None):
+    def run(self, plan, images=None, lenses=None):
         """The final-resolution half on a plan: `images` None -> the frames the plan was prepared from, else new frames of the same rig
-        (no low-resolution pass).  Returns device-resident (panorama u8x3, mask u8)."""
+        (no low-resolution pass).  lenses: the LensMaps of new, distorted `images`, which are rectified first (the plan's own frames
+        are rectified already).  Returns device-resident (panorama u8x3, mask u8)."""
+        if lenses is not None:
+            if images is None:
+                raise StitchingError("lenses go with new images: the frames the plan was prepared from are rectified already")
+            images = list(images)
+            lenses = lens_list(lenses, len(images))
+            plan.check_frames(images, lenses)
+            images = rectify_all(images, lenses, ctx=self._ctx())
         frames = plan.frames if images is None else list(images)
         plan.check_frames(frames)
         st, ctx = self.settings, self._ctx()
@@ -586,21 +610,27 @@ class Composer:
             return plan.job.run()
         return plan.job.run(frames=final)
 
-    def compose(self, images, cameras):
-        """prepare + run -> the panorama (device-resident u8x3), as Stitcher.stitch returns it"""
-        pano, _ = self.run(self.prepare(images, cameras))
+    def compose(self, images, cameras, lenses=None):
+        """prepare + run -> the panorama (device-resident u8x3), as Stitcher.stitch returns it; lenses: see `prepare`"""
+        pano, _ = self.run(self.prepare(images, cameras, lenses=lenses))
         return pano
 
-    def stitch(self, images, feature_estimator=None, match_estimator=None, camera_solver=None):
+    def stitch(self, images, feature_estimator=None, match_estimator=None, camera_solver=None, lenses=None):
         """Frames in, panorama out (device-resident u8x3), with no cv2 and no cameras supplied: the registration half of Stitcher.stitch
         (stitching/stitcher.py:99-105) by the project's own estimators — resize to MEDIUM on the device, FeatureEstimator.detect,
         MatchEstimator.match, CameraSolver.register — then `compose` on the images registration kept.  The three objects default to
-        their classes' defaults.  `self.registration` keeps the indices of the images kept, their cameras and the solver's info."""
+        their classes' defaults.  `self.registration` keeps the indices of the images kept, their cameras and the solver's info.
+        lenses: one LensMap per image, or one for all: registration and composition then see the rectified frames."""
         from .camera_estimation import CameraSolver
         from .feature_estimation import FeatureEstimator
         from .match_estimation import MatchEstimator
 
+        if lenses is not None:
+            images = list(images)
+            lenses = lens_list(lenses, len(images))
         st, ctx = self.settings, self._ctx()
+        if lenses is not None:
+            images = rectify_all(images, lenses, ctx=ctx)
         frames = [as_device(f, ctx) for f in images]
         if len(frames) < 2:
             raise StitchingError("stitching needs at least two images")

@@ -99,3 +99,76 @@ def run_sharded_job_in_one_process(ctx, frames, cams, world, per_rank, **job_kw)
     pano = np.concatenate([b[0] for b in bands], axis=1)
     mask = np.concatenate([b[1] for b in bands], axis=1)
     return pano, mask, jobs
+
+
+def weight_pyramid_of_export(packed, rect, nb):
+    """the fp32 weight planes W_0 .. W_nb out of a packed contribution strip (csrc/stx_blend_host.cpp mb_contrib_layout: per level three
+    int16 planes, row pitch a multiple of 32 samples, then the weights, pitch a multiple of 16; every section on a 256-byte boundary)"""
+    raw = np.asarray(packed).reshape(-1)
+    w, h = rect[2], rect[3]
+    up = lambda v, a: (v + a - 1) // a * a  # noqa: E731
+    off, out = 0, []
+    for i in range(nb + 1):
+        lw, lh = max(w >> i, 1), max(h >> i, 1)
+        off = up(off + up(lw, 32) * lh * 3 * 2, 256)
+        ws = up(lw, 16)
+        out.append(raw[off:off + ws * lh * 4].view(np.float32).reshape(lh, ws)[:, :lw].copy())
+        off = up(off + ws * lh * 4, 256)
+    return out
+
+
+def many_images_feeds(n):
+    """-> (images, masks, corners): n images of 1100 x 96 stacked over the same panorama pixels with binary masks — checkerboards, flat
+    and random images, ragged left edges, every fifth mask salt and pepper (test_gpu_parity.test_blend_many_images_over_the_same_pixels;
+    classified in tests/test_constructed_multiband.py)"""
+    rng = np.random.default_rng(1000 + n)
+    w, h = 1100, 96
+    yy, xx = np.mgrid[0:h, 0:w]
+    imgs, masks, corners = [], [], []
+    for k in range(n):
+        kind = k % 4
+        if kind == 0:
+            im = np.where(((xx + yy + k) & 1)[..., None] == 1, 255, 0).astype(np.uint8).repeat(3, axis=2)
+        elif kind == 1:
+            im = np.full((h, w, 3), 255 if k % 8 == 1 else 0, np.uint8)
+        else:
+            im = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+        m = np.full((h, w), 255, np.uint8)
+        x0, x1 = int(rng.integers(0, 200)), int(rng.integers(w - 200, w + 1))
+        m[:, :x0] = 0
+        m[:, x1:] = 0
+        ragged = rng.integers(0, 12, h)
+        for y in range(h):  # ragged left edge: the count changes from pixel to pixel within a lane's patch
+            m[y, x0:x0 + int(ragged[y])] = 0
+        if k % 5 == 4:
+            m[rng.integers(0, 2, (h, w)) == 0] = 0  # a salt-and-pepper mask
+        imgs.append(im)
+        masks.append(m)
+        corners.append((int(rng.integers(0, 9)) if k else 0, int(rng.integers(0, 5)) if k else 0))
+    return imgs, masks, corners
+
+
+def sparse_masks(kind, masks, rng):
+    """warped masks thinned to islands at the 512-column tile seams, single dots (image 1: nothing), grey islands, or one-pixel lines
+    along the rectangle's edges (test_gpu_parity.test_blend_sparse_masks_bit_exact; classified in tests/test_constructed_multiband.py)"""
+    out = []
+    for k, m in enumerate(masks):
+        hh, ww = m.shape
+        z = np.zeros_like(m)
+        if kind == "islands":
+            for x in (0, 500, 1016, ww - 40):
+                y = int(rng.integers(0, hh - 30))
+                z[y:y + 24, x:x + 33] = m[y:y + 24, x:x + 33]
+        elif kind == "empty_and_dots":
+            if k != 1:  # image 1: nothing at all
+                for (y, x) in ((0, 0), (hh - 1, ww - 1), (hh // 2, 511), (hh // 2 + 1, 512), (3, ww // 3)):
+                    z[y, x] = 255
+        elif kind == "grey_islands":
+            for _ in range(5):
+                y, x = int(rng.integers(0, hh - 20)), int(rng.integers(0, ww - 80))
+                z[y:y + 17, x:x + 70] = rng.integers(0, 256, (17, 70), dtype=np.uint8)
+        else:
+            z[0, :] = 255; z[hh - 1, :] = 255; z[:, 0] = 255; z[:, ww - 1] = 255
+            z &= m if k % 2 else z
+        out.append(z)
+    return out

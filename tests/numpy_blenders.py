@@ -87,8 +87,13 @@ def result_roi(corners, sizes):
 
 
 class NumpyMultiBand:
-    def __init__(self, num_bands):
+    """keep=True records what tests/constructed_multiband.classify restates the kernels' tests on: per feed its rectangle (relative to
+    the padded roi) and its G, W and Laplacian pyramids in `fed`; after blend() the normalised levels in `norm` and the finished
+    (collapsed) levels in `finished`"""
+
+    def __init__(self, num_bands, keep=False):
         self.req = int(num_bands)
+        self.keep, self.fed, self.norm, self.finished = keep, [], None, None
 
     def prepare(self, roi):
         x, y, w, h = roi
@@ -130,6 +135,8 @@ class NumpyMultiBand:
             wt.append(pyr_down_32f(wt[-1]))
         lap = [sat16(g[i].astype(np.int32) - pyr_up_16s(g[i + 1]).astype(np.int32)) for i in range(B)] + [g[B]]
         x0, y0, x1, y1 = tlx - rx, tly - ry, brx - rx, bry - ry
+        if self.keep:
+            self.fed.append({"rect": (x0, y0, x1 - x0, y1 - y0), "image": (tl[0] - rx, tl[1] - ry, iw, ih), "g": g, "w": wt, "lap": lap})
         for i in range(B + 1):
             prod = trunc_short((lap[i].astype(np.float32) * wt[i][:, :, None]).astype(np.float32))
             d = self.lap[i][y0:y1, x0:x1]
@@ -143,8 +150,12 @@ class NumpyMultiBand:
         for i in range(B + 1):
             q = (self.lap[i].astype(np.float32) / (self.wts[i] + EPS)[:, :, None]).astype(np.float32)
             lv.append(trunc_short(q))
+        if self.keep:
+            self.norm = [a.copy() for a in lv]
         for i in range(B, 0, -1):
             lv[i - 1] = sat16(pyr_up_16s(lv[i]).astype(np.int32) + lv[i - 1].astype(np.int32))
+        if self.keep:
+            self.finished = lv
         w, h = self.final
         out = lv[0][:h, :w].copy()
         m = np.where(self.wts[0][:h, :w] > EPS, 255, 0).astype(np.uint8)

@@ -457,27 +457,7 @@ def test_blend_sparse_masks_bit_exact(oracle, gpu_ctx, kind):
     rng = np.random.default_rng(31)
 
     def fn(masks, corners, sizes):
-        out = []
-        for k, m in enumerate(masks):
-            hh, ww = m.shape
-            z = np.zeros_like(m)
-            if kind == "islands":
-                for x in (0, 500, 1016, ww - 40):
-                    y = int(rng.integers(0, hh - 30))
-                    z[y:y + 24, x:x + 33] = m[y:y + 24, x:x + 33]
-            elif kind == "empty_and_dots":
-                if k != 1:  # image 1: nothing at all
-                    for (y, x) in ((0, 0), (hh - 1, ww - 1), (hh // 2, 511), (hh // 2 + 1, 512), (3, ww // 3)):
-                        z[y, x] = 255
-            elif kind == "grey_islands":
-                for _ in range(5):
-                    y, x = int(rng.integers(0, hh - 20)), int(rng.integers(0, ww - 80))
-                    z[y:y + 17, x:x + 70] = rng.integers(0, 256, (17, 70), dtype=np.uint8)
-            else:
-                z[0, :] = 255; z[hh - 1, :] = 255; z[:, 0] = 255; z[:, ww - 1] = 255
-                z &= m if k % 2 else z
-            out.append(z)
-        return out
+        return helpers.sparse_masks(kind, masks, rng)  # (rng: the closure's current binding, re-seeded before the device's run)
 
     o = helpers.run_pipeline(oracle.Warper, oracle.Blender, imgs, cams, blend_strength=6, masks_fn=fn)
     rng = np.random.default_rng(31)
@@ -493,30 +473,8 @@ def test_blend_many_images_over_the_same_pixels(oracle, gpu_ctx, n):
     multiplication by v_rcp_f32's reciprocal below 16, the shared-reciprocal IEEE expansion from 16 on.  Extreme pixel values (0 / 255
     checkerboards against flat images) drive the int16 Laplacian sums to both ends of their range; every tier against the oracle's
     plain fp32 division, with counts that change inside a lane's 8 x 2 patch (ragged mask edges)."""
-    rng = np.random.default_rng(1000 + n)
-    w, h = 1100, 96
-    yy, xx = np.mgrid[0:h, 0:w]
-    imgs, masks, corners = [], [], []
-    for k in range(n):
-        kind = k % 4
-        if kind == 0:
-            im = np.where(((xx + yy + k) & 1)[..., None] == 1, 255, 0).astype(np.uint8).repeat(3, axis=2)
-        elif kind == 1:
-            im = np.full((h, w, 3), 255 if k % 8 == 1 else 0, np.uint8)
-        else:
-            im = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
-        m = np.full((h, w), 255, np.uint8)
-        x0, x1 = int(rng.integers(0, 200)), int(rng.integers(w - 200, w + 1))
-        m[:, :x0] = 0
-        m[:, x1:] = 0
-        ragged = rng.integers(0, 12, h)
-        for y in range(h):  # ragged left edge: the count changes from pixel to pixel within a lane's patch
-            m[y, x0:x0 + int(ragged[y])] = 0
-        if k % 5 == 4:
-            m[rng.integers(0, 2, (h, w)) == 0] = 0  # a salt-and-pepper mask
-        imgs.append(im)
-        masks.append(m)
-        corners.append((int(rng.integers(0, 9)) if k else 0, int(rng.integers(0, 5)) if k else 0))
+    imgs, masks, corners = helpers.many_images_feeds(n)
+    w, h = masks[0].shape[1], masks[0].shape[0]
     sizes = [(w, h)] * n
     ob, gb = oracle.Blender("multiband", 10), S.Blender("multiband", 10)  # 5 bands
     ob.prepare(corners, sizes)

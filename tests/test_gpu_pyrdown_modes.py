@@ -30,20 +30,7 @@ def _inputs():
     return [synthetic.make_frame(800 + i, w, h) for i in range(4)], cams
 
 
-def _weight_pyramid_of_export(packed, rect, nb):
-    """the fp32 weight planes W_0 .. W_nb out of a packed contribution strip (csrc/stx_blend_host.cpp mb_contrib_layout: per level three
-    int16 planes, row pitch a multiple of 32 samples, then the weights, pitch a multiple of 16; every section on a 256-byte boundary)"""
-    raw = np.asarray(packed).reshape(-1)
-    w, h = rect[2], rect[3]
-    up = lambda v, a: (v + a - 1) // a * a  # noqa: E731
-    off, out = 0, []
-    for i in range(nb + 1):
-        lw, lh = max(w >> i, 1), max(h >> i, 1)
-        off = up(off + up(lw, 32) * lh * 3 * 2, 256)
-        ws = up(lw, 16)
-        out.append(raw[off:off + ws * lh * 4].view(np.float32).reshape(lh, ws)[:, :lw].copy())
-        off = up(off + ws * lh * 4, 256)
-    return out
+_weight_pyramid_of_export = helpers.weight_pyramid_of_export
 
 
 @pytest.mark.parametrize("grey", [False, True])

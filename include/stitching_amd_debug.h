@@ -45,6 +45,12 @@ int stx_debug_blend_uploads(stx_ctx* ctx, int* out_uploads);
  * blend() of another kind).  tests/test_gpu_blend_resident.py. */
 int stx_debug_blend_mask_stored(stx_ctx* ctx, int* out_stored);
 
+/* Which kernels the seam masks of this context went through (stx_seam_mask_resize, stx_seam_mask_resize_batch, ..._batch_sub): the
+ * profiler gives every path the one name "seam_mask_resize".  out_images = images launched so far, counted since the context was made,
+ * through {the one-launch LDS kernel, the table-fed 4-pixel batch kernels, the single-image 4-pixel kernels, the per-pixel kernel}.
+ * A caller reads it before and after a call and takes the difference.  tests/test_gpu_constructed_resizes.py. */
+int stx_debug_seam_resize_paths(stx_ctx* ctx, int out_images[4]);
+
 #ifdef __cplusplus
 }
 #endif

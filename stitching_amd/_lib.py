@@ -188,6 +188,7 @@ PROTOTYPES = {
     "stx_debug_warp_table_launches": [_vp, _ip],
     "stx_debug_blend_uploads": [_vp, _ip],
     "stx_debug_blend_mask_stored": [_vp, _ip],
+    "stx_debug_seam_resize_paths": [_vp, _ip],
 }
 EXPORTS = tuple(PROTOTYPES)
 

@@ -104,6 +104,9 @@ struct stx_ctx {
     int warp_table_launches = 0;
     int blend_uploads = 0;
     int blend_mask_stored = 0;  // the level-0 launch of the last multi-band blend() stored the panorama mask (stx_debug_blend_mask_stored)
+    // seam masks sent through {one-launch LDS, table 4-pixel batch, single 4-pixel, per-pixel} since the context was made
+    // (stx_debug_seam_resize_paths): bumped where stx_resize.hip makes the launches
+    int seam_resize_paths[4] = {0, 0, 0, 0};
 };
 
 #define STX_STAGE_SEGS 4

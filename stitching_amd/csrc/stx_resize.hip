@@ -191,6 +191,7 @@ int stx_launch_seam_resize_batch(stx_ctx* ctx, int n, const stx_buf* const* seam
         StxProfScope prof(ctx, "seam_mask_resize", bytes);
         hipLaunchKernelGGL(dilate3x3_batch_kernel, dim3((msw + 63) / 64, (msh + 3) / 4, m), dim3(256), 0, ctx->stream, B);
         hipLaunchKernelGGL(seam_resize4_batch_kernel, dim3((mdw + 255) / 256, (mdh + 4 * SEAM_ROWS - 1) / (4 * SEAM_ROWS), m), dim3(256), 0, ctx->stream, B);
+        ctx->seam_resize_paths[1] += m;
     }
     return stx_check_launch("seam_mask_resize");
 }
@@ -370,6 +371,7 @@ int stx_launch_seam_resize_lds(stx_ctx* ctx, int n, const stx_buf* const* seams,
         }
         StxProfScope prof(ctx, "seam_mask_resize", bytes);
         hipLaunchKernelGGL(seam_resize_lds_kernel, dim3((mdw + SEAM1_TW - 1) / SEAM1_TW, (mdh + SEAM1_TH - 1) / SEAM1_TH, m), dim3(256), lds, ctx->stream, B);
+        ctx->seam_resize_paths[0] += m;
     }
     *done = true;
     return stx_check_launch("seam_mask_resize");
@@ -397,7 +399,11 @@ int stx_launch_resize_exact(stx_ctx* ctx, const stx_buf* src, stx_buf* dst, cons
                            (long long)src->stride, src->w, src->h, (uint8_t*)tmp.get(), (long long)tstride);
         K.src = (const uint8_t*)tmp.get(); K.sstride = (long long)tstride;
         hipLaunchKernelGGL(seam_resize4_kernel, dim3((dst->w + 255) / 256, (dst->h + 4 * SEAM_ROWS - 1) / (4 * SEAM_ROWS)), dim3(256), 0, ctx->stream, K);
-    } else if (dilate) hipLaunchKernelGGL((resize_exact_kernel<1, true>), grid, dim3(256), 0, ctx->stream, K);
+        ctx->seam_resize_paths[2]++;
+    } else if (dilate) {
+        hipLaunchKernelGGL((resize_exact_kernel<1, true>), grid, dim3(256), 0, ctx->stream, K);
+        ctx->seam_resize_paths[3]++;
+    }
     else if (src->c == 1) hipLaunchKernelGGL((resize_exact_kernel<1, false>), grid, dim3(256), 0, ctx->stream, K);
     else if (src->c == 3) hipLaunchKernelGGL((resize_exact_kernel<3, false>), grid, dim3(256), 0, ctx->stream, K);
     else return stx_fail(STX_ERR_UNSUPPORTED, "resize: 1 or 3 channels");

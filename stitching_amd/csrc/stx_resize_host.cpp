@@ -225,3 +225,11 @@ STX_EXPORT int stx_seam_mask_resize_batch_sub(stx_ctx* ctx, int n, const stx_buf
     if (!full_wh_xy0 && n > 0) return stx_fail(STX_ERR_INVALID, "null argument");
     return seam_resize_batch_impl(ctx, n, seam_masks, final_masks, full_wh_xy0, outs);
 }
+
+// include/stitching_amd_debug.h: which kernels the seam masks of this context went through so far
+STX_EXPORT int stx_debug_seam_resize_paths(stx_ctx* ctx, int out_images[4])
+{
+    if (!ctx || !out_images) return stx_fail(STX_ERR_INVALID, "null argument");
+    std::copy(ctx->seam_resize_paths, ctx->seam_resize_paths + 4, out_images);
+    return STX_OK;
+}

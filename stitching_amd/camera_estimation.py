@@ -29,6 +29,7 @@ import warnings
 import numpy as np
 
 from . import _lib
+from ._marshal import info_dict, ptr
 from .camera import CameraParams
 from .device import get_context
 from .match_estimation import centred_points, level0_points
@@ -367,9 +368,7 @@ class RayProblem:
         cams = np.ascontiguousarray(np.asarray(edges, np.int32).reshape(-1, 2))
         offsets = np.ascontiguousarray(offsets, np.int64)
         xyuv = np.ascontiguousarray(xyuv, np.float64)
-        _lib.check(self.ctx._lib.stx_ray_problem_create(
-            self.ctx.handle, self.n_edges, cams.ctypes.data_as(C.POINTER(C.c_int)), offsets.ctypes.data_as(C.POINTER(C.c_longlong)),
-            xyuv.ctypes.data_as(C.POINTER(C.c_double)), C.byref(self._h)))
+        _lib.check(self.ctx._lib.stx_ray_problem_create(self.ctx.handle, self.n_edges, ptr(cams), ptr(offsets), ptr(xyuv), C.byref(self._h)))
         self.info = None
 
     def evaluate(self, variants):
@@ -381,11 +380,10 @@ class RayProblem:
         if self.model == "reproj" and (variants.ndim != 3 or variants.shape[1:] != (15, 18)):
             raise StitchingError(f"variants of shape {variants.shape}: the reprojection adjustment takes (cameras, 15, 18)")
         out, info = np.zeros((self.n_edges, 120 if self.model == "reproj" else 45), np.float64), np.zeros(4, np.float64)
-        dp = C.POINTER(C.c_double)
         entry = {"affine": self.ctx._lib.stx_affine_problem_eval, "reproj": self.ctx._lib.stx_reproj_problem_eval}.get(
             self.model, self.ctx._lib.stx_ray_problem_eval)
-        _lib.check(entry(self._h, int(variants.shape[0]), variants.ctypes.data_as(dp), out.ctypes.data_as(dp), info.ctypes.data_as(dp)))
-        self.info = {"edges": int(info[0]), "matches": int(info[1]), "device_ms": float(info[2]), "device_ms_with_copy": float(info[3])}
+        _lib.check(entry(self._h, int(variants.shape[0]), ptr(variants), ptr(out), ptr(info)))
+        self.info = info_dict(info, [("edges", int), ("matches", int), ("device_ms", float), ("device_ms_with_copy", float)])
         return out
 
     def free(self):

@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _lib
 from .blender import Blender
+from ._marshal import host_array
 from .device import DeviceImage, as_device, get_context, is_foreign_device_array
 from .stitching_error import StitchingError
 
@@ -68,9 +69,7 @@ def largest_interior_rectangle(mask, ctx=None):
     if is_foreign_device_array(mask):
         mask = as_device(mask, ctx)
     if not isinstance(mask, DeviceImage):
-        if not isinstance(mask, np.ndarray) and hasattr(mask, "get"):
-            mask = mask.get()
-        mask = np.asarray(mask)
+        mask = host_array(mask)
         if mask.ndim != 2:
             raise StitchingError(f"the panorama mask must be HxW, got shape {mask.shape}")
         if mask.dtype != np.uint8:

@@ -41,8 +41,7 @@ STX_EXPORT int stx_ray_problem_create(stx_ctx* ctx, int n_edges, const int* edge
         STX_HIP(hipMemcpyAsync(P->d_edge_cams.get(), edge_cams, (size_t)n_edges * 2 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
         STX_HIP(hipMemcpyAsync(P->d_offsets.get(), offsets, ((size_t)n_edges + 1) * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
         if (total > 0) STX_HIP(hipMemcpyAsync(P->d_pts.get(), pts, (size_t)total * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        for (hipEvent_t& ev : P->ev)
-            if (hipEventCreate(&ev) != hipSuccess) return stx_fail(STX_ERR_HIP, "hipEventCreate failed");
+        STX_TRY(P->timer.arm(4));
         STX_HIP(hipStreamSynchronize(ctx->stream));  // the caller's arrays are free again
     }
     *out = P.release();
@@ -72,18 +71,16 @@ int problem_eval(stx_ray_problem* P, const char* what, int count, int width, int
     if (!out) return stx_fail(STX_ERR_INVALID, "null argument");
     stx_ctx* ctx = P->ctx;
     STX_TRY(stx_set_device(ctx));
-    STX_HIP(hipEventRecord(P->ev[0], ctx->stream));
+    STX_TRY(P->timer.mark(0, ctx->stream));
     STX_HIP(hipMemcpyAsync(P->d_variants.get(), variants, (size_t)P->min_cams * per_cam * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     STX_TRY(launch(ctx, P->n_edges, (const int*)P->d_edge_cams.get(), (const long long*)P->d_offsets.get(), (const double*)P->d_pts.get(),
-                   (const double*)P->d_variants.get(), (double*)P->d_out.get(), P->ev[1], P->ev[2]));
+                   (const double*)P->d_variants.get(), (double*)P->d_out.get(), P->timer.ev[1], P->timer.ev[2]));
     STX_HIP(hipMemcpyAsync(out, P->d_out.get(), (size_t)P->n_edges * sums * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    STX_HIP(hipEventRecord(P->ev[3], ctx->stream));
+    STX_TRY(P->timer.mark(3, ctx->stream));
     STX_HIP(hipStreamSynchronize(ctx->stream));  // the one wait
     if (out_info) {
-        float a = 0.f, b = 0.f;
-        if (hipEventElapsedTime(&a, P->ev[1], P->ev[2]) != hipSuccess || hipEventElapsedTime(&b, P->ev[0], P->ev[3]) != hipSuccess)
-            return stx_fail(STX_ERR_HIP, "hipEventElapsedTime failed");
-        out_info[2] = a; out_info[3] = b;
+        STX_TRY(P->timer.ms(1, 2, &out_info[2]));
+        STX_TRY(P->timer.ms(0, 3, &out_info[3]));
     }
     return STX_OK;
 }

@@ -282,19 +282,6 @@ __global__ __launch_bounds__(CROP_WG) void crop_reduce_kernel(const CropBest* be
     }
 }
 
-struct CropRun {
-    stx_ctx* ctx = nullptr;
-    StxDevBlock blocks[4];
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~CropRun()
-    {
-        if (!ctx) return;
-        hipStreamSynchronize(ctx->stream);
-        for (StxDevBlock& p : blocks) p.reset();  // behind the synchronisation, in the order they were taken
-        for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
-    }
-};
-
 }  // namespace
 
 STX_EXPORT int stx_crop_lir(stx_ctx* ctx, const stx_buf* mask, int out_xywh[4], int out_contours[2], double out_info[1])
@@ -308,25 +295,22 @@ STX_EXPORT int stx_crop_lir(stx_ctx* ctx, const stx_buf* mask, int out_xywh[4], 
     if (H > 65535) return stx_fail(STX_ERR_INVALID, "mask of %d rows: at most 65535", H);
     if ((long long)W * H >= (1ll << 31) - 1) return stx_fail(STX_ERR_INVALID, "mask of %d x %d pixels: at most 2^31 - 2 pixels", W, H);
     STX_TRY(stx_set_device(ctx));
-    CropRun X;
-    X.ctx = ctx;
+    // locals go in the reverse order of their declaration: the guard's wait first, behind it the blocks in the order they were taken
+    // (lab, scratch, best, res), then the events
+    StxEventTimer timer;
+    StxDevBlock res, best, scratch, lab;
+    StxRunGuard wait(ctx);
     const long long N = (long long)W * H;
     const int grid = std::min(H, CROP_ROWS_GRID);
     const bool in_lds = W <= CROP_LDS_MAX_W;
-    StxDevBlock* lab = &X.blocks[0];
-    StxDevBlock* scratch = &X.blocks[1];
-    StxDevBlock* best = &X.blocks[2];
-    StxDevBlock* res = &X.blocks[3];
-    STX_TRY(stx_dev_alloc(ctx, sizeof(int) * (size_t)(N + 1), lab));
-    STX_TRY(stx_dev_alloc(ctx, in_lds ? 4 : sizeof(int) * 2 * (size_t)W * grid, scratch));
-    STX_TRY(stx_dev_alloc(ctx, sizeof(CropBest) * (size_t)H, best));
-    STX_TRY(stx_dev_alloc(ctx, sizeof(int) * 8, res));
-    int* d_lab = (int*)lab->get();
-    int* d_res = (int*)res->get();
-    if (out_info) {
-        for (hipEvent_t& e : X.ev) STX_HIP(hipEventCreate(&e));
-        STX_HIP(hipEventRecord(X.ev[0], ctx->stream));
-    }
+    STX_TRY(stx_dev_alloc(ctx, sizeof(int) * (size_t)(N + 1), &lab));
+    STX_TRY(stx_dev_alloc(ctx, in_lds ? 4 : sizeof(int) * 2 * (size_t)W * grid, &scratch));
+    STX_TRY(stx_dev_alloc(ctx, sizeof(CropBest) * (size_t)H, &best));
+    STX_TRY(stx_dev_alloc(ctx, sizeof(int) * 8, &res));
+    int* d_lab = (int*)lab.get();
+    int* d_res = (int*)res.get();
+    if (out_info) STX_TRY(timer.arm(2));
+    STX_TRY(timer.mark(0, ctx->stream));
     STX_HIP(hipMemsetAsync(d_res, 0, sizeof(int) * 8, ctx->stream));
     const CropMask M{mask->ptr, (long long)mask->stride, W, H};
     const dim3 px((W + CROP_WG - 1) / CROP_WG, H);
@@ -353,27 +337,23 @@ STX_EXPORT int stx_crop_lir(stx_ctx* ctx, const stx_buf* mask, int out_xywh[4], 
         STX_TRY(stx_check_launch("crop_cols"));
     }
     {
-        CropRowsK K{d_v, W, H, (int*)scratch->get(), (CropBest*)best->get()};
+        CropRowsK K{d_v, W, H, (int*)scratch.get(), (CropBest*)best.get()};
         StxProfScope prof(ctx, "crop_rows", (double)N * 4);
         hipLaunchKernelGGL(crop_rows_kernel, dim3(grid), dim3(CROP_WG), in_lds ? sizeof(int) * 3 * (size_t)W : 0, ctx->stream, K);
         STX_TRY(stx_check_launch("crop_rows"));
     }
     {
         StxProfScope prof(ctx, "crop_reduce", (double)H * sizeof(CropBest));
-        hipLaunchKernelGGL(crop_reduce_kernel, dim3(1), dim3(CROP_WG), 0, ctx->stream, (const CropBest*)best->get(), H, d_res);
+        hipLaunchKernelGGL(crop_reduce_kernel, dim3(1), dim3(CROP_WG), 0, ctx->stream, (const CropBest*)best.get(), H, d_res);
         STX_TRY(stx_check_launch("crop_reduce"));
     }
-    if (out_info) STX_HIP(hipEventRecord(X.ev[1], ctx->stream));
+    STX_TRY(timer.mark(1, ctx->stream));
     int h_res[8] = {0};
     STX_HIP(hipMemcpyAsync(h_res, d_res, sizeof(h_res), hipMemcpyDeviceToHost, ctx->stream));
     STX_HIP(hipStreamSynchronize(ctx->stream));
     out_contours[0] = h_res[0];
     out_contours[1] = h_res[1];
     for (int k = 0; k < 4; k++) out_xywh[k] = h_res[2 + k];
-    if (out_info) {
-        float ms = 0.f;
-        STX_HIP(hipEventElapsedTime(&ms, X.ev[0], X.ev[1]));
-        out_info[0] = ms;
-    }
+    if (out_info) STX_TRY(timer.ms(0, 1, &out_info[0]));
     return STX_OK;
 }

@@ -140,24 +140,11 @@ STX_EXPORT int stx_emit(stx_ctx* ctx, int n, const stx_emit_item* in, int matrix
     STX_TRY(upload_small(ctx, items.data(), items.size() * sizeof(StxEmitItem), &d_items));
     // the protocol's handle 1, the legacy default stream, is the runtime's null stream; 2 is hipStreamPerThread's own value (stx_ingest)
     hipStream_t consumer = (uintptr_t)consumer_stream == 1 ? nullptr : (hipStream_t)consumer_stream;
-    if (has_stream) {  // after whatever the consumer has queued (it may still read the surface): an event there, waited for by the
-                       // context's stream — no host wait
-        hipEvent_t ev = nullptr;
-        STX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        hipError_t e = hipEventRecord(ev, consumer);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ev, 0);
-        hipEventDestroy(ev);  // released by the runtime once it has completed
-        if (e != hipSuccess) return stx_fail(STX_ERR_HIP, "emit: ordering after the consumer's stream failed: %s", hipGetErrorString(e));
-    }
+    // after whatever the consumer has queued (it may still read the surface): no host wait
+    if (has_stream) STX_TRY(stx_stream_wait(ctx->stream, consumer, "emit: ordering after the consumer's stream"));
     STX_TRY(stx_launch_emit(ctx, (const StxEmitItem*)d_items.get(), n, (int)tiles, kCoef[matrix][range], bytes));
-    if (has_stream) {  // and the consumer's stream after the launch
-        hipEvent_t ev = nullptr;
-        STX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        hipError_t e = hipEventRecord(ev, ctx->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(consumer, ev, 0);
-        hipEventDestroy(ev);
-        if (e != hipSuccess) return stx_fail(STX_ERR_HIP, "emit: ordering the consumer's stream after the launch failed: %s", hipGetErrorString(e));
-    }
+    // and the consumer's stream after the launch
+    if (has_stream) STX_TRY(stx_stream_wait(consumer, ctx->stream, "emit: ordering the consumer's stream after the launch"));
     for (size_t k = 0; k < made.size(); k++) out[k] = made[k].release();
     return STX_OK;  // the descriptor block goes back here: stream-ordered reuse
 }

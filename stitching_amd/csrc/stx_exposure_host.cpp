@@ -308,20 +308,16 @@ int exp_sqrt_table(stx_ctx* ctx)
 }
 
 // device side of the feeds: the job table once, the statistics of one feed per call; between feeds the multiplied images and their gain tables
+// Members go in the reverse order of their declaration: the guard's wait first, and behind it everything goes back in this order — the
+// scratch images, d_bg, d_bt, d_imgs, d_jobs, d_oi, d_od, the events.
 struct ExpRun {
-    stx_ctx* ctx = nullptr;
+    stx_ctx* ctx;
+    StxEventTimer timer;  // around the statistics launch
+    StxDevBlock d_od, d_oi, d_jobs, d_imgs;
+    StxDevBlock d_bt, d_bg;          // StxExpBlockMul per image, float gains per block
     std::vector<StxBufRef> scratch;  // the images multiplied between feeds (the caller's are never written)
-    StxDevBlock d_bg, d_bt;          // float gains per block, StxExpBlockMul per image
-    StxDevBlock d_imgs, d_jobs, d_oi, d_od;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~ExpRun()
-    {
-        if (!ctx) return;
-        hipStreamSynchronize(ctx->stream);
-        scratch.clear();  // everything goes back behind the synchronisation, in this order
-        for (StxDevBlock* p : {&d_bg, &d_bt, &d_imgs, &d_jobs, &d_oi, &d_od}) p->reset();
-        for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
-    }
+    StxRunGuard wait;
+    explicit ExpRun(stx_ctx* c) : ctx(c), wait(c) {}
 };
 
 int exp_stats(ExpRun& X, const ExpPlan& P, const stx_buf* const* imgs, const stx_buf* const* masks, std::vector<long long>& oi,
@@ -345,17 +341,17 @@ int exp_stats(ExpRun& X, const ExpPlan& P, const stx_buf* const* imgs, const stx
     for (const StxExpJob& J : P.jobs) bytes += 8.0 * J.w * J.h;
     STX_HIP(hipMemcpyAsync(X.d_imgs.get(), tab.data(), sizeof(StxExpImg) * P.n, hipMemcpyHostToDevice, ctx->stream));
     const int mode = kind_channels(P.kind) ? STX_EXP_INT : (P.kind == STX_EXPOSURE_GAIN_BLOCKS ? STX_EXP_ORDERED : STX_EXP_TREE);
-    if (ms && !X.ev[0]) { STX_HIP(hipEventCreate(&X.ev[0])); STX_HIP(hipEventCreate(&X.ev[1])); }
-    if (ms) STX_HIP(hipEventRecord(X.ev[0], ctx->stream));
+    if (ms) STX_TRY(X.timer.arm(2));
+    STX_TRY(X.timer.mark(0, ctx->stream));
     STX_TRY(stx_launch_exposure_stats(ctx, (const StxExpImg*)X.d_imgs.get(), (const StxExpJob*)X.d_jobs.get(), nj, mode, ctx->exp_sqrt,
                                       (long long*)X.d_oi.get(), (double*)X.d_od.get(), bytes));
-    if (ms) STX_HIP(hipEventRecord(X.ev[1], ctx->stream));
+    STX_TRY(X.timer.mark(1, ctx->stream));
     STX_HIP(hipMemcpyAsync(oi.data(), X.d_oi.get(), sizeof(long long) * 7 * nj, hipMemcpyDeviceToHost, ctx->stream));
     STX_HIP(hipMemcpyAsync(od.data(), X.d_od.get(), sizeof(double) * 2 * nj, hipMemcpyDeviceToHost, ctx->stream));
     STX_HIP(hipStreamSynchronize(ctx->stream));
     if (ms) {
-        float e = 0.f;
-        STX_HIP(hipEventElapsedTime(&e, X.ev[0], X.ev[1]));
+        double e = 0.0;
+        STX_TRY(X.timer.ms(0, 1, &e));
         *ms += e;
     }
     return STX_OK;
@@ -439,8 +435,7 @@ STX_EXPORT int stx_exposure_stats(stx_ctx* ctx, int kind, int n, const stx_buf* 
     STX_TRY(exp_check_ctx(ctx, P, imgs));
     STX_TRY(stx_set_device(ctx));
     STX_TRY(exp_sqrt_table(ctx));
-    ExpRun X;
-    X.ctx = ctx;
+    ExpRun X(ctx);
     std::vector<long long> oi;
     std::vector<double> od;
     STX_TRY(exp_stats(X, P, imgs, masks, oi, od, nullptr));
@@ -479,8 +474,7 @@ STX_EXPORT int stx_exposure_feed_ex(stx_ctx* ctx, int kind, int n, const stx_buf
     const bool blocks = kind_blocks(kind);
     std::vector<double> acc((size_t)planes * m, 1.0), g((size_t)planes * m, 1.0);
     std::vector<const stx_buf*> cur(imgs, imgs + n);
-    ExpRun X;
-    X.ctx = ctx;
+    ExpRun X(ctx);
     std::vector<StxBufRef>& scratch = X.scratch;
     double stats_ms = 0.0, host_ms = 0.0, dev_acc[3] = {0.0, 0.0, 0.0};
     stx_ctx* const solve_on = solver == STX_EXPOSURE_SOLVER_DEVICE ? ctx : nullptr;

@@ -137,12 +137,7 @@ STX_EXPORT int stx_ingest(stx_ctx* ctx, int n, const stx_foreign_frame* frames, 
         // the protocol's handle 1, the legacy default stream, is the runtime's null stream (the runtime takes no handle of value 1:
         // hipEventRecord on it crashed); 2 is hipStreamPerThread's own value
         hipStream_t producer = (uintptr_t)producer_stream == 1 ? nullptr : (hipStream_t)producer_stream;
-        hipEvent_t ev = nullptr;
-        STX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        hipError_t e = hipEventRecord(ev, producer);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ev, 0);
-        hipEventDestroy(ev);  // released by the runtime once it has completed
-        if (e != hipSuccess) return stx_fail(STX_ERR_HIP, "ingest: ordering after the producer's stream failed: %s", hipGetErrorString(e));
+        STX_TRY(stx_stream_wait(ctx->stream, producer, "ingest: ordering after the producer's stream"));
     }
     STX_TRY(stx_launch_ingest(ctx, (const StxIngestItem*)d_items.get(), n, (int)tiles, kCoef[matrix][range], bytes));
     for (int i = 0; i < n; i++) out[i] = dsts[i].release();

@@ -48,6 +48,47 @@ inline int stx_check_launch(const char* what)
         if (rc_ != STX_OK) return rc_; \
     } while (0)
 
+// the timing events of one estimator run, at most 4.  arm(n) where the caller asked for timings; mark(k) records event k and does nothing
+// while the timer is not armed; ms(a, b) reads the time between two marks once the stream has been waited for
+struct StxEventTimer {
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    int armed = 0;  // events created
+    StxEventTimer() = default;
+    StxEventTimer(const StxEventTimer&) = delete;
+    StxEventTimer& operator=(const StxEventTimer&) = delete;
+    ~StxEventTimer() { for (int k = 0; k < armed; k++) hipEventDestroy(ev[k]); }
+    int arm(int n)
+    {
+        for (; armed < n && armed < 4; armed++) STX_HIP(hipEventCreate(&ev[armed]));
+        return STX_OK;
+    }
+    int mark(int k, hipStream_t stream)
+    {
+        if (k < armed) STX_HIP(hipEventRecord(ev[k], stream));
+        return STX_OK;
+    }
+    int ms(int a, int b, double* out) const
+    {
+        float t = 0.f;
+        STX_HIP(hipEventElapsedTime(&t, ev[a], ev[b]));
+        *out = t;
+        return STX_OK;
+    }
+};
+
+// `waiter` goes on behind what `signaller` has queued so far: an untimed event there, waited for by `waiter` — no host wait.  The runtime
+// releases the event once it has completed.  what: the caller's words for the message, "<what> failed: ..."
+inline int stx_stream_wait(hipStream_t waiter, hipStream_t signaller, const char* what)
+{
+    hipEvent_t ev = nullptr;
+    STX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, signaller);
+    if (e == hipSuccess) e = hipStreamWaitEvent(waiter, ev, 0);
+    hipEventDestroy(ev);
+    if (e != hipSuccess) return stx_fail(STX_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    return STX_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // context: stream, caching allocator, profiler
 // ---------------------------------------------------------------------------------------------
@@ -126,6 +167,16 @@ inline int stx_dev_alloc(stx_ctx* ctx, size_t bytes, StxDevBlock* out)
     *out = StxDevBlock(p, StxDevFree{ctx});
     return STX_OK;
 }
+// guard of an estimator run: waits for the context's stream when the run ends, on a refusal or a HIP error as well.  Members and locals
+// go in the reverse order of their declaration, so declare it BEHIND the blocks, scratch images and timer of the run: it then waits
+// before any of them is given back, and they go back last-declared first.
+struct StxRunGuard {
+    stx_ctx* ctx;
+    explicit StxRunGuard(stx_ctx* c) : ctx(c) {}
+    StxRunGuard(const StxRunGuard&) = delete;
+    StxRunGuard& operator=(const StxRunGuard&) = delete;
+    ~StxRunGuard() { if (ctx) hipStreamSynchronize(ctx->stream); }
+};
 // small host array -> a fresh block through the context's pinned ring (asynchronous)
 int upload_small(stx_ctx* ctx, const void* h, size_t bytes, StxDevBlock* d_out);
 size_t align_up(size_t v, size_t a);
@@ -379,8 +430,7 @@ struct stx_ray_problem {
     int n_edges = 0, min_cams = 0;  // min_cams: the largest camera an edge names, plus one
     long long total = 0;
     StxDevBlock d_edge_cams, d_offsets, d_pts, d_variants, d_out;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // start, launch, launch done, copy back queued
-    ~stx_ray_problem() { for (hipEvent_t e : ev) if (e) hipEventDestroy(e); }
+    StxEventTimer timer;  // start, launch, launch done, copy back queued: armed with the problem, destroyed with it (before the blocks)
 };
 // E, g[8], B upper triangle[36] of every edge -> d_out[45 n_edges]; start / stop (or null): recorded around the launch
 int stx_launch_ray_normal_equations(stx_ctx* ctx, int n_edges, const int* d_edge_cams, const long long* d_offsets, const double* d_pts,

@@ -8,10 +8,6 @@
 #include "stx_internal.h"
 
 namespace {
-struct MatchEvents {  // start, uploads queued, kernels queued, copies back queued
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~MatchEvents() { for (hipEvent_t e : ev) if (e) hipEventDestroy(e); }
-};
 // STX_MATCH_TRAIN=uniform: match_2nn loads the train descriptors wave-uniformly from memory instead of through LDS tiles (the same
 // results; read at every call, for the A/B of tools/bench_matches.py)
 bool train_through_lds()
@@ -94,12 +90,9 @@ STX_EXPORT int stx_match_features_model(stx_ctx* ctx, int n, const unsigned char
     if (np == 0) return STX_OK;
     STX_TRY(stx_set_device(ctx));
     const int total = off[n];
-    MatchEvents X;
-    if (out_info) {
-        for (hipEvent_t& e : X.ev)
-            if (hipEventCreate(&e) != hipSuccess) return stx_fail(STX_ERR_HIP, "hipEventCreate failed");
-        STX_HIP(hipEventRecord(X.ev[0], ctx->stream));
-    }
+    StxEventTimer timer;  // start, uploads queued, kernels queued, copies back queued
+    if (out_info) STX_TRY(timer.arm(4));
+    STX_TRY(timer.mark(0, ctx->stream));
     StxDevBlock d_desc, d_pts, d_jobs, d_pairs, d_nn, d_counts, d_matches, d_xyuv, d_hyp, d_pick, d_H, d_mask;
     STX_TRY(stx_dev_alloc(ctx, std::max<size_t>((size_t)total * 32, 32), &d_desc));
     STX_TRY(stx_dev_alloc(ctx, std::max<size_t>((size_t)total * 16, 16), &d_pts));
@@ -120,7 +113,7 @@ STX_EXPORT int stx_match_features_model(stx_ctx* ctx, int n, const unsigned char
     STX_TRY(stx_dev_alloc(ctx, np * 9 * sizeof(double), &d_H));
     STX_TRY(stx_dev_alloc(ctx, std::max<size_t>((size_t)cap, 1), &d_mask));
     if (cap > 0) STX_HIP(hipMemsetAsync(d_mask.get(), 0, (size_t)cap, ctx->stream));
-    if (out_info) STX_HIP(hipEventRecord(X.ev[1], ctx->stream));
+    STX_TRY(timer.mark(1, ctx->stream));
     if (!jobs.empty())
         STX_TRY(stx_launch_match_2nn(ctx, (const StxMatchJob*)d_jobs.get(), (int)jobs.size(), (int)blocks, (const uint32_t*)d_desc.get(),
                                      (uint2*)d_nn.get(), compares, train_through_lds()));
@@ -131,7 +124,7 @@ STX_EXPORT int stx_match_features_model(stx_ctx* ctx, int n, const unsigned char
     STX_TRY(stx_launch_match_pick(ctx, (const StxMatchPair*)d_pairs.get(), (int)np, (const int*)d_counts.get(), (const double*)d_xyuv.get(),
                                   ransac_iters, threshold_sq, seed, model, (const int*)d_hyp.get(), (int*)d_pick.get(), (double*)d_H.get(),
                                   (uint8_t*)d_mask.get()));
-    if (out_info) STX_HIP(hipEventRecord(X.ev[2], ctx->stream));
+    STX_TRY(timer.mark(2, ctx->stream));
     STX_HIP(hipMemcpyAsync(out_counts, d_counts.get(), np * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     STX_HIP(hipMemcpyAsync(out_pick, d_pick.get(), np * 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     STX_HIP(hipMemcpyAsync(out_H, d_H.get(), np * 9 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -139,7 +132,7 @@ STX_EXPORT int stx_match_features_model(stx_ctx* ctx, int n, const unsigned char
         STX_HIP(hipMemcpyAsync(out_matches, d_matches.get(), (size_t)cap * 3 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
         STX_HIP(hipMemcpyAsync(out_mask, d_mask.get(), (size_t)cap, hipMemcpyDeviceToHost, ctx->stream));
     }
-    if (out_info) STX_HIP(hipEventRecord(X.ev[3], ctx->stream));
+    STX_TRY(timer.mark(3, ctx->stream));
     STX_HIP(hipStreamSynchronize(ctx->stream));  // the one wait
     long long matches = 0;
     for (size_t k = 0; k < np; k++) {
@@ -148,10 +141,9 @@ STX_EXPORT int stx_match_features_model(stx_ctx* ctx, int n, const unsigned char
         matches += out_counts[k];
     }
     if (out_info) {
-        float a = 0.f, b = 0.f;
-        if (hipEventElapsedTime(&a, X.ev[1], X.ev[2]) != hipSuccess || hipEventElapsedTime(&b, X.ev[0], X.ev[3]) != hipSuccess)
-            return stx_fail(STX_ERR_HIP, "hipEventElapsedTime failed");
-        out_info[1] = (double)matches; out_info[2] = a; out_info[3] = b;
+        out_info[1] = (double)matches;
+        STX_TRY(timer.ms(1, 2, &out_info[2]));
+        STX_TRY(timer.ms(0, 3, &out_info[3]));
     }
     return STX_OK;  // the scratch blocks go back here, behind the synchronisation
 }

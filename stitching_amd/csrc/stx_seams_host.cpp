@@ -58,19 +58,99 @@ int seam_plan(int n, const int* sizes, const int* corners, std::vector<SeamPlanP
     return STX_OK;
 }
 
+// The frame both finders share.  Members go in the reverse order of their declaration: the guard's wait first, behind it the pair table,
+// the arena, the events and, on a failure, the results.
 struct SeamRun {
-    stx_ctx* ctx = nullptr;
-    StxDevBlock d_pairs, d_arena;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    ~SeamRun()
-    {
-        if (!ctx) return;
-        hipStreamSynchronize(ctx->stream);
-        d_pairs.reset();  // behind the synchronisation
-        d_arena.reset();
-        for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
-    }
+    stx_ctx* ctx;
+    std::vector<StxBufRef> outs;  // handed to masks_out at the end
+    StxEventTimer timer;          // start, masks copied, levels queued
+    StxDevBlock d_arena, d_pairs;
+    StxRunGuard wait;
+    SeamRun(stx_ctx* c, int n) : ctx(c), outs(n), wait(c) {}
 };
+
+// n, the pointers and every mask — with `images` (with_images) every image as well —: type, size, context
+int seam_check(stx_ctx* ctx, int n, const int* sizes_wh, const int* corners_xy, bool with_images, const stx_buf* const* images,
+               const stx_buf* const* masks_in, stx_buf** masks_out)
+{
+    if (!ctx) return stx_fail(STX_ERR_INVALID, "ctx is null");
+    if (n < 0 || (n > 0 && (!sizes_wh || !corners_xy || (with_images && !images) || !masks_in || !masks_out)))
+        return stx_fail(STX_ERR_INVALID, "bad argument");
+    for (int k = 0; k < n; k++) {
+        const stx_buf* m = masks_in[k];
+        const stx_buf* im = with_images ? images[k] : nullptr;
+        const int w = sizes_wh[2 * k], h = sizes_wh[2 * k + 1];
+        if (!m) return stx_fail(STX_ERR_INVALID, "null mask %d", k);
+        if (with_images && !im) return stx_fail(STX_ERR_INVALID, "null image %d", k);
+        if (m->elem != STX_U8 || m->c != 1) return stx_fail(STX_ERR_INVALID, "seam finding needs u8x1 masks (mask %d)", k);
+        if (im && (im->elem != STX_U8 || im->c != 3)) return stx_fail(STX_ERR_INVALID, "colour seams need u8x3 images (image %d)", k);
+        if (m->w != w || m->h != h) return stx_fail(STX_ERR_INVALID, "mask %d is %dx%d, its image %dx%d", k, m->w, m->h, w, h);
+        if (im && (im->w != w || im->h != h))
+            return stx_fail(STX_ERR_INVALID, "image %d is %dx%d, its size is given as %dx%d", k, im->w, im->h, w, h);
+        if (m->ctx != ctx) return stx_fail(STX_ERR_INVALID, "mask %d belongs to another context", k);
+        if (im && im->ctx != ctx) return stx_fail(STX_ERR_INVALID, "image %d belongs to another context", k);
+    }
+    return STX_OK;
+}
+
+// what the caller learns of the plan, and no results yet
+void seam_report(const std::vector<SeamPlanPair>& plan, int nlevels, int n, stx_buf** masks_out, double* out_info)
+{
+    if (out_info) { out_info[0] = (double)plan.size(); out_info[1] = nlevels; out_info[2] = 0.0; out_info[3] = 0.0; }
+    for (int k = 0; k < n; k++) masks_out[k] = nullptr;
+}
+
+// the results: copies of the inputs (the caller's masks are never written)
+int seam_copy_masks(SeamRun& X, int n, const stx_buf* const* masks_in, bool timed)
+{
+    stx_ctx* ctx = X.ctx;
+    if (timed) STX_TRY(X.timer.arm(3));
+    STX_TRY(X.timer.mark(0, ctx->stream));
+    for (int k = 0; k < n; k++) {
+        const stx_buf* m = masks_in[k];
+        STX_TRY(stx_buf_new(ctx, m->w, m->h, 1, STX_U8, &X.outs[k]));
+        X.outs[k]->mask_binary = m->mask_binary;  // zeroing keeps a 0 / 255 mask binary
+        if (hipMemcpy2DAsync(X.outs[k]->ptr, X.outs[k]->stride, m->ptr, m->stride, (size_t)m->w, m->h, hipMemcpyDeviceToDevice,
+                             ctx->stream) != hipSuccess)
+            return stx_fail(STX_ERR_HIP, "hipMemcpy2DAsync of a seam mask failed");
+    }
+    return X.timer.mark(1, ctx->stream);
+}
+
+// pairs grouped by level (stable: run() order inside a level): order[t] is the pair of table row t, level l has the rows
+// lstart[l] .. lstart[l + 1]
+void seam_group_levels(const std::vector<SeamPlanPair>& plan, int nlevels, std::vector<int>& order, std::vector<int>& lstart)
+{
+    order.resize(plan.size());
+    for (size_t p = 0; p < plan.size(); p++) order[p] = (int)p;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return plan[a].level < plan[b].level; });
+    lstart.assign(nlevels + 1, 0);
+    for (const SeamPlanPair& P : plan) lstart[P.level + 1]++;
+    for (int l = 0; l < nlevels; l++) lstart[l + 1] += lstart[l];
+}
+
+// the pair table on the device and one arena, of the largest level
+int seam_upload(SeamRun& X, const void* tab, size_t tab_bytes, size_t arena_bytes)
+{
+    STX_TRY(stx_dev_alloc(X.ctx, tab_bytes, &X.d_pairs));
+    STX_TRY(stx_dev_alloc(X.ctx, arena_bytes, &X.d_arena));
+    if (hipMemcpyAsync(X.d_pairs.get(), tab, tab_bytes, hipMemcpyHostToDevice, X.ctx->stream) != hipSuccess)
+        return stx_fail(STX_ERR_HIP, "seam pair table upload failed");
+    return STX_OK;
+}
+
+// the one wait, the two times, and the results are the caller's
+int seam_finish(SeamRun& X, const char* what, int n, stx_buf** masks_out, double* out_info)
+{
+    STX_TRY(X.timer.mark(2, X.ctx->stream));
+    if (hipStreamSynchronize(X.ctx->stream) != hipSuccess) return stx_fail(STX_ERR_HIP, "%s failed", what);
+    if (out_info) {
+        STX_TRY(X.timer.ms(1, 2, &out_info[2]));
+        STX_TRY(X.timer.ms(0, 2, &out_info[3]));
+    }
+    for (int k = 0; k < n; k++) masks_out[k] = X.outs[k].release();
+    return STX_OK;
+}
 
 }  // namespace
 
@@ -97,55 +177,28 @@ STX_EXPORT int stx_seam_find(stx_ctx* ctx, int kind, int n, const int* sizes_wh,
                              stx_buf** masks_out, double out_info[4])
 {
     if (kind != STX_SEAM_NO && kind != STX_SEAM_VORONOI) return stx_fail(STX_ERR_INVALID, "unknown seam finder kind %d", kind);
-    if (!ctx) return stx_fail(STX_ERR_INVALID, "ctx is null");
-    if (n < 0 || (n > 0 && (!sizes_wh || !corners_xy || !masks_in || !masks_out))) return stx_fail(STX_ERR_INVALID, "bad argument");
-    for (int k = 0; k < n; k++) {
-        const stx_buf* m = masks_in[k];
-        if (!m) return stx_fail(STX_ERR_INVALID, "null mask %d", k);
-        if (m->elem != STX_U8 || m->c != 1) return stx_fail(STX_ERR_INVALID, "seam finding needs u8x1 masks (mask %d)", k);
-        if (m->w != sizes_wh[2 * k] || m->h != sizes_wh[2 * k + 1])
-            return stx_fail(STX_ERR_INVALID, "mask %d is %dx%d, its image %dx%d", k, m->w, m->h, sizes_wh[2 * k], sizes_wh[2 * k + 1]);
-        if (m->ctx != ctx) return stx_fail(STX_ERR_INVALID, "mask %d belongs to another context", k);
-    }
+    STX_TRY(seam_check(ctx, n, sizes_wh, corners_xy, false, nullptr, masks_in, masks_out));
     std::vector<SeamPlanPair> plan;
     int nlevels = 0;
-    if (kind == STX_SEAM_VORONOI) STX_TRY(seam_plan(n, sizes_wh, corners_xy, plan, &nlevels));
-    if (out_info) { out_info[0] = (double)plan.size(); out_info[1] = nlevels; out_info[2] = 0.0; out_info[3] = 0.0; }
-    for (int k = 0; k < n; k++) masks_out[k] = nullptr;
-    if (n == 0) return STX_OK;
+    if (kind == STX_SEAM_VORONOI) STX_TRY(seam_plan(n, sizes_wh, corners_xy, plan, &nlevels));  // "no": the copies are the result
+    seam_report(plan, nlevels, n, masks_out, out_info);
+    if (n == 0) return STX_OK;  // nothing to copy or cut: the device is not touched
     STX_TRY(stx_set_device(ctx));
-    std::vector<StxBufRef> outs(n);  // handed to masks_out at the end; on a failure released behind X's synchronisation
-    SeamRun X;
-    X.ctx = ctx;
-    if (out_info) {
-        for (hipEvent_t& e : X.ev)
-            if (hipEventCreate(&e) != hipSuccess) return stx_fail(STX_ERR_HIP, "hipEventCreate failed");
-        if (hipEventRecord(X.ev[0], ctx->stream) != hipSuccess) return stx_fail(STX_ERR_HIP, "hipEventRecord failed");
-    }
-    // the results: copies of the inputs (the caller's masks are never written)
-    for (int k = 0; k < n; k++) {
-        const stx_buf* m = masks_in[k];
-        STX_TRY(stx_buf_new(ctx, m->w, m->h, 1, STX_U8, &outs[k]));
-        outs[k]->mask_binary = m->mask_binary;  // zeroing keeps a 0 / 255 mask binary
-        if (hipMemcpy2DAsync(outs[k]->ptr, outs[k]->stride, m->ptr, m->stride, (size_t)m->w, m->h, hipMemcpyDeviceToDevice,
-                             ctx->stream) != hipSuccess)
-            return stx_fail(STX_ERR_HIP, "hipMemcpy2DAsync of a seam mask failed");
-    }
-    if (out_info && hipEventRecord(X.ev[1], ctx->stream) != hipSuccess) return stx_fail(STX_ERR_HIP, "hipEventRecord failed");
+    SeamRun X(ctx, n);
+    STX_TRY(seam_copy_masks(X, n, masks_in, out_info != nullptr));
     if (!plan.empty()) {
-        // pairs grouped by level (stable: run() order inside a level), arena offsets per level, one arena of the largest level
-        std::vector<int> order(plan.size());
-        for (size_t p = 0; p < plan.size(); p++) order[p] = (int)p;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return plan[a].level < plan[b].level; });
+        // arena offsets per level
+        std::vector<int> order, lstart;
+        seam_group_levels(plan, nlevels, order, lstart);
         std::vector<StxSeamPair> tab(plan.size());
-        std::vector<int> lstart(nlevels + 1, 0), lrows(nlevels, 0), lcols(nlevels, 0);
+        std::vector<int> lrows(nlevels, 0), lcols(nlevels, 0);
         std::vector<long long> lsize(nlevels, 0);
         std::vector<double> lbytes(nlevels, 0.0);
         const int g = STX_SEAM_GAP;
         for (size_t t = 0; t < order.size(); t++) {
             const SeamPlanPair& P = plan[order[t]];
-            const stx_buf* a = outs[P.i].get();
-            const stx_buf* b = outs[P.j].get();
+            const stx_buf* a = X.outs[P.i].get();
+            const stx_buf* b = X.outs[P.j].get();
             StxSeamPair& S = tab[t];
             S.m1 = a->ptr; S.s1 = (long long)a->stride; S.w1 = a->w; S.h1 = a->h;
             S.m2 = b->ptr; S.s2 = (long long)b->stride; S.w2 = b->w; S.h2 = b->h;
@@ -158,33 +211,18 @@ STX_EXPORT int stx_seam_find(stx_ctx* ctx, int kind, int n, const int* sizes_wh,
                 return stx_fail(STX_ERR_INVALID, "internal: seam roi outside its images");
             S.off = lsize[P.level];
             lsize[P.level] += 2ll * S.wh * S.rw;
-            lstart[P.level + 1]++;
             lrows[P.level] = std::max(lrows[P.level], S.wh);
             lcols[P.level] = std::max(lcols[P.level], S.rw);
             lbytes[P.level] += 2.0 * S.ww * S.wh + 12.0 * S.wh * S.rw + (double)S.rw * S.rh;
         }
-        for (int l = 0; l < nlevels; l++) lstart[l + 1] += lstart[l];
         const long long arena = *std::max_element(lsize.begin(), lsize.end());
-        STX_TRY(stx_dev_alloc(ctx, sizeof(StxSeamPair) * tab.size(), &X.d_pairs));
-        STX_TRY(stx_dev_alloc(ctx, sizeof(uint16_t) * (size_t)arena, &X.d_arena));
+        STX_TRY(seam_upload(X, tab.data(), sizeof(StxSeamPair) * tab.size(), sizeof(uint16_t) * (size_t)arena));
         const StxSeamPair* d_pairs = (const StxSeamPair*)X.d_pairs.get();
-        if (hipMemcpyAsync(X.d_pairs.get(), tab.data(), sizeof(StxSeamPair) * tab.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-            return stx_fail(STX_ERR_HIP, "seam pair table upload failed");
         for (int l = 0; l < nlevels; l++)
             STX_TRY(stx_launch_seam_level(ctx, d_pairs + lstart[l], lstart[l + 1] - lstart[l], lrows[l], lcols[l], (uint16_t*)X.d_arena.get(),
                                           lbytes[l]));
     }
-    if (out_info && hipEventRecord(X.ev[2], ctx->stream) != hipSuccess) return stx_fail(STX_ERR_HIP, "hipEventRecord failed");
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return stx_fail(STX_ERR_HIP, "seam finding failed");
-    if (out_info) {
-        float a = 0.f, b = 0.f;
-        if (hipEventElapsedTime(&a, X.ev[1], X.ev[2]) != hipSuccess || hipEventElapsedTime(&b, X.ev[0], X.ev[2]) != hipSuccess)
-            return stx_fail(STX_ERR_HIP, "hipEventElapsedTime failed");
-        out_info[2] = a;
-        out_info[3] = b;
-    }
-    for (int k = 0; k < n; k++) masks_out[k] = outs[k].release();
-    return STX_OK;
+    return seam_finish(X, "seam finding", n, masks_out, out_info);
 }
 
 // The project's own colour-aware finder (tests/numpy_color_seams.py is the contract; not OpenCV's DpSeamFinder): the same pairs, the same
@@ -192,22 +230,7 @@ STX_EXPORT int stx_seam_find(stx_ctx* ctx, int kind, int n, const int* sizes_wh,
 STX_EXPORT int stx_color_seam_find(stx_ctx* ctx, int n, const int* sizes_wh, const int* corners_xy, const stx_buf* const* images,
                                    const stx_buf* const* masks_in, stx_buf** masks_out, double out_info[4])
 {
-    if (!ctx) return stx_fail(STX_ERR_INVALID, "ctx is null");
-    if (n < 0 || (n > 0 && (!sizes_wh || !corners_xy || !images || !masks_in || !masks_out))) return stx_fail(STX_ERR_INVALID, "bad argument");
-    for (int k = 0; k < n; k++) {
-        const stx_buf* m = masks_in[k];
-        const stx_buf* im = images[k];
-        if (!m) return stx_fail(STX_ERR_INVALID, "null mask %d", k);
-        if (!im) return stx_fail(STX_ERR_INVALID, "null image %d", k);
-        if (m->elem != STX_U8 || m->c != 1) return stx_fail(STX_ERR_INVALID, "seam finding needs u8x1 masks (mask %d)", k);
-        if (im->elem != STX_U8 || im->c != 3) return stx_fail(STX_ERR_INVALID, "colour seams need u8x3 images (image %d)", k);
-        if (m->w != sizes_wh[2 * k] || m->h != sizes_wh[2 * k + 1])
-            return stx_fail(STX_ERR_INVALID, "mask %d is %dx%d, its image %dx%d", k, m->w, m->h, sizes_wh[2 * k], sizes_wh[2 * k + 1]);
-        if (im->w != sizes_wh[2 * k] || im->h != sizes_wh[2 * k + 1])
-            return stx_fail(STX_ERR_INVALID, "image %d is %dx%d, its size is given as %dx%d", k, im->w, im->h, sizes_wh[2 * k], sizes_wh[2 * k + 1]);
-        if (m->ctx != ctx) return stx_fail(STX_ERR_INVALID, "mask %d belongs to another context", k);
-        if (im->ctx != ctx) return stx_fail(STX_ERR_INVALID, "image %d belongs to another context", k);
-    }
+    STX_TRY(seam_check(ctx, n, sizes_wh, corners_xy, true, images, masks_in, masks_out));
     std::vector<SeamPlanPair> plan;
     int nlevels = 0;
     STX_TRY(seam_plan(n, sizes_wh, corners_xy, plan, &nlevels));
@@ -230,33 +253,16 @@ STX_EXPORT int stx_color_seam_find(stx_ctx* ctx, int n, const int* sizes_wh, con
             return stx_fail(STX_ERR_INVALID, "colour seam of images %d and %d: %d pixels across the %s seam, at most %d (accumulator rows in LDS)",
                             P.i, P.j, G.W, G.vertical ? "vertical" : "horizontal", STX_COLOR_SEAM_MAX_CROSS);
     }
-    if (out_info) { out_info[0] = (double)plan.size(); out_info[1] = nlevels; out_info[2] = 0.0; out_info[3] = 0.0; }
-    for (int k = 0; k < n; k++) masks_out[k] = nullptr;
-    if (n == 0) return STX_OK;
+    seam_report(plan, nlevels, n, masks_out, out_info);
+    if (n == 0) return STX_OK;  // nothing to copy or cut: the device is not touched
     STX_TRY(stx_set_device(ctx));
-    std::vector<StxBufRef> outs(n);  // handed to masks_out at the end; on a failure released behind X's synchronisation
-    SeamRun X;
-    X.ctx = ctx;
-    if (out_info) {
-        for (hipEvent_t& e : X.ev)
-            if (hipEventCreate(&e) != hipSuccess) return stx_fail(STX_ERR_HIP, "hipEventCreate failed");
-        if (hipEventRecord(X.ev[0], ctx->stream) != hipSuccess) return stx_fail(STX_ERR_HIP, "hipEventRecord failed");
-    }
-    for (int k = 0; k < n; k++) {
-        const stx_buf* m = masks_in[k];
-        STX_TRY(stx_buf_new(ctx, m->w, m->h, 1, STX_U8, &outs[k]));
-        outs[k]->mask_binary = m->mask_binary;  // zeroing keeps a 0 / 255 mask binary
-        if (hipMemcpy2DAsync(outs[k]->ptr, outs[k]->stride, m->ptr, m->stride, (size_t)m->w, m->h, hipMemcpyDeviceToDevice,
-                             ctx->stream) != hipSuccess)
-            return stx_fail(STX_ERR_HIP, "hipMemcpy2DAsync of a seam mask failed");
-    }
-    if (out_info && hipEventRecord(X.ev[1], ctx->stream) != hipSuccess) return stx_fail(STX_ERR_HIP, "hipEventRecord failed");
+    SeamRun X(ctx, n);
+    STX_TRY(seam_copy_masks(X, n, masks_in, out_info != nullptr));
     if (!plan.empty()) {
-        std::vector<int> order(plan.size());
-        for (size_t p = 0; p < plan.size(); p++) order[p] = (int)p;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return plan[a].level < plan[b].level; });
+        std::vector<int> order, lstart;
+        seam_group_levels(plan, nlevels, order, lstart);
         std::vector<StxColorSeamPair> tab(plan.size());
-        std::vector<int> lstart(nlevels + 1, 0), lcross(nlevels, 0);
+        std::vector<int> lcross(nlevels, 0);
         std::vector<long long> lsize(nlevels, 0), larea(nlevels, 0);
         std::vector<double> lbytes(nlevels, 0.0);
         for (size_t t = 0; t < order.size(); t++) {
@@ -264,8 +270,8 @@ STX_EXPORT int stx_color_seam_find(stx_ctx* ctx, int n, const int* sizes_wh, con
             const Geo& G = geo[order[t]];
             const stx_buf* ia = images[P.i];
             const stx_buf* ib = images[P.j];
-            const stx_buf* a = outs[P.i].get();
-            const stx_buf* b = outs[P.j].get();
+            const stx_buf* a = X.outs[P.i].get();
+            const stx_buf* b = X.outs[P.j].get();
             const int xa = P.x - corners_xy[2 * P.i], ya = P.y - corners_xy[2 * P.i + 1];
             const int xb = P.x - corners_xy[2 * P.j], yb = P.y - corners_xy[2 * P.j + 1];
             // the roi (read and written unchecked by the kernels) lies inside both images
@@ -280,31 +286,16 @@ STX_EXPORT int stx_color_seam_find(stx_ctx* ctx, int n, const int* sizes_wh, con
             S.off_choice = lsize[P.level];
             S.off_seam = (long long)align_up((size_t)(S.off_choice + area), 4);
             lsize[P.level] = S.off_seam + 4ll * G.L;
-            lstart[P.level + 1]++;
             lcross[P.level] = std::max(lcross[P.level], G.W);
             larea[P.level] = std::max(larea[P.level], area);
             lbytes[P.level] += 8.0 * area + 2.0 * area + 2.0 * area;  // images and masks, the choices (written, read back at most once), the masks again
         }
-        for (int l = 0; l < nlevels; l++) lstart[l + 1] += lstart[l];
         const long long arena = *std::max_element(lsize.begin(), lsize.end());
-        STX_TRY(stx_dev_alloc(ctx, sizeof(StxColorSeamPair) * tab.size(), &X.d_pairs));
-        STX_TRY(stx_dev_alloc(ctx, (size_t)arena, &X.d_arena));
+        STX_TRY(seam_upload(X, tab.data(), sizeof(StxColorSeamPair) * tab.size(), (size_t)arena));
         const StxColorSeamPair* d_pairs = (const StxColorSeamPair*)X.d_pairs.get();
-        if (hipMemcpyAsync(X.d_pairs.get(), tab.data(), sizeof(StxColorSeamPair) * tab.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-            return stx_fail(STX_ERR_HIP, "seam pair table upload failed");
         for (int l = 0; l < nlevels; l++)
             STX_TRY(stx_launch_color_seam_level(ctx, d_pairs + lstart[l], lstart[l + 1] - lstart[l], lcross[l], larea[l], (uint8_t*)X.d_arena.get(),
                                                 lbytes[l]));
     }
-    if (out_info && hipEventRecord(X.ev[2], ctx->stream) != hipSuccess) return stx_fail(STX_ERR_HIP, "hipEventRecord failed");
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return stx_fail(STX_ERR_HIP, "colour seam finding failed");
-    if (out_info) {
-        float a = 0.f, b = 0.f;
-        if (hipEventElapsedTime(&a, X.ev[1], X.ev[2]) != hipSuccess || hipEventElapsedTime(&b, X.ev[0], X.ev[2]) != hipSuccess)
-            return stx_fail(STX_ERR_HIP, "hipEventElapsedTime failed");
-        out_info[2] = a;
-        out_info[3] = b;
-    }
-    for (int k = 0; k < n; k++) masks_out[k] = outs[k].release();
-    return STX_OK;
+    return seam_finish(X, "colour seam finding", n, masks_out, out_info);
 }

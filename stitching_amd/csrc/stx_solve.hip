@@ -227,11 +227,6 @@ __global__ __launch_bounds__(256) void lu_fill_kernel(const double* A, long long
     if (lane == 0) bout[row] = A[(long long)row * lda + n];
 }
 
-struct LuEvents {
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~LuEvents() { for (hipEvent_t e : ev) if (e) hipEventDestroy(e); }
-};
-
 }  // namespace
 
 // Solves the n x n system given by its non-zero entries (col < n) and its right side (col == n) -> x[n].  out (or null): {device ms of
@@ -260,10 +255,10 @@ int stx_lu_device(stx_ctx* ctx, int n, const StxLuEntry* ent, size_t count, doub
     double* A = (double*)d_A.get();
     int* piv = (int*)d_piv.get();
     int* info = piv + Nr;
-    LuEvents E;
-    if (out) { STX_HIP(hipEventCreate(&E.ev[0])); STX_HIP(hipEventCreate(&E.ev[1])); }
+    StxEventTimer timer;
+    if (out) STX_TRY(timer.arm(2));
     hipStream_t st = ctx->stream;
-    if (out) STX_HIP(hipEventRecord(E.ev[0], st));
+    STX_TRY(timer.mark(0, st));
     STX_HIP(hipMemsetAsync(A, 0, bytes, st));
     STX_HIP(hipMemsetAsync(piv, 0, sizeof(int) * (Nr + 1), st));
     if (count) {
@@ -283,7 +278,7 @@ int stx_lu_device(stx_ctx* ctx, int n, const StxLuEntry* ent, size_t count, doub
                                (const int*)info);
     }
     STX_TRY(stx_check_launch("lu elimination"));
-    if (out) STX_HIP(hipEventRecord(E.ev[1], st));
+    STX_TRY(timer.mark(1, st));
     hipLaunchKernelGGL(lu_count_kernel, dim3((n + 3) / 4), dim3(256), 0, st, (const double*)A, lda, n, (int*)d_cnt.get());
     STX_TRY(stx_check_launch("lu_count"));
     std::vector<int> cnt(n);
@@ -293,9 +288,8 @@ int stx_lu_device(stx_ctx* ctx, int n, const StxLuEntry* ent, size_t count, doub
     STX_HIP(hipStreamSynchronize(st));
     const auto t0 = std::chrono::steady_clock::now();
     if (out) {
-        float ms = 0.f;
-        STX_HIP(hipEventElapsedTime(&ms, E.ev[0], E.ev[1]));
-        out[0] = ms; out[1] = 0.0; out[2] = 0.0;
+        STX_TRY(timer.ms(0, 1, &out[0]));
+        out[1] = 0.0; out[2] = 0.0;
     }
     if (h_info) return stx_fail(STX_ERR_INVALID, "exposure system is singular at row %d", h_info - 1);
     std::vector<long long> off(n + 1, 0);

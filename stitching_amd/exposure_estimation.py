@@ -11,34 +11,20 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .device import DeviceImage, as_device, get_context, is_foreign_device_array
+from ._marshal import count_then_fill, handles, image_spec, info_dict, int_pairs, one_context, ptr
+from .device import as_device, get_context
 from .stitching_error import StitchingError
 
 
-def _check_image(a, what, i):
-    """Shape / dtype check without a host copy of device images (a foreign device array becomes a DeviceImage on the device)."""
-    if is_foreign_device_array(a):
-        a = as_device(a)
-    if isinstance(a, DeviceImage):
-        ch, dt, hw = a.channels, a.dtype, (a.height, a.width)
-    else:
-        if not isinstance(a, np.ndarray) and hasattr(a, "get"):
-            a = a.get()
-        a = np.asarray(a)
-        if a.ndim not in (2, 3):
-            raise StitchingError(f"{what} {i}: expected an HxW or HxWxC array, got shape {a.shape}")
-        ch, dt, hw = (1 if a.ndim == 2 else a.shape[2]), a.dtype, a.shape[:2]
+def _image(a, what, i):
+    """The array (numpy or DeviceImage) and its (w, h): u8 with 3 channels for an image, 1 for a mask, not empty."""
+    a, wh, ch, dt = image_spec(a, what, i)
     want = 3 if what == "image" else 1
     if dt != np.uint8 or ch != want:
         raise StitchingError(f"{what} {i}: exposure estimation needs u8 with {want} channel(s), got {dt} with {ch}")
-    if hw[0] == 0 or hw[1] == 0:
+    if wh[0] == 0 or wh[1] == 0:
         raise StitchingError(f"{what} {i}: empty image")
-    return a, hw
-
-
-def _block_grid(w, h, bl):
-    bpw, bph = -(-w // bl), -(-h // bl)
-    return bpw, bph
+    return a, wh
 
 
 class ExposureEstimator:
@@ -60,51 +46,44 @@ class ExposureEstimator:
         self.info = None
 
     def _prepare(self, corners, imgs, masks):
+        """-> (ctx, the leading arguments of stx_exposure_feed_ex and stx_exposure_stats, the images' (w, h), what those arguments
+        point into: to be held until the calls are made)"""
         imgs, masks, corners = list(imgs), list(masks), [tuple(int(v) for v in c) for c in corners]
         if not (len(imgs) == len(masks) == len(corners)):
             raise StitchingError("feed needs as many corners, images and masks")
         sizes = []
         for i, (im, mk) in enumerate(zip(imgs, masks)):
-            im, hw = _check_image(im, "image", i)
-            mk, mhw = _check_image(mk, "mask", i)
-            if hw != mhw:
-                raise StitchingError(f"mask {i} is {mhw[1]}x{mhw[0]}, its image {hw[1]}x{hw[0]}")
-            imgs[i], masks[i] = im, mk
-            sizes.append(hw)
-        ctxs = {id(a.ctx): a.ctx for a in imgs + masks if isinstance(a, DeviceImage)}
-        if len(ctxs) > 1:
-            raise StitchingError("device images of more than one context")
-        ctx = next(iter(ctxs.values())) if ctxs else get_context()
-        d_imgs = [as_device(a, ctx) for a in imgs]
-        d_masks = [as_device(a, ctx) for a in masks]
-        n = len(imgs)
-        cs = np.ascontiguousarray(np.asarray(corners, np.int32).reshape(n, 2))
-        return ctx, n, d_imgs, d_masks, cs, sizes
+            imgs[i], wh = _image(im, "image", i)
+            masks[i], mwh = _image(mk, "mask", i)
+            if wh != mwh:
+                raise StitchingError(f"mask {i} is {mwh[0]}x{mwh[1]}, its image {wh[0]}x{wh[1]}")
+            sizes.append(wh)
+        ctx = one_context(imgs + masks)
+        d_imgs, d_masks, cs = [as_device(a, ctx) for a in imgs], [as_device(a, ctx) for a in masks], int_pairs(corners, len(imgs))
+        args = (ctx.handle, _lib.EXPOSURE_KINDS[self.kind], len(imgs), handles(d_imgs), handles(d_masks), ptr(cs), self.block_size)
+        return ctx, args, sizes, (d_imgs, d_masks, cs)  # args holds raw handles and addresses: these keep what they name alive
 
     def feed(self, corners, imgs, masks):
         """Estimate the gains (numpy arrays, cv.UMat-likes or DeviceImages of one context; the images are not modified)."""
         corners, imgs, masks = list(corners), list(imgs), list(masks)
         if not corners and not imgs and not masks:
             return
-        ctx, n, d_imgs, d_masks, cs, sizes = self._prepare(corners, imgs, masks)
-        kind = _lib.EXPOSURE_KINDS[self.kind]
-        ia, ma = (C.c_void_p * n)(*[a._h for a in d_imgs]), (C.c_void_p * n)(*[a._h for a in d_masks])
-        cp = cs.ctypes.data_as(C.POINTER(C.c_int))
-        count = C.c_longlong(0)
+        ctx, args, sizes, alive = self._prepare(corners, imgs, masks)
         solver = -1 if self.solver is None else _lib.EXPOSURE_SOLVERS[self.solver]
-        _lib.check(ctx._lib.stx_exposure_feed_ex(ctx.handle, kind, n, ia, ma, cp, self.block_size, self.nr_feeds, solver, None,
-                                                 C.byref(count), None))
-        out = np.zeros(max(1, count.value), np.float64)
         info = np.zeros(8, np.float64)
-        _lib.check(ctx._lib.stx_exposure_feed_ex(ctx.handle, kind, n, ia, ma, cp, self.block_size, self.nr_feeds, solver,
-                                                 out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(count),
-                                                 info.ctypes.data_as(C.POINTER(C.c_double))))
+
+        def call(count, out):
+            o, i = (None, None) if out is None else (ptr(out), ptr(info))
+            _lib.check(ctx._lib.stx_exposure_feed_ex(*args, self.nr_feeds, solver, o, count, i))
+
+        out, _ = count_then_fill(call, C.c_longlong, lambda k: np.zeros(k, np.float64))
+        del alive  # both calls are made
         names = {v: k for k, v in _lib.EXPOSURE_SOLVERS.items()}
-        self.info = {"units": int(info[0]), "pair_jobs": int(info[1]), "stats_ms": float(info[2]), "solve_ms": float(info[3]),
-                     "solver": names[int(info[4])], "device_lu_ms": float(info[5]), "host_tail_ms": float(info[6]),
-                     "u_nonzeros": int(info[7])}
+        self.info = info_dict(info, [("units", int), ("pair_jobs", int), ("stats_ms", float), ("solve_ms", float),
+                                     ("solver", lambda v: names[int(v)]), ("device_lu_ms", float), ("host_tail_ms", float),
+                                     ("u_nonzeros", int)])
         gains, o = [], 0
-        for h, w in sizes:
+        for w, h in sizes:
             if self.kind == "gain":
                 gains.append(out[o:o + 1].reshape(1, 1).copy())
                 o += 1
@@ -112,7 +91,7 @@ class ExposureEstimator:
                 gains.append(out[o:o + 3].reshape(3, 1).copy())
                 o += 3
             else:
-                bpw, bph = _block_grid(w, h, self.block_size)
+                bpw, bph = -(-w // self.block_size), -(-h // self.block_size)
                 k = bpw * bph * (3 if self.kind == "channel_blocks" else 1)
                 g = out[o:o + k].astype(np.float32)
                 gains.append(g.reshape(bph, bpw, 3) if self.kind == "channel_blocks" else g.reshape(bph, bpw))
@@ -126,18 +105,14 @@ class ExposureEstimator:
     def stats(self, corners, imgs, masks):
         """The first feed's overlap statistics per pair job: (ab (J, 2) int, c (J,) int64, sums (J, 6) float64) — sums are
         {sum_a, sum_b, 0...} for the gain kinds and {B, G, R of a, B, G, R of b} for the channel kinds."""
-        ctx, n, d_imgs, d_masks, cs, _ = self._prepare(corners, imgs, masks)
-        kind = _lib.EXPOSURE_KINDS[self.kind]
-        ia, ma = (C.c_void_p * n)(*[a._h for a in d_imgs]), (C.c_void_p * n)(*[a._h for a in d_masks])
-        cp = cs.ctypes.data_as(C.POINTER(C.c_int))
-        nj = C.c_longlong(0)
-        _lib.check(ctx._lib.stx_exposure_stats(ctx.handle, kind, n, ia, ma, cp, self.block_size, C.byref(nj), None, None, None))
-        J = max(1, nj.value)
-        ab, c, s = np.zeros((J, 2), np.int32), np.zeros(J, np.int64), np.zeros((J, 6), np.float64)
-        _lib.check(ctx._lib.stx_exposure_stats(ctx.handle, kind, n, ia, ma, cp, self.block_size, C.byref(nj),
-                                               ab.ctypes.data_as(C.POINTER(C.c_int)), c.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                               s.ctypes.data_as(C.POINTER(C.c_double))))
-        k = nj.value
+        ctx, args, _, alive = self._prepare(corners, imgs, masks)
+
+        def call(count, out):
+            _lib.check(ctx._lib.stx_exposure_stats(*args, count, *([None] * 3 if out is None else [ptr(a) for a in out])))
+
+        (ab, c, s), k = count_then_fill(call, C.c_longlong, lambda J: (np.zeros((J, 2), np.int32), np.zeros(J, np.int64),
+                                                                       np.zeros((J, 6), np.float64)))
+        del alive  # both calls are made
         return ab[:k], c[:k], s[:k]
 
 
@@ -156,13 +131,9 @@ def solve_gains(m, pairs, n_iij_iji, skip, solver="host", ctx=None):
     L = _lib.lib()
     if solver == "device":
         ctx = ctx or get_context()
-        _lib.check(L.stx_exposure_solve_device(ctx.handle, int(m), pairs.shape[0], pairs.ctypes.data_as(C.POINTER(C.c_int)),
-                                               vals.ctypes.data_as(C.POINTER(C.c_double)), sk.ctypes.data_as(C.POINTER(C.c_ubyte)),
-                                               out.ctypes.data_as(C.POINTER(C.c_double)), None))
+        _lib.check(L.stx_exposure_solve_device(ctx.handle, int(m), pairs.shape[0], ptr(pairs), ptr(vals), ptr(sk), ptr(out), None))
         return out[:m]
-    _lib.check(L.stx_exposure_solve(int(m), pairs.shape[0], pairs.ctypes.data_as(C.POINTER(C.c_int)),
-                                    vals.ctypes.data_as(C.POINTER(C.c_double)), sk.ctypes.data_as(C.POINTER(C.c_ubyte)),
-                                    out.ctypes.data_as(C.POINTER(C.c_double))))
+    _lib.check(L.stx_exposure_solve(int(m), pairs.shape[0], ptr(pairs), ptr(vals), ptr(sk), ptr(out)))
     return out[:m]
 
 
@@ -175,9 +146,7 @@ def lu_solve_device(A, b, ctx=None, want_info=False):
         raise StitchingError("lu_solve_device: A must be n x n with n >= 1 and b hold n values")
     ctx = ctx or get_context()
     x, info = np.zeros(A.shape[0], np.float64), np.zeros(4, np.float64)
-    dp = C.POINTER(C.c_double)
-    _lib.check(ctx._lib.stx_lu_solve_device(ctx.handle, A.shape[0], A.ctypes.data_as(dp), b.ctypes.data_as(dp), x.ctypes.data_as(dp),
-                                            info.ctypes.data_as(dp)))
+    _lib.check(ctx._lib.stx_lu_solve_device(ctx.handle, A.shape[0], ptr(A), ptr(b), ptr(x), ptr(info)))
     if want_info:
-        return x, {"device_lu_ms": float(info[0]), "host_tail_ms": float(info[1]), "u_nonzeros": int(info[2])}
+        return x, info_dict(info, [("device_lu_ms", float), ("host_tail_ms", float), ("u_nonzeros", int)])
     return x

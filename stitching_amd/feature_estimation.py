@@ -8,14 +8,14 @@ byte; DESIGN.md section 15 has the kernels (csrc/stx_features.hip) and the limit
 What depends on floating point is computed here, once, in float64 and handed to the device as integers: the level sizes, the quotas of
 the levels, the direction tables CX / CY and the 36 rotated comparison patterns.
 """
-import ctypes as C
 import functools
 import math
 
 import numpy as np
 
 from . import _lib
-from .device import DeviceImage, as_device, get_context
+from ._marshal import handles, info_dict, one_context, ptr
+from .device import as_device
 from .stitching_error import StitchingError
 
 BINS = 36            # orientation bins of 10 degrees
@@ -159,10 +159,7 @@ class FeatureEstimator:
         if n == 0:
             self.info = {"levels": 0, "candidates": 0, "keypoints": 0}
             return []
-        ctxs = {id(a.ctx): a.ctx for a in imgs + masks if isinstance(a, DeviceImage)}
-        if len(ctxs) > 1:
-            raise StitchingError("device images of more than one context")
-        ctx = next(iter(ctxs.values())) if ctxs else get_context()
+        ctx = one_context(imgs + masks)
         d_imgs = [as_device(a, ctx) for a in imgs]
         d_masks = [None if m is None else as_device(m, ctx) for m in masks]
         ML = self.MAX_LEVELS
@@ -178,16 +175,11 @@ class FeatureEstimator:
         found = np.zeros(n, np.int32)
         lxyb, R, desc = np.zeros((n, cap, 4), np.int32), np.zeros((n, cap), np.int64), np.zeros((n, cap, 32), np.uint8)
         info = np.zeros(4, np.float64)
-        ip = C.POINTER(C.c_int)
-        ia = (C.c_void_p * n)(*[a._h for a in d_imgs])
-        ma = (C.c_void_p * n)(*[None if m is None else m._h for m in d_masks])
         tables, pats = direction_tables(), rotated_patterns()
         _lib.check(ctx._lib.stx_features_detect(
-            ctx.handle, n, ia, ma, self.nfeatures, self.nlevels, self.fast_threshold, counts.ctypes.data_as(ip), wh.ctypes.data_as(ip),
-            quotas.ctypes.data_as(ip), tables.ctypes.data_as(ip), pats.ctypes.data_as(C.POINTER(C.c_byte)), found.ctypes.data_as(ip),
-            lxyb.ctypes.data_as(ip), R.ctypes.data_as(C.POINTER(C.c_longlong)), desc.ctypes.data_as(C.POINTER(C.c_ubyte)),
-            info.ctypes.data_as(C.POINTER(C.c_double))))
-        self.info = {"levels": int(info[0]), "candidates": int(info[1]), "keypoints": int(info[2])}
+            ctx.handle, n, handles(d_imgs), handles(d_masks), self.nfeatures, self.nlevels, self.fast_threshold, ptr(counts), ptr(wh),
+            ptr(quotas), ptr(tables), ptr(pats), ptr(found), ptr(lxyb), ptr(R), ptr(desc), ptr(info)))
+        self.info = info_dict(info, [("levels", int), ("candidates", int), ("keypoints", int)])
         out = []
         for i, a in enumerate(d_imgs):
             k = int(found[i])

@@ -13,12 +13,12 @@ With model="affine" the RANSAC fits a similarity (2 matches a sample) or, with f
 centred — the registration of scans and flat tiles, whose cameras the affine warper applies to raw pixels.  Everything but the hypothesis
 and the refit is shared with the homography; tests/numpy_affine.py is that contract and DESIGN.md section 18 the description.
 """
-import ctypes as C
 import math
 
 import numpy as np
 
 from . import _lib
+from ._marshal import handles, info_dict, ptr
 from .device import get_context
 from .stitching_error import StitchingError
 
@@ -213,19 +213,17 @@ class MatchEstimator:
         matches, mask = np.zeros((max(cap, 1), 3), np.int32), np.zeros(max(cap, 1), np.uint8)
         info = np.zeros(4, np.float64)
         ctx = ctx or get_context()
-        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
-        da = (C.c_void_p * n)(*[d.ctypes.data for d in desc])
-        pa = (C.c_void_p * n)(*[p.ctypes.data for p in pts])
+        # host addresses: the descriptors may be of any dtype (the library refuses what is not u8), so not ptr()
+        da, pa = handles([d.ctypes.data for d in desc]), handles([p.ctypes.data for p in pts])
         t = self.ransac_threshold
-        front = (ctx.handle, n, da, shape.ctypes.data_as(ip), pa, rows.ctypes.data_as(ip), ratio_threshold(self.match_conf), self.range_width,
-                 self.ransac_iters, t * t, self.seed)
-        back = (counts.ctypes.data_as(ip), matches.ctypes.data_as(ip), mask.ctypes.data_as(C.POINTER(C.c_ubyte)), pick.ctypes.data_as(ip),
-                Hs.ctypes.data_as(dp), info.ctypes.data_as(dp))
+        front = (ctx.handle, n, da, ptr(shape), pa, ptr(rows), ratio_threshold(self.match_conf), self.range_width, self.ransac_iters, t * t,
+                 self.seed)
+        back = (ptr(counts), ptr(matches), ptr(mask), ptr(pick), ptr(Hs), ptr(info))
         if self.model == "homography":
             _lib.check(ctx._lib.stx_match_features(*front, *back))
         else:
             _lib.check(ctx._lib.stx_match_features_model(*front, _lib.MATCH_MODELS[self.model], *back))
-        self.info = {"pairs": int(info[0]), "matches": int(info[1]), "device_ms": float(info[2]), "device_ms_with_copy": float(info[3])}
+        self.info = info_dict(info, [("pairs", int), ("matches", int), ("device_ms", float), ("device_ms_with_copy", float)])
         slot = 0
         for k, (i, j) in enumerate(pairs):
             m = int(counts[k])

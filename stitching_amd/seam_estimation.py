@@ -14,40 +14,62 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, config
-from .device import DeviceImage, as_device, get_context, is_foreign_device_array
+from ._marshal import adopt, count_then_fill, handles, host_array, image_spec, info_dict, int_pairs, one_context, ptr
+from .device import DeviceImage, as_device, is_foreign_device_array
 from .stitching_error import StitchingError
 
-
-def _size(a, what, i):
-    """(w, h) and the array (numpy or DeviceImage), without a host copy of device images (a foreign device array becomes a DeviceImage on
-    the device)."""
-    if is_foreign_device_array(a):
-        a = as_device(a)
-    if isinstance(a, DeviceImage):
-        return (a.width, a.height), a
-    if not isinstance(a, np.ndarray) and hasattr(a, "get"):
-        a = a.get()
-    a = np.asarray(a)
-    if a.ndim not in (2, 3):
-        raise StitchingError(f"{what} {i}: expected an HxW or HxWxC array, got shape {a.shape}")
-    return (a.shape[1], a.shape[0]), a
+_INFO = [("pairs", int), ("levels", int), ("device_ms", float), ("device_ms_with_copy", float)]
 
 
 def schedule(corners, sizes):
     """Host only (no GPU): run()'s overlapping pairs and their dependency levels.  -> (pairs (P, 6) int32 rows i, j, x, y, w, h of the
     roi; levels (P,) int32)."""
     n = len(sizes)
-    cs = np.ascontiguousarray(np.asarray(corners, np.int32).reshape(n, 2))
-    ss = np.ascontiguousarray(np.asarray(sizes, np.int32).reshape(n, 2))
-    ip = C.POINTER(C.c_int)
+    cs, ss = int_pairs(corners, n), int_pairs(sizes, n)
     L = _lib.lib()
-    count = C.c_int(0)
-    _lib.check(L.stx_seam_schedule(n, ss.ctypes.data_as(ip), cs.ctypes.data_as(ip), C.byref(count), None, None))
-    pairs = np.zeros((max(1, count.value), 6), np.int32)
-    levels = np.zeros(max(1, count.value), np.int32)
-    _lib.check(L.stx_seam_schedule(n, ss.ctypes.data_as(ip), cs.ctypes.data_as(ip), C.byref(count), pairs.ctypes.data_as(ip),
-                                   levels.ctypes.data_as(ip)))
-    return pairs[:count.value], levels[:count.value]
+
+    def call(count, out):
+        _lib.check(L.stx_seam_schedule(n, ptr(ss), ptr(cs), count, *([None] * 2 if out is None else [ptr(a) for a in out])))
+
+    (pairs, levels), k = count_then_fill(call, C.c_int, lambda P: (np.zeros((P, 6), np.int32), np.zeros(P, np.int32)))
+    return pairs[:k], levels[:k]
+
+
+def _size_only(a, i):
+    """how SeamEstimator reads an image: (w, h), and nothing of it goes to the device"""
+    return image_spec(a, "image", i)[1], None
+
+
+def _find(est, read_image, export, lead, imgs, corners, masks):
+    """find() of both estimators.  read_image(a, i) -> ((w, h), the image whose pixels the export reads, or None: it takes masks alone).
+    The images it returns go to the device, their handles in front of the masks', and decide with the masks whether the results stay
+    there.  lead: the export's arguments between the context and n."""
+    imgs, masks, corners = list(imgs), list(masks), [tuple(int(v) for v in c) for c in corners]
+    if not (len(imgs) == len(masks) == len(corners)):
+        raise StitchingError("find needs as many images, corners and masks")
+    n = len(imgs)
+    if n == 0:
+        est.info = info_dict([0, 0, 0.0, 0.0], _INFO)
+        return []
+    sizes, read = [], []
+    for i in range(n):
+        wh, image = read_image(imgs[i], i)
+        m, mwh, _, _ = image_spec(masks[i], "mask", i)
+        if isinstance(m, np.ndarray) and (m.ndim != 2 or m.dtype != np.uint8):
+            raise StitchingError(f"mask {i}: seam finding needs u8 masks with one channel, got {m.dtype} of shape {m.shape}")
+        if mwh != wh:
+            raise StitchingError(f"mask {i} is {mwh[0]}x{mwh[1]}, its image {wh[0]}x{wh[1]}")
+        masks[i] = m
+        sizes.append(wh)
+        read += [] if image is None else [image]
+    ctx = one_context(imgs + read + masks)  # a DeviceImage counts even where only its size is read
+    resident = config.device_resident() or any(isinstance(a, DeviceImage) for a in read + masks)
+    d_imgs, d_masks = [as_device(a, ctx) for a in read], [as_device(m, ctx) for m in masks]  # alive until the call is made
+    image_handles = [handles(d_imgs)] if d_imgs else []
+    ss, cs, outs, info = int_pairs(sizes, n), int_pairs(corners, n), handles([None] * n), np.zeros(4, np.float64)
+    _lib.check(getattr(ctx._lib, export)(ctx.handle, *lead, n, ptr(ss), ptr(cs), *image_handles, handles(d_masks), outs, ptr(info)))
+    est.info = info_dict(info, _INFO)
+    return adopt(ctx, outs, resident)
 
 
 class SeamEstimator:
@@ -63,53 +85,18 @@ class SeamEstimator:
         """Seam masks for images `imgs` (numpy arrays, cv.UMat-likes or DeviceImages: only their sizes are read) at `corners` with
         u8 masks `masks` (never written).  Returns new masks: DeviceImages when any mask is a DeviceImage or config.device_resident(),
         numpy arrays otherwise."""
-        imgs, masks, corners = list(imgs), list(masks), [tuple(int(v) for v in c) for c in corners]
-        if not (len(imgs) == len(masks) == len(corners)):
-            raise StitchingError("find needs as many images, corners and masks")
-        n = len(imgs)
-        if n == 0:
-            self.info = {"pairs": 0, "levels": 0, "device_ms": 0.0, "device_ms_with_copy": 0.0}
-            return []
-        sizes = []
-        for i in range(n):
-            wh, _ = _size(imgs[i], "image", i)
-            mwh, m = _size(masks[i], "mask", i)
-            if isinstance(m, np.ndarray) and (m.ndim != 2 or m.dtype != np.uint8):
-                raise StitchingError(f"mask {i}: seam finding needs u8 masks with one channel, got {m.dtype} of shape {m.shape}")
-            if mwh != wh:
-                raise StitchingError(f"mask {i} is {mwh[0]}x{mwh[1]}, its image {wh[0]}x{wh[1]}")
-            masks[i] = m
-            sizes.append(wh)
-        ctxs = {id(a.ctx): a.ctx for a in imgs + masks if isinstance(a, DeviceImage)}
-        if len(ctxs) > 1:
-            raise StitchingError("device images of more than one context")
-        ctx = next(iter(ctxs.values())) if ctxs else get_context()
-        resident = config.device_resident() or any(isinstance(m, DeviceImage) for m in masks)
-        d_masks = [as_device(m, ctx) for m in masks]
-        ss = np.ascontiguousarray(np.asarray(sizes, np.int32).reshape(n, 2))
-        cs = np.ascontiguousarray(np.asarray(corners, np.int32).reshape(n, 2))
-        ip = C.POINTER(C.c_int)
-        ma, outs = (C.c_void_p * n)(*[m._h for m in d_masks]), (C.c_void_p * n)()
-        info = np.zeros(4, np.float64)
-        _lib.check(ctx._lib.stx_seam_find(ctx.handle, _lib.SEAM_KINDS[self.kind], n, ss.ctypes.data_as(ip), cs.ctypes.data_as(ip), ma,
-                                          outs, info.ctypes.data_as(C.POINTER(C.c_double))))
-        self.info = {"pairs": int(info[0]), "levels": int(info[1]), "device_ms": float(info[2]), "device_ms_with_copy": float(info[3])}
-        res = [DeviceImage(ctx, C.c_void_p(outs[i])) for i in range(n)]
-        return res if resident else [r.numpy() for r in res]
+        return _find(self, _size_only, "stx_seam_find", (_lib.SEAM_KINDS[self.kind],), imgs, corners, masks)
 
 
 def _color_image(a, i):
     """u8 HxWx3 (numpy or DeviceImage) from what a caller hands a finder: u8 images, or the float32 images with integer values in
     0 .. 255 the reference's SeamFinder.find makes of them (stitching/seam_finder.py:33-35)."""
-    if is_foreign_device_array(a):
-        a = as_device(a)
-    if isinstance(a, DeviceImage):
-        if a.dtype != np.uint8 or a.channels != 3:
+    if isinstance(a, DeviceImage) or is_foreign_device_array(a):
+        a, wh, ch, dt = image_spec(a, "image", i)
+        if dt != np.uint8 or ch != 3:
             raise StitchingError(f"image {i}: colour seams need u8 images with 3 channels, got {a.dtype} of shape {a.shape}")
-        return (a.width, a.height), a
-    if not isinstance(a, np.ndarray) and hasattr(a, "get"):
-        a = a.get()
-    a = np.asarray(a)
+        return wh, a
+    a = host_array(a)  # its own refusal of every shape but HxWx3
     if a.ndim != 3 or a.shape[2] != 3 or a.dtype not in (np.uint8, np.float32):
         raise StitchingError(f"image {i}: colour seams need u8 (or float32 holding 0 .. 255) images of shape HxWx3, got {a.dtype} of "
                              f"shape {a.shape}")
@@ -145,36 +132,4 @@ class ColorSeamEstimator:
         """Seam masks for the u8 BGR images `imgs` (numpy arrays, cv.UMat-likes or DeviceImages; float32 arrays of integers in 0 .. 255
         are cast) at `corners` with u8 masks `masks`; neither is written.  Returns new masks: DeviceImages when any input is a
         DeviceImage or config.device_resident(), numpy arrays otherwise."""
-        imgs, masks, corners = list(imgs), list(masks), [tuple(int(v) for v in c) for c in corners]
-        if not (len(imgs) == len(masks) == len(corners)):
-            raise StitchingError("find needs as many images, corners and masks")
-        n = len(imgs)
-        if n == 0:
-            self.info = {"pairs": 0, "levels": 0, "device_ms": 0.0, "device_ms_with_copy": 0.0}
-            return []
-        sizes = []
-        for i in range(n):
-            wh, imgs[i] = _color_image(imgs[i], i)
-            mwh, m = _size(masks[i], "mask", i)
-            if isinstance(m, np.ndarray) and (m.ndim != 2 or m.dtype != np.uint8):
-                raise StitchingError(f"mask {i}: seam finding needs u8 masks with one channel, got {m.dtype} of shape {m.shape}")
-            if mwh != wh:
-                raise StitchingError(f"mask {i} is {mwh[0]}x{mwh[1]}, its image {wh[0]}x{wh[1]}")
-            masks[i] = m
-            sizes.append(wh)
-        ctxs = {id(a.ctx): a.ctx for a in imgs + masks if isinstance(a, DeviceImage)}
-        if len(ctxs) > 1:
-            raise StitchingError("device images of more than one context")
-        ctx = next(iter(ctxs.values())) if ctxs else get_context()
-        resident = config.device_resident() or any(isinstance(a, DeviceImage) for a in imgs + masks)
-        d_imgs, d_masks = [as_device(a, ctx) for a in imgs], [as_device(m, ctx) for m in masks]
-        ss = np.ascontiguousarray(np.asarray(sizes, np.int32).reshape(n, 2))
-        cs = np.ascontiguousarray(np.asarray(corners, np.int32).reshape(n, 2))
-        ip = C.POINTER(C.c_int)
-        ia, ma, outs = (C.c_void_p * n)(*[a._h for a in d_imgs]), (C.c_void_p * n)(*[m._h for m in d_masks]), (C.c_void_p * n)()
-        info = np.zeros(4, np.float64)
-        _lib.check(ctx._lib.stx_color_seam_find(ctx.handle, n, ss.ctypes.data_as(ip), cs.ctypes.data_as(ip), ia, ma, outs,
-                                                info.ctypes.data_as(C.POINTER(C.c_double))))
-        self.info = {"pairs": int(info[0]), "levels": int(info[1]), "device_ms": float(info[2]), "device_ms_with_copy": float(info[3])}
-        res = [DeviceImage(ctx, C.c_void_p(outs[i])) for i in range(n)]
-        return res if resident else [r.numpy() for r in res]
+        return _find(self, _color_image, "stx_color_seam_find", (), imgs, corners, masks)

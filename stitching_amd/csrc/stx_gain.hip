@@ -15,14 +15,16 @@ using namespace stxd;
 namespace {
 // GainCompensator::apply / ChannelsCompensator::apply: cv::multiply(u8x3 image, double scalar) evaluates in fp32
 // (arithm_op demotes a CV_64F scalar to CV_32F for 8-bit sources) and stores saturate_cast<uchar>(float) = cvRound + clamp
-struct GainK { uint8_t* img; long long stride; int w, h; float g[3]; };
+// dwords: host-proved, the first row and the row pitch are multiples of 4 bytes, so every 4-pixel group starts on a dword.  A view
+// (odd first column, odd pitch) is not: its rows go byte by byte, 4 pixels per lane all the same
+struct GainK { uint8_t* img; long long stride; int w, h; float g[3]; int dwords; };
 __global__ __launch_bounds__(256) void gain_apply_kernel(GainK P)
 {
     const int x4 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;  // 4 pixels = 12 bytes = 3 dwords per lane
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x4 >= P.w || y >= P.h) return;
     uint8_t* row = P.img + (long long)y * P.stride;
-    if (x4 + 4 <= P.w) {
+    if (P.dwords && x4 + 4 <= P.w) {
         uint32_t* q = reinterpret_cast<uint32_t*>(row + (long long)x4 * 3);
         uint32_t d[3] = {q[0], q[1], q[2]}, o[3] = {0, 0, 0};
 #pragma unroll
@@ -33,7 +35,8 @@ __global__ __launch_bounds__(256) void gain_apply_kernel(GainK P)
         }
         q[0] = o[0]; q[1] = o[1]; q[2] = o[2];
     } else {
-        for (int x = x4; x < P.w; x++)
+        const int xe = min(x4 + 4, P.w);
+        for (int x = x4; x < xe; x++)
             for (int c = 0; c < 3; c++) {
                 const float v = stxd::fmul((float)row[x * 3 + c], P.g[c]);
                 row[x * 3 + c] = (uint8_t)min(max(stxd::cv_round(v), 0), 255);
@@ -47,6 +50,7 @@ int stx_launch_gain_apply(stx_ctx* ctx, stx_buf* img, const float g[3])
     GainK K;
     K.img = img->ptr; K.stride = (long long)img->stride; K.w = img->w; K.h = img->h;
     K.g[0] = g[0]; K.g[1] = g[1]; K.g[2] = g[2];
+    K.dwords = ((uintptr_t)img->ptr & 3) == 0 && (img->stride & 3) == 0;
     StxProfScope prof(ctx, "gain_apply", 6.0 * img->w * img->h);
     hipLaunchKernelGGL(gain_apply_kernel, dim3((img->w + 255) / 256, (img->h + 3) / 4), dim3(256), 0, ctx->stream, K);
     return stx_check_launch("gain_apply");

@@ -168,6 +168,16 @@ int stx_buf_from_host_async(stx_ctx* ctx, const void* host, size_t host_stride_b
 int stx_buf_to_host_async(const stx_buf* buf, void* host, size_t host_stride_bytes);
 /* rectangular sub-view sharing the parent's memory (numpy slicing in stitching/cropper.py:150-151) */
 int stx_buf_view(const stx_buf* buf, int x, int y, int w, int h, stx_buf** out);
+/* Source validity masks: which pixels of a frame are picture (a lens' wedges, the corners of a circular fisheye image, a mount in view).
+ * stx_buf_with_validity: a NEW handle onto the same pixels as img (a whole-image view) that carries mask — u8x1 of img's size, same
+ *   context; the handle holds a reference on it, img itself is not changed and mask is never written.  Refused with STX_ERR_INVALID
+ *   before anything is allocated: a null handle, img not u8x3, mask not u8x1, unequal sizes, different contexts, img already carrying a
+ *   mask.  stx_buf_view of such a handle carries the matching view of the mask.
+ * stx_buf_validity: a new handle on the attached mask, or *out = NULL when there is none.
+ * Honoured by stx_warp_batch and stx_warp_image_and_mask where they write masks (see stx_warp_batch); every other entry point reads
+ * the pixels and ignores the mask. */
+int stx_buf_with_validity(const stx_buf* img, const stx_buf* mask_u8x1, stx_buf** out);
+int stx_buf_validity(const stx_buf* buf, stx_buf** out);
 /* info = {w, h, channels, elem, stride_bytes, device} */
 int stx_buf_info(const stx_buf* buf, int64_t info[6]);
 /* device address of the first pixel (for zero-copy consumers, e.g. RCCL strip exchange) */
@@ -228,7 +238,13 @@ int stx_warp_image_and_mask(stx_ctx* ctx, int type, float scale, const float K[9
  *   projector families use no tables and leave the handle empty.  Kept tables belong to given rectangles: rects_xywh, or
  *   STX_WARP_FRESH_ROIS on the first panorama of a rig, whose ROIs become the rects_xywh of the later calls.  A handle belongs to the
  *   context that made it: another context's is refused.  stx_warp_tables_free gives the block back (stream-ordered: warps that read it
- *   may still be in flight). */
+ *   may still be in flight).
+ * validity: a source made by stx_buf_with_validity carries its own mask M, and the warped mask of that image is then
+ *   remapNearest(M, xmap, ymap) with a constant 0 border — the source value at (saturate_cast<short>(cvRound(x)), ... (y)) where both
+ *   indices are inside, 0 elsewhere, cvRound taken of the fp32 coordinate itself — instead of the warp of a 255-filled rectangle.  An
+ *   image without a mask behaves as with a 255-filled one, and a batch may mix both.  The image bytes, the ROIs, out_xywh and the
+ *   tables' record do not depend on the mask; a grey mask comes out grey, and the warped mask counts as binary (stx_buf_flags) when M
+ *   does.  With gain_maps on top the gain runs as the second pass (equal bytes, see above).  M may be a view (its own pitch). */
 #define STX_WARP_FRESH_ROIS 1
 int stx_warp_batch(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s, const stx_buf* const* srcs,
                    const int* rects_xywh, const stx_buf* const* gain_maps_f32, const int* gain_flags, int flags, stx_buf** out_imgs,
@@ -527,6 +543,11 @@ int stx_seam_mask_resize(stx_ctx* ctx, const stx_buf* seam_mask_u8x1, const stx_
 /* stx_resize_linear_exact for n images of unequal sizes (u8x1 and u8x3 mixed, views included) in one launch: the generator loop of
  * Images.resize (stitching/images.py:72-77, stitching/stitcher.py:167-168).  dst_wh = {w, h} per image; outs[i] is byte for byte what
  * stx_resize_linear_exact(srcs[i], w, h) returns.  n <= 0 is STX_ERR_INVALID; a failing call hands nothing out. */
+/* Conservative shrink of source validity masks (u8x1) to the lower resolutions of a pipeline, one launch for the list.  Pixel (x, y) of
+ * the dw x dh result is 255 iff EVERY source pixel in columns [x sw / dw, ((x + 1) sw + dw - 1) / dw) and the rows likewise (integer
+ * divisions) is non-zero, else 0; dw == sw binarises.  Refused (STX_ERR_INVALID, nothing allocated): dw > sw or dh > sh, zero sizes,
+ * inputs that are not u8x1, masks of another context.  The results are binary (stx_buf_flags). */
+int stx_mask_shrink_batch(stx_ctx* ctx, int n, const stx_buf* const* masks_u8x1, const int* dst_wh, stx_buf** outs);
 int stx_resize_linear_exact_batch(stx_ctx* ctx, int n, const stx_buf* const* srcs_u8, const int* dst_wh, stx_buf** outs);
 /* the same for all n images of a panorama (the generator loop stitching/stitcher.py:223-225): one table upload, one dilate
  * and one resize launch per 16 images */

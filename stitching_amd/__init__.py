@@ -12,7 +12,8 @@ from .config import (device_resident, exposure_estimator, exposure_solver, pyrdo
                      set_exposure_estimator, set_exposure_solver, set_pyrdown_mode, set_remap_mode, set_seam_estimator, set_trig_mode,
                      trig_mode)
 from .cropper import Cropper, Rectangle
-from .device import Context, DeviceImage, as_device, device_count, get_context, pinned_empty, set_default_device
+from .device import (Context, DeviceImage, as_device, device_count, get_context, pinned_empty, set_default_device, shrink_masks_all,
+                     with_validity)
 from .exposure_error_compensator import ExposureErrorCompensator
 from .exposure_estimation import ExposureEstimator
 from .feature_detector import FeatureDetector
@@ -34,7 +35,7 @@ from .warper import Warper
 __all__ = [
     "AffineComposer", "Blender", "CameraAdjuster", "CameraEstimator", "CameraParams", "CameraSolver", "ColorSeamEstimator", "ComposePlan", "Composer", "Context", "Cropper", "Rectangle", "DeviceImage", "ExposureErrorCompensator", "ExposureEstimator", "FeatureDetector", "FeatureEstimator", "FeatureMatcher", "ImageFeatures", "Images", "MatchEstimator", "MatchesInfo", "MegapixDownscaler", "MegapixScaler", "StitchingError", "StitchingWarning",
     "SeamEstimator", "SeamFinder", "Subsetter", "Timelapser", "Warper", "WaveCorrector", "resize_linear_exact", "resize_linear_exact_all",
-    "LensMap", "rectify", "rectify_all",
+    "LensMap", "rectify", "rectify_all", "with_validity", "shrink_masks_all",
     "as_device", "emit", "emit_all", "ingest", "ingest_all", "parse_cuda_array_interface", "device_count", "pinned_empty", "device_resident", "get_context", "set_default_device", "set_device_resident", "set_trig_mode", "trig_mode", "set_remap_mode", "remap_mode", "set_pyrdown_mode", "pyrdown_mode",
     "set_exposure_estimator", "exposure_estimator", "set_exposure_solver", "exposure_solver", "set_seam_estimator", "seam_estimator",
 ]

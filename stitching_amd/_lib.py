@@ -102,6 +102,8 @@ PROTOTYPES = {
     "stx_buf_to_host": [_vp, _vp, _z],
     "stx_buf_to_host_async": [_vp, _vp, _z],
     "stx_buf_view": [_vp, _i, _i, _i, _i, _vpp],
+    "stx_buf_with_validity": [_vp, _vp, _vpp],
+    "stx_buf_validity": [_vp, _vpp],
     "stx_buf_info": [_vp, C.POINTER(C.c_int64)],
     "stx_buf_device_ptr": [_vp, _vpp],
     "stx_buf_free": [_vp],
@@ -116,6 +118,7 @@ PROTOTYPES = {
     "stx_block_gain_apply_batch": [_vp, _i, _vpp, _vpp, _ip, _ip],
     "stx_resize_linear_exact": [_vp, _vp, _i, _i, _vpp],
     "stx_resize_linear_exact_batch": [_vp, _i, _vpp, _ip, _vpp],
+    "stx_mask_shrink_batch": [_vp, _i, _vpp, _ip, _vpp],
     "stx_seam_mask_resize": [_vp, _vp, _vp, _vpp],
     "stx_seam_mask_resize_batch": [_vp, _i, _vpp, _vpp, _vpp],
     "stx_seam_mask_resize_batch_sub": [_vp, _i, _vpp, _vpp, _ip, _vpp],

@@ -34,6 +34,7 @@ void stx_buf_release(stx_buf* b)
 {
     if (!b) return;
     if (b->refs.fetch_sub(1) != 1) return;
+    if (b->validity) stx_buf_release(b->validity);
     if (b->parent) stx_buf_release(b->parent);
     else stx_dev_free(b->ctx, b->base);
     delete b;
@@ -135,11 +136,9 @@ STX_EXPORT int stx_buf_to_host_async(const stx_buf* buf, void* host, size_t host
     return buf_to_host(buf, host, host_stride, false);
 }
 
-STX_EXPORT int stx_buf_view(const stx_buf* buf, int x, int y, int w, int h, stx_buf** out)
+// a new handle onto the rectangle (x, y, w, h) of buf's pixels (checked by the caller); holds a reference on buf
+static stx_buf* view_of(const stx_buf* buf, int x, int y, int w, int h)
 {
-    if (!buf || !out) return stx_fail(STX_ERR_INVALID, "null argument");
-    if (x < 0 || y < 0 || w <= 0 || h <= 0 || x + w > buf->w || y + h > buf->h)
-        return stx_fail(STX_ERR_INVALID, "view (%d,%d,%d,%d) outside %dx%d", x, y, w, h, buf->w, buf->h);
     stx_buf* root = const_cast<stx_buf*>(buf);
     stx_buf* v = new stx_buf();
     v->ctx = buf->ctx;
@@ -150,7 +149,40 @@ STX_EXPORT int stx_buf_view(const stx_buf* buf, int x, int y, int w, int h, stx_
     v->parent = root;
     v->mask_binary = buf->mask_binary;
     stx_buf_retain(root);
+    return v;
+}
+
+STX_EXPORT int stx_buf_view(const stx_buf* buf, int x, int y, int w, int h, stx_buf** out)
+{
+    if (!buf || !out) return stx_fail(STX_ERR_INVALID, "null argument");
+    if (x < 0 || y < 0 || w <= 0 || h <= 0 || x + w > buf->w || y + h > buf->h)
+        return stx_fail(STX_ERR_INVALID, "view (%d,%d,%d,%d) outside %dx%d", x, y, w, h, buf->w, buf->h);
+    stx_buf* v = view_of(buf, x, y, w, h);
+    if (buf->validity) v->validity = view_of(buf->validity, x, y, w, h);  // a frame's view carries the matching view of its mask
     *out = v;
+    return STX_OK;
+}
+
+STX_EXPORT int stx_buf_with_validity(const stx_buf* img, const stx_buf* mask, stx_buf** out)
+{
+    if (!img || !mask || !out) return stx_fail(STX_ERR_INVALID, "null argument");
+    if (img->elem != STX_U8 || img->c != 3) return stx_fail(STX_ERR_INVALID, "a validity mask belongs to a u8x3 frame");
+    if (mask->elem != STX_U8 || mask->c != 1) return stx_fail(STX_ERR_INVALID, "a validity mask is u8 with 1 channel");
+    if (mask->w != img->w || mask->h != img->h)
+        return stx_fail(STX_ERR_INVALID, "validity mask of %dx%d on a frame of %dx%d", mask->w, mask->h, img->w, img->h);
+    if (mask->ctx != img->ctx) return stx_fail(STX_ERR_INVALID, "frame and validity mask belong to different contexts");
+    if (img->validity) return stx_fail(STX_ERR_INVALID, "the frame already carries a validity mask");
+    stx_buf* v = view_of(img, 0, 0, img->w, img->h);
+    v->validity = const_cast<stx_buf*>(mask);
+    stx_buf_retain(v->validity);
+    *out = v;
+    return STX_OK;
+}
+
+STX_EXPORT int stx_buf_validity(const stx_buf* buf, stx_buf** out)
+{
+    if (!buf || !out) return stx_fail(STX_ERR_INVALID, "null argument");
+    *out = buf->validity ? view_of(buf->validity, 0, 0, buf->validity->w, buf->validity->h) : nullptr;
     return STX_OK;
 }
 

@@ -205,6 +205,9 @@ struct stx_buf {
     int w = 0, h = 0, c = 0, elem = 0;
     size_t stride = 0;  // bytes
     stx_buf* parent = nullptr;
+    // the validity mask a u8x3 frame carries (stx_buf_with_validity): a u8x1 image of this size, one reference held; read by
+    // stx_warp_batch and stx_warp_image_and_mask alone, never written
+    stx_buf* validity = nullptr;
     int mask_binary = 0;  // 1: a u8x1 image known to hold only 0 and 255 (warped masks; scanned host uploads)
     std::atomic<int> refs{1};
 };
@@ -265,6 +268,8 @@ struct StxWarpLaunch {
     uint8_t* dimg; size_t dimg_stride;    // u8x3 or null
     uint8_t* dmask; size_t dmask_stride;  // u8x1 or null
     int nearest_src;               // 1: out image = nearest sample of a u8x1 source (generic mask warp)
+    // source validity mask (stx_buf_with_validity): u8x1 of sw x sh with its own pitch; the warped mask is its nearest sample.  null: 255
+    const uint8_t* vsrc = nullptr; size_t vstride = 0;
     int debug_maps = 0;            // stx_debug_warp_maps (test hook): dimg / dmask are f32 maps of x / y; 1: the kernel a warp would take, 2: the generic one
     // fused exposure gain (stx_warp_batch with gain_maps): device tables made by stx_launch_gain_rows for this destination rectangle; null: none
     const float* gain_H = nullptr; long long gain_hstride = 0; const void* gain_yt = nullptr; int gain_gh = 0;
@@ -453,6 +458,8 @@ struct StxResizeItem {
     double xscale, yscale;  // 1 / (dw / sw), 1 / (dh / sh) in double, as linear_exact_table takes them
 };
 int stx_launch_resize_exact_batch(stx_ctx* ctx, const StxResizeItem* d_items, int n, int total_tiles, double algo_bytes);
+// conservative shrink of u8x1 validity masks over the same descriptors and tile list (c, xscale, yscale unused)
+int stx_launch_mask_shrink_batch(stx_ctx* ctx, const StxResizeItem* d_items, int n, int total_tiles, double algo_bytes);
 // device frame ingest (stx_ingest.hip; host side in stx_ingest_host.cpp) -----------------------------------------------------------
 // A lane takes STX_INGEST_LANE_PX pixels of a row (RAW: as many 4-byte words of it; a row is then w BYTES), a workgroup 64 lanes x
 // STX_INGEST_ROWS row units; a row unit is two rows of the 4:2:0 formats (one chroma pair serves its 2 x 2 block), one row otherwise.

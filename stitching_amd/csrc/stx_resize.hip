@@ -449,3 +449,42 @@ int stx_launch_resize_exact_batch(stx_ctx* ctx, const StxResizeItem* d_items, in
     hipLaunchKernelGGL(resize_exact_batch_kernel, dim3(total_tiles), dim3(256), 0, ctx->stream, d_items, n);
     return stx_check_launch("resize_linear_exact_batch");
 }
+
+// ---------------------------------------------------------------------------------------------
+// Conservative shrink of source validity masks (stx_mask_shrink_batch): destination pixel (x, y) of a dw x dh result is 255 iff EVERY
+// source pixel of its footprint — columns [x sw / dw, ((x + 1) sw + dw - 1) / dw), rows likewise, integer divisions — is non-zero,
+// else 0: a pixel of the smaller frame counts as picture only where all the pixels it was averaged from are.  Integers only.  The grid
+// is the flat tile list of the batched resize above; a lane owns one destination pixel and walks its footprint (dw <= sw, dh <= sh:
+// never empty, never beyond the source: ((x + 1) sw + dw - 1) / dw <= sw for x + 1 <= dw).
+// ---------------------------------------------------------------------------------------------
+namespace {
+__global__ __launch_bounds__(256) void mask_shrink_batch_kernel(const StxResizeItem* __restrict__ items, int n)
+{
+    const int tile = blockIdx.x;
+    int lo = 0, hi = n - 1;  // the last image whose first tile is <= tile
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (items[mid].tile0 <= tile) lo = mid; else hi = mid - 1;
+    }
+    const StxResizeItem& D = items[lo];
+    const int t = tile - D.tile0, tyi = t / D.tiles_x, txi = t - tyi * D.tiles_x;
+    const int x = txi * STX_RESIZE_TW + (threadIdx.x & 63);
+    const int y = tyi * STX_RESIZE_TH + (threadIdx.x >> 6);
+    if (x >= D.dw || y >= D.dh) return;
+    const int x0 = (int)((long long)x * D.sw / D.dw), x1 = (int)(((long long)(x + 1) * D.sw + D.dw - 1) / D.dw);
+    const int y0 = (int)((long long)y * D.sh / D.dh), y1 = (int)(((long long)(y + 1) * D.sh + D.dh - 1) / D.dh);
+    bool all = true;
+    for (int sy = y0; sy < y1 && all; sy++) {
+        const uint8_t* row = D.src + (long long)sy * D.sstride;
+        for (int sx = x0; sx < x1; sx++) all = all && row[sx] != 0;
+    }
+    D.dst[(long long)y * D.dstride + x] = all ? 255 : 0;
+}
+}  // namespace
+
+int stx_launch_mask_shrink_batch(stx_ctx* ctx, const StxResizeItem* d_items, int n, int total_tiles, double algo_bytes)
+{
+    StxProfScope prof(ctx, "mask_shrink_batch", algo_bytes);
+    hipLaunchKernelGGL(mask_shrink_batch_kernel, dim3(total_tiles), dim3(256), 0, ctx->stream, d_items, n);
+    return stx_check_launch("mask_shrink_batch");
+}

@@ -92,6 +92,45 @@ STX_EXPORT int stx_resize_linear_exact_batch(stx_ctx* ctx, int n, const stx_buf*
     return STX_OK;  // the descriptor block goes back here: stream-ordered reuse
 }
 
+// Source validity masks at the lower resolutions of a pipeline: one launch for the list, everything checked before anything is allocated
+STX_EXPORT int stx_mask_shrink_batch(stx_ctx* ctx, int n, const stx_buf* const* masks, const int* dst_wh, stx_buf** outs)
+{
+    if (!ctx || !masks || !dst_wh || !outs) return stx_fail(STX_ERR_INVALID, "null argument");
+    if (n <= 0) return stx_fail(STX_ERR_INVALID, "shrink of %d masks", n);
+    STX_TRY(stx_set_device(ctx));
+    std::vector<StxResizeItem> items((size_t)n);
+    long long tiles = 0;
+    double bytes = 0.0;
+    for (int i = 0; i < n; i++) {
+        const stx_buf* m = masks[i];
+        if (!m) return stx_fail(STX_ERR_INVALID, "null argument");
+        const int dw = dst_wh[2 * i], dh = dst_wh[2 * i + 1];
+        if (m->elem != STX_U8 || m->c != 1) return stx_fail(STX_ERR_INVALID, "mask %d is not u8x1", i);
+        if (m->ctx != ctx) return stx_fail(STX_ERR_INVALID, "mask %d belongs to another context", i);
+        if (dw <= 0 || dh <= 0) return stx_fail(STX_ERR_INVALID, "mask %d: shrink to %dx%d", i, dw, dh);
+        if (dw > m->w || dh > m->h) return stx_fail(STX_ERR_INVALID, "mask %d: %dx%d is larger than the mask's %dx%d (a shrink only)", i, dw, dh, m->w, m->h);
+        StxResizeItem& K = items[i];
+        K = StxResizeItem{};
+        K.src = m->ptr; K.sstride = (long long)m->stride; K.sw = m->w; K.sh = m->h; K.dw = dw; K.dh = dh; K.c = 1;
+        K.tiles_x = (dw + STX_RESIZE_TW - 1) / STX_RESIZE_TW;
+        K.tile0 = (int)tiles;
+        tiles += (long long)K.tiles_x * ((dh + STX_RESIZE_TH - 1) / STX_RESIZE_TH);
+        if (tiles > 0x7fffffffLL) return stx_fail(STX_ERR_INVALID, "shrink batch of more than 2^31 destination tiles");
+        bytes += (double)m->w * m->h + (double)dw * dh;  // every source pixel once, every result once
+    }
+    std::vector<StxBufRef> dsts((size_t)n);
+    for (int i = 0; i < n; i++) {
+        STX_TRY(stx_buf_new(ctx, items[i].dw, items[i].dh, 1, STX_U8, &dsts[i]));
+        dsts[i]->mask_binary = 1;
+        items[i].dst = dsts[i]->ptr; items[i].dstride = (long long)dsts[i]->stride;
+    }
+    StxDevBlock d_items;
+    STX_TRY(upload_small(ctx, items.data(), items.size() * sizeof(StxResizeItem), &d_items));
+    STX_TRY(stx_launch_mask_shrink_batch(ctx, (const StxResizeItem*)d_items.get(), n, (int)tiles, bytes));
+    for (int i = 0; i < n; i++) outs[i] = dsts[i].release();
+    return STX_OK;  // the descriptor block goes back here: stream-ordered reuse
+}
+
 STX_EXPORT int stx_seam_mask_resize(stx_ctx* ctx, const stx_buf* seam_mask, const stx_buf* final_mask, stx_buf** out)
 {
     if (!ctx || !seam_mask || !final_mask || !out) return stx_fail(STX_ERR_INVALID, "null argument");

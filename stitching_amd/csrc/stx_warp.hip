@@ -348,7 +348,8 @@ __global__ __launch_bounds__(256) void warp_kernel(WarpK P, const float2* __rest
 //                  pixels) into the mirror zone first (13 more ops per axis) — the pitched rows of a multi-row panorama
 //                  have large parts of their ROI there;
 //       generic  : anything else (|32 v| >= 2^21, NaN, divisions that need rescaling): per-tap borderInterpolate.
-// Preconditions (host): source < 2^31 bytes, 2 <= sw, sh <= 32767, no nearest-neighbour source image.
+// Preconditions (host): source < 2^31 bytes, 2 <= sw, sh <= 32767; the nearest-neighbour source of stx_warp(INTER_NEAREST) stays with
+// warp_kernel.  A source validity mask (VALID) < 2^31 bytes with a pitch < 2^24.
 // ---------------------------------------------------------------------------------------------
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -509,13 +510,27 @@ STX_DEV int periodic_axis(int s, int n, int period, float inv_period, int bias)
     return (int)r - 32 * n;
 }
 
+// VALID: the nearest-neighbour sample of a source validity mask (remapNearest, BORDER_CONSTANT 0) for a position the inside test on
+// 32 v has passed: cvRound of the fp32 coordinate ITSELF — not (s + 16) >> 5 of the 1/32 pattern s = cvRound(32 v), which rounds
+// v = k + 31/64 up to k + 1 where cvRound(v) = k.  `in` proves 0 <= cvRound(x) < sw and 0 <= cvRound(y) < sh, so the conversions need
+// no saturation; a position outside reads byte 0 of the mask (always there) and gives 0.  Offsets are 32-bit: the host admits masks
+// below 2^31 bytes with a pitch below 2^24 only (fast_ok), rows < 2^15.
+STX_DEV uint32_t nearest_valid(const STX_GAS uint8_t* msrc, uint32_t msstride, bool in, float x, float y)
+{
+    const uint32_t off = in ? __umul24((uint32_t)(int)rintf(y), msstride) + (uint32_t)(int)rintf(x) : 0u;
+    const uint32_t v = msrc[off];
+    return in ? v : 0u;
+}
+
 // RM: STX_REMAP_* of the image samples (Q15: the fixed-point blend; FLOAT / FLOAT_FMA: the fp32 model — interior wavefronts through
 // blend_float_to_lds, every other wavefront one pixel at a time through sample_float: borders are a minority)
 // GAIN: the warped image leaves multiplied by the block gain of its position (cvRound(p g) saturated, cv::multiply's arithmetic) — applied
 // to the finished bytes on their way from LDS to memory, whatever sampling path made them
 // FLAT: the batch's images share ONE 1-D grid (WarpBatchK::first_wg) instead of a grid of (largest image, 1, images): chosen by the host
 // when the images' tile counts differ (see launch_typed)
-template <int TYPE, bool IMG, bool MASK, bool DBG = false, int RM = STX_REMAP_Q15, bool GAIN = false, bool FLAT = false>
+// VALID (with MASK): some image of the launch carries a source validity mask (WarpK::msrc; null for the others: 255) — every wavefront,
+// interior ones included, writes its mask bytes to LDS: nothing is 255 by construction any more
+template <int TYPE, bool IMG, bool MASK, bool DBG = false, int RM = STX_REMAP_Q15, bool GAIN = false, bool FLAT = false, bool VALID = false>
 __global__ __launch_bounds__(WARP_FW) __attribute__((amdgpu_waves_per_eu(8, 8))) void warp_fast_kernel(WarpBatchK B)
 {
     // which image of the batch this workgroup belongs to: seven scalar compares against the images' first workgroups
@@ -561,6 +576,12 @@ __global__ __launch_bounds__(WARP_FW) __attribute__((amdgpu_waves_per_eu(8, 8)))
                  "+s"(ux_zhi), "+s"(uy_zlo), "+s"(uy_zhi));
     asm volatile("" : "+s"(src_a), "+s"(dimg_a), "+s"(dmask_a), "+s"(dimg_stride), "+s"(dmask_stride), "+s"(sstride), "+s"(colT_a),
                  "+s"(rowT_a));
+    unsigned long long msrc_a = 0ull;
+    uint32_t msstride = 0u;
+    if (MASK && VALID) {
+        msrc_a = (unsigned long long)P.msrc; msstride = (uint32_t)P.msstride;
+        asm volatile("" : "+s"(msrc_a), "+s"(msstride));
+    }
     const STX_GAS v2f* colT = (const STX_GAS v2f*)colT_a;   // scalar base + 32-bit lane offset
     const STX_CAS v4f* rowT = (const STX_CAS v4f*)rowT_a;  // wave-uniform reads: scalar loads
     // XCD-aware tile order: workgroup b runs on XCD b % 8 (observed dispatch rule, used for speed only), and the
@@ -750,6 +771,18 @@ __global__ __launch_bounds__(WARP_FW) __attribute__((amdgpu_waves_per_eu(8, 8)))
                                                                       (j & 1) ? Y[j >> 1].y : Y[j >> 1].x, lpx + 192 * j);
             }
         }
+        if (MASK && VALID) {
+            // the nearest sample of an interior position is inside (above): no test, but the mask's own bytes instead of 255
+            if (msrc_a) {
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    lmk[64 * j] = (uint8_t)nearest_valid((const STX_GAS uint8_t*)msrc_a, msstride, true, (j & 1) ? X[j >> 1].y : X[j >> 1].x,
+                                                         (j & 1) ? Y[j >> 1].y : Y[j >> 1].x);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; j++) lmk[64 * j] = 255;
+            }
+        }
     } else if (RM != STX_REMAP_Q15) {
         const int sw = sw_s, sh = sh_s;
         if (MASK) {
@@ -757,7 +790,11 @@ __global__ __launch_bounds__(WARP_FW) __attribute__((amdgpu_waves_per_eu(8, 8)))
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const bool in = xs[j] >= -16.f && xs[j] < mx32_hi && ys[j] >= -16.f && ys[j] < my32_hi;
-                lmk[64 * j] = in ? 255 : 0;
+                if (VALID && msrc_a)  // (wave-uniform: the image's own mask, or none)
+                    lmk[64 * j] = (uint8_t)nearest_valid((const STX_GAS uint8_t*)msrc_a, msstride, in, (j & 1) ? X[j >> 1].y : X[j >> 1].x,
+                                                         (j & 1) ? Y[j >> 1].y : Y[j >> 1].x);
+                else
+                    lmk[64 * j] = in ? 255 : 0;
             }
         }
         if (IMG) {
@@ -777,7 +814,11 @@ __global__ __launch_bounds__(WARP_FW) __attribute__((amdgpu_waves_per_eu(8, 8)))
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const bool in = xs[j] >= -16.f && xs[j] < mx32_hi && ys[j] >= -16.f && ys[j] < my32_hi;
-                lmk[64 * j] = in ? 255 : 0;
+                if (VALID && msrc_a)  // (wave-uniform: the image's own mask, or none)
+                    lmk[64 * j] = (uint8_t)nearest_valid((const STX_GAS uint8_t*)msrc_a, msstride, in, (j & 1) ? X[j >> 1].y : X[j >> 1].x,
+                                                         (j & 1) ? Y[j >> 1].y : Y[j >> 1].x);
+                else
+                    lmk[64 * j] = in ? 255 : 0;
             }
         }
         if (IMG) {
@@ -873,7 +914,7 @@ __global__ __launch_bounds__(WARP_FW) __attribute__((amdgpu_waves_per_eu(8, 8)))
         if (MASK) {
             STX_GAS uint8_t* base = (STX_GAS uint8_t*)(dmask_a + (unsigned long long)y0 * (unsigned long long)dmask_stride + (unsigned long long)xw);
             *reinterpret_cast<STX_GAS uint32_t*>(base + (__umul24((uint32_t)r, (uint32_t)dmask_stride) + (uint32_t)c * 4u)) =
-                wave_int ? 0xffffffffu : s_mk[wv][4 * it + r][c];
+                wave_int && !VALID ? 0xffffffffu : s_mk[wv][4 * it + r][c];
         }
     } else {
         if (IMG) {
@@ -905,7 +946,7 @@ __global__ __launch_bounds__(WARP_FW) __attribute__((amdgpu_waves_per_eu(8, 8)))
         if (MASK) {
             if (y0 + r < dh && (long long)xw + c * 4 + 4 <= dmask_stride)
                 *reinterpret_cast<uint32_t*>((uint8_t*)dmask_a + (long long)(y0 + r) * dmask_stride + xw + c * 4) =
-                    wave_int ? 0xffffffffu : s_mk[wv][4 * it + r][c];
+                    wave_int && !VALID ? 0xffffffffu : s_mk[wv][4 * it + r][c];
         }
     }
   }
@@ -1194,9 +1235,19 @@ bool fast_ok(const WarpK& K)
     return !K.msrc && K.sw <= 32767 && K.sh <= 32767 && K.sw >= 2 && K.sh >= 2 && (long long)K.sstride * K.sh < (1ll << 31);
 }
 
+// the same for a launch whose msrc may be a source validity mask (nearest: the launch of stx_warp(INTER_NEAREST), where msrc IS the
+// source and warp_kernel stays): the tuned kernel samples the mask through 32-bit offsets and a 24-bit row multiply
+bool fast_ok(const WarpK& K, bool nearest)
+{
+    if (nearest || !K.msrc) return fast_ok(K);
+    WarpK G = K;
+    G.msrc = nullptr;
+    return fast_ok(G) && K.msstride < (1ll << 24) && K.msstride * K.sh < (1ll << 31);
+}
+
 template <int TYPE>
-int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, const char* prof_name, const double* algo_bytes, int dbg,
-                 stx_warp_tables* kept)
+int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, bool nearest, const char* prof_name, const double* algo_bytes,
+                 int dbg, stx_warp_tables* kept)
 {
     hipStream_t s = ctx->stream;
     // per-column / per-row trig tables (a few KB per image, L2 resident), one allocation for the batch, freed in stream order
@@ -1243,7 +1294,7 @@ int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, cons
         WarpBatchK B;
         memset(&B, 0, sizeof(B));
         int max_tab = 0, gx = 0, gy = 0;
-        bool fast = true;
+        bool fast = true, valid = false;  // valid: some image of the launch carries a source validity mask
         double tab_bytes = 0.0, bytes = 0.0;
         for (int i = 0; i < m; i++) {
             const WarpK& K = Ks[base + i];
@@ -1262,8 +1313,9 @@ int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, cons
             max_tab = std::max(max_tab, K.dw + ((K.dh + 3) & ~3));
             gx = std::max(gx, (K.dw + WARP_TW - 1) / WARP_TW);
             gy = std::max(gy, (K.dh + WARP_TH - 1) / WARP_TH);
-            fast = fast && fast_ok(K) && dbg != 2;
-            if (gain && (!fast_ok(K) || dbg))
+            fast = fast && fast_ok(K, nearest) && dbg != 2;
+            valid = valid || (mask && !nearest && K.msrc != nullptr);
+            if (gain && (!fast_ok(K, nearest) || dbg || valid))
                 return stx_fail(STX_ERR_UNSUPPORTED, "a fused gain needs the tuned warp kernel (image %d does not qualify)", base + i);
             tab_bytes += (double)K.dw * sizeof(float2) + (double)K.dh * 5 * sizeof(float);
             bytes += algo_bytes[base + i];
@@ -1312,9 +1364,16 @@ int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, cons
         if (flat) STX_FAST_LAUNCH_K(warp_fast_kernel<TYPE, I, M, false, R, G, true>);     \
         else STX_FAST_LAUNCH_K(warp_fast_kernel<TYPE, I, M, false, R, G, false>);         \
     } while (0)
+// with a validity mask somewhere in the launch: never with a fused gain (stx_warp_batch runs the gain as its second pass then)
+#define STX_FAST_LAUNCH_V(I, R)                                                                  \
+    do {                                                                                         \
+        if (flat) STX_FAST_LAUNCH_K(warp_fast_kernel<TYPE, I, true, false, R, false, true, true>); \
+        else STX_FAST_LAUNCH_K(warp_fast_kernel<TYPE, I, true, false, R, false, false, true>);     \
+    } while (0)
 #define STX_FAST_LAUNCH(I, M, R)                              \
     do {                                                      \
-        if (gain) STX_FAST_LAUNCH_G(I, M, R, true);           \
+        if (M && valid) STX_FAST_LAUNCH_V(I, R);              \
+        else if (gain) STX_FAST_LAUNCH_G(I, M, R, true);      \
         else STX_FAST_LAUNCH_G(I, M, R, false);               \
     } while (0)
 #define STX_FAST_LAUNCH_RM(I, M)                                             \
@@ -1326,7 +1385,9 @@ int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, cons
             if (dbg) STX_FAST_LAUNCH_K(warp_fast_kernel<TYPE, false, false, true>);
             else if (img && mask) STX_FAST_LAUNCH_RM(true, true);
             else if (img) STX_FAST_LAUNCH_RM(true, false);
+            else if (valid) STX_FAST_LAUNCH_V(false, STX_REMAP_Q15);
             else STX_FAST_LAUNCH_G(false, true, STX_REMAP_Q15, false);
+#undef STX_FAST_LAUNCH_V
 #undef STX_FAST_LAUNCH_RM
 #undef STX_FAST_LAUNCH
 #undef STX_FAST_LAUNCH_G
@@ -1396,8 +1457,9 @@ void fill_warpk(const StxWarpLaunch& L, WarpK* Kp, double* bytes)
     const bool img = L.dimg != nullptr, mask = L.dmask != nullptr;
     K.src = img ? L.src : nullptr;
     K.sstride = (long long)L.sstride;
-    K.msrc = L.nearest_src ? L.src : nullptr;
-    K.msstride = (long long)L.sstride;
+    // the nearest-neighbour source: the source itself (stx_warp INTER_NEAREST), else the source's validity mask where a mask is written
+    K.msrc = L.nearest_src ? L.src : (mask && !L.debug_maps ? L.vsrc : nullptr);
+    K.msstride = L.nearest_src ? (long long)L.sstride : (long long)L.vstride;
     K.dimg = L.dimg; K.dimg_stride = (long long)L.dimg_stride;
     K.g_H = img ? L.gain_H : nullptr; K.g_hstride = L.gain_hstride; K.g_yt = reinterpret_cast<const int2*>(L.gain_yt); K.g_gh = L.gain_gh;
     K.dmask = L.dmask; K.dmask_stride = (long long)L.dmask_stride;
@@ -1440,7 +1502,9 @@ void fill_warpk(const StxWarpLaunch& L, WarpK* Kp, double* bytes)
     // plane / affine: z = (kr7 v' + kr6 u') + c8; with kr6 = kr7 = 0 and finite tables (num_ok) that is c8 for every pixel
     K.z_one = K.num_ok && L.proj.family == STX_F_PLANE && K.kr[6] == 0.f && K.kr[7] == 0.f && K.c8 == 1.0f ? 1 : 0;
     // algorithmic bytes: read the source once, write the warped image + mask once
-    *bytes = (img ? 3.0 * L.sw * L.sh + 3.0 * L.dw * L.dh : 0.0) + (mask ? 1.0 * L.dw * L.dh : 0.0);
+    // (+ a validity mask once)
+    *bytes = (img ? 3.0 * L.sw * L.sh + 3.0 * L.dw * L.dh : 0.0) + (mask ? 1.0 * L.dw * L.dh : 0.0) +
+             (K.msrc && !L.nearest_src ? 1.0 * L.sw * L.sh : 0.0);
 }
 
 }  // namespace
@@ -1455,13 +1519,14 @@ int stx_launch_warp_batch(stx_ctx* ctx, const StxWarpLaunch* Ls, int n, stx_warp
     for (int i = 0; i < n; i++) fill_warpk(Ls[i], &Ks[i], &bytes[i]);
     const bool img = Ls[0].dimg != nullptr, mask = Ls[0].dmask != nullptr;
     const int dbg = Ls[0].debug_maps;  // stx_debug_warp_maps: dimg / dmask are the two float maps
+    const bool nearest = Ls[0].nearest_src != 0;  // stx_warp(INTER_NEAREST): a call of one launch
     const char* name = dbg ? "warp_debug_maps" : (img ? (mask ? "warp_img_mask" : "warp_img") : "warp_mask");
     switch (Ls[0].proj.family) {
-    case STX_F_PLANE: return launch_typed<STX_WARP_PLANE>(ctx, Ks.data(), n, img, mask, name, bytes.data(), dbg, kept);
-    case STX_F_CYLINDRICAL: return launch_typed<STX_WARP_CYLINDRICAL>(ctx, Ks.data(), n, img, mask, name, bytes.data(), dbg, kept);
+    case STX_F_PLANE: return launch_typed<STX_WARP_PLANE>(ctx, Ks.data(), n, img, mask, nearest, name, bytes.data(), dbg, kept);
+    case STX_F_CYLINDRICAL: return launch_typed<STX_WARP_CYLINDRICAL>(ctx, Ks.data(), n, img, mask, nearest, name, bytes.data(), dbg, kept);
     case STX_F_SPHERICAL:
     case STX_F_MERCATOR:  // separable like the sphere (row table: warp_tables_kernel)
-        return launch_typed<STX_WARP_SPHERICAL>(ctx, Ks.data(), n, img, mask, name, bytes.data(), dbg, kept);
+        return launch_typed<STX_WARP_SPHERICAL>(ctx, Ks.data(), n, img, mask, nearest, name, bytes.data(), dbg, kept);
     default: return launch_general(ctx, Ks.data(), n, img, mask, name, bytes.data(), dbg);
     }
 }
@@ -1474,7 +1539,7 @@ bool stx_warp_fast_eligible(const StxWarpLaunch& L)
     WarpK K;
     double bytes;
     fill_warpk(L, &K, &bytes);
-    return fast_ok(K) && !L.debug_maps && L.dimg != nullptr;
+    return fast_ok(K, L.nearest_src != 0) && !L.debug_maps && L.dimg != nullptr;
 }
 
 // out_minmax4[i] = {min u, min v, max u, max v} over the border of image i (cyl / spherical)

@@ -304,6 +304,8 @@ static StxWarpLaunch warp_launch(const StxProjector& p, const int* rect, const s
     L.sstride = src ? src->stride : 0;
     L.src_channels = src ? src->c : 0;
     L.nearest_src = 0;
+    // the validity mask the source carries (stx_buf_with_validity) is honoured where a mask is written
+    if (src && src->validity && dmask) { L.vsrc = src->validity->ptr; L.vstride = src->validity->stride; }
     L.dimg = dimg ? dimg->ptr : nullptr; L.dimg_stride = dimg ? dimg->stride : 0;
     L.dmask = dmask ? dmask->ptr : nullptr; L.dmask_stride = dmask ? dmask->stride : 0;
     return L;
@@ -326,7 +328,8 @@ static int warp_impl(stx_ctx* ctx, int type, float scale, const float* K, const 
     StxWarpLaunch L = nearest_src ? warp_launch(p, roi, src, sw, sh, nullptr, bi.get()) : warp_launch(p, roi, src, sw, sh, bi.get(), bm.get());
     L.nearest_src = nearest_src ? 1 : 0;
     STX_TRY(stx_launch_warp(ctx, L));
-    if (bm) bm->mask_binary = 1;  // remapNearest of a 255-filled source with a constant-0 border
+    // remapNearest of a 255-filled source with a constant-0 border; of a validity mask: binary when that is
+    if (bm) bm->mask_binary = L.vsrc ? src->validity->mask_binary : 1;
     if (out_img) *out_img = bi.release();
     if (out_mask) *out_mask = bm.release();
     if (out_xywh) memcpy(out_xywh, roi, 16);
@@ -447,7 +450,8 @@ STX_EXPORT int stx_warp_batch(stx_ctx* ctx, int type, float scale, int n, const 
         static const bool no_fuse = getenv("STITCHING_AMD_NO_GAIN_FUSION") != nullptr;  // diagnostic: A/B against the separate pass
         fused = !no_fuse;
         for (int i = 0; i < n && fused; i++)
-            fused = gain_maps[i]->c == 1 && gain_flags && (gain_flags[i] & STX_GAIN_MAP_BOUNDED) && stx_warp_fast_eligible(Ls[i]) &&
+            // (a validity mask: the tuned kernel has no gain x validity form; this launch runs once per rig, the second pass gives the same bytes)
+            fused = !Ls[i].vsrc && gain_maps[i]->c == 1 && gain_flags && (gain_flags[i] & STX_GAIN_MAP_BOUNDED) && stx_warp_fast_eligible(Ls[i]) &&
                     (size_t)gain_maps[i]->h * (size_t)Ls[i].dw < ((size_t)16 << 20);
         if (fused) {
             std::vector<size_t> offH(n), offY(n);
@@ -472,7 +476,7 @@ STX_EXPORT int stx_warp_batch(stx_ctx* ctx, int type, float scale, int n, const 
     gscratch.reset();  // stream-ordered reuse
     if (gain_maps && !fused) STX_TRY(stx_block_gain_apply_batch(ctx, n, stx_buf_ptrs(bi).data(), gain_maps, sub.data(), gain_flags));
     for (int i = 0; i < n; i++) {
-        if (bm[i]) bm[i]->mask_binary = 1;
+        if (bm[i]) bm[i]->mask_binary = Ls[i].vsrc ? srcs[i]->validity->mask_binary : 1;
         if (out_imgs) out_imgs[i] = bi[i].release();
         if (out_masks) out_masks[i] = bm[i].release();
     }

@@ -224,6 +224,13 @@ class DeviceImage:
         _lib.check(self.ctx._lib.stx_buf_view(self._h, x0, y0, x1 - x0, y1 - y0, C.byref(out)))
         return DeviceImage(self.ctx, out)
 
+    @property
+    def validity(self):
+        """The validity mask this frame carries (with_validity), as a DeviceImage on the same bytes, or None."""
+        out = C.c_void_p()
+        _lib.check(self.ctx._lib.stx_buf_validity(self._h, C.byref(out)))
+        return DeviceImage(self.ctx, out) if out.value else None
+
     def device_ptr(self):
         p = C.c_void_p()
         _lib.check(self.ctx._lib.stx_buf_device_ptr(self._h, C.byref(p)))
@@ -256,6 +263,38 @@ class DeviceImage:
 
     def __repr__(self):
         return f"DeviceImage(shape={self.shape}, dtype={self.dtype}, device={self.ctx.device})"
+
+
+def with_validity(frame, mask, ctx=None):
+    """`frame` (HxWx3 uint8) with the validity mask `mask` (HxW uint8: non-zero = picture) attached: a new DeviceImage onto the same
+    pixels (stx_buf_with_validity) whose `.validity` is the mask.  Warper.warp_images_and_masks / warp_image_and_mask, StitchJob and
+    Composer then produce warped masks that are the nearest-neighbour warp of `mask` instead of a warped rectangle; everything else
+    reads the pixels and ignores the mask.  Host arrays are uploaded (masks of 0 / 255 are recognised as binary on the way), foreign
+    device arrays are copied on the device (as_device); slicing the result keeps the matching slice of the mask.  `frame` itself is
+    not changed."""
+    f = as_device(frame, ctx)
+    m = as_device(mask, f.ctx)
+    out = C.c_void_p()
+    _lib.check(f.ctx._lib.stx_buf_with_validity(f._h, m._h, C.byref(out)))
+    return DeviceImage(f.ctx, out)
+
+
+def shrink_masks_all(masks, sizes, ctx=None):
+    """Validity masks at a lower resolution, conservatively: pixel (x, y) of a (w, h) result is 255 where EVERY pixel of the mask in
+    columns [x sw // w, ((x + 1) sw + w - 1) // w) and the rows likewise is non-zero, else 0 (stx_mask_shrink_batch: one launch for the
+    list).  sizes: (w, h) per mask, none larger than its mask; equal sizes binarise.  Returns DeviceImages."""
+    masks = [as_device(m, ctx) for m in masks]
+    sizes = [(int(s[0]), int(s[1])) for s in sizes]
+    if len(masks) != len(sizes):
+        raise StitchingError(f"{len(masks)} masks and {len(sizes)} sizes")
+    n = len(masks)
+    if n == 0:
+        return []
+    c = masks[0].ctx
+    wh = (C.c_int * (2 * n))(*[v for s in sizes for v in s])
+    h_src, h_out = (C.c_void_p * n)(*[m._h for m in masks]), (C.c_void_p * n)()
+    _lib.check(c._lib.stx_mask_shrink_batch(c.handle, n, h_src, wh, h_out))
+    return [DeviceImage(c, C.c_void_p(h_out[i])) for i in range(n)]
 
 
 def is_foreign_device_array(a):

@@ -490,6 +490,9 @@ class ShardedStitchJob:
         self.ctx = ctx or get_context()
         self.rank, self.world = int(rank), int(world)
         self.frames = [as_device(f, self.ctx) for f in frames]
+        if any(f.validity is not None for f in self.frames):
+            raise StitchingError("ShardedStitchJob takes no frames with a validity mask (with_validity): source masks are not carried "
+                                 "through the sharded blend; use StitchJob")
         self.cameras = list(cameras)
         self.all_cameras = list(all_cameras)
         n = len(self.all_cameras)

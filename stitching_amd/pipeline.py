@@ -15,7 +15,7 @@ import numpy as np
 from . import _lib, config
 from .blender import Blender
 from .cropper import Cropper
-from .device import as_device, get_context, is_foreign_device_array
+from .device import as_device, get_context, is_foreign_device_array, shrink_masks_all, with_validity
 from .exposure_error_compensator import ExposureErrorCompensator
 from .images import Images
 from .rectify import lens_list, rectify_all
@@ -131,10 +131,19 @@ def rig_key(cam_bytes, camera_aspect, warper_type, scale, sizes, blender_type, n
             tuple(modes), crop)
 
 
-def masks_belong_to_job(feed_masks, seam_masks):
+class OwnedMasks(list):
+    """Source validity masks the library made itself (a lens's masks, their shrunk copies): device images nobody else writes, so a job
+    that is given them may keep its geometry as with host arrays."""
+
+
+def masks_belong_to_job(feed_masks, seam_masks, source_masks=None):
     """The condition of geometry reuse (and of the seam-cell crops): no mask input, or host arrays — the job uploaded its own copies.  A
-    mask given as a device array may be rewritten by its owner between runs."""
+    mask given as a device array may be rewritten by its owner between runs.  source_masks: the frames' validity masks likewise — host
+    arrays (None entries: no mask) or OwnedMasks belong to the job."""
     given = feed_masks if feed_masks is not None else seam_masks
+    if source_masks is not None and not isinstance(source_masks, OwnedMasks) and \
+            not all(m is None or isinstance(m, np.ndarray) for m in source_masks):
+        return False
     return given is None or all(isinstance(m, np.ndarray) for m in given)
 
 
@@ -148,7 +157,7 @@ class StitchJob:
 
     def __init__(self, frames, cameras, warper_type="spherical", blender_type="multiband", num_bands=None,
                  blend_strength=Blender.DEFAULT_BLEND_STRENGTH, ctx=None, async_upload=False, feed_masks=None, seam_masks=None,
-                 crop_to_masks=True, compensator=None, cropper=None, crop_aspect=1, camera_aspect=1, reuse_geometry=True):
+                 crop_to_masks=True, compensator=None, cropper=None, crop_aspect=1, camera_aspect=1, reuse_geometry=True, source_masks=None):
         """async_upload: numpy frames in page-locked memory (pinned_empty) are only queued for upload; they must stay
         untouched until ctx.sync() (a streaming caller alternates two contexts).
         feed_masks: final-resolution u8 masks fed to the blender instead of the warped masks (seam masks already at the
@@ -173,12 +182,23 @@ class StitchJob:
         keeps it under rig_key(...); a later run with an equal key warps the images alone into the kept rectangles, feeds the kept masks
         and builds its pyramids without their weight half — the same bytes, made once.  A key that differs (Warper.set_scale with other
         cameras, a process-wide arithmetic mode, ...) drops the kept state, and that run is a first run.  Only where every mask input
-        belongs to the job (masks_belong_to_job); jobs with device-array masks, and reuse_geometry=False, redo everything every run."""
+        belongs to the job (masks_belong_to_job); jobs with device-array masks, and reuse_geometry=False, redo everything every run.
+        source_masks: one validity mask per frame (u8, the frame's size, non-zero = picture; None entries: none): the warped masks are
+        the nearest-neighbour warps of these instead of warped rectangles (with_validity) — whatever the job then
+        does with warped masks (feeding, SeamFinder.resize) sees them.  Attached once, and again to the frames of set_frames /
+        run(frames=).  ROIs, the blender's rectangle and view_rects do not change: a source mask changes what is inside a warped mask,
+        never its rectangle.  Host arrays belong to the job; device arrays of the caller turn reuse_geometry off."""
         cropper, crop_aspect = _split_cropper(cropper, crop_aspect)
         if len(frames) != len(cameras) or not frames:
             raise StitchingError("need one camera per frame and at least one frame")
         self.ctx = ctx or get_context()
         self.frames = [as_device(f, self.ctx, wait=not async_upload) for f in frames]
+        self.source_masks = None
+        if source_masks is not None:
+            if len(source_masks) != len(self.frames):
+                raise StitchingError(f"{len(source_masks)} source masks for {len(self.frames)} frames")
+            self.source_masks = [None if m is None else as_device(m, self.ctx) for m in source_masks]
+            self.frames = self._with_source_masks(self.frames)
         self.cameras = list(cameras)
         self.sizes = [(f.width, f.height) for f in self.frames]
         self.warper = Warper(warper_type, ctx=self.ctx)
@@ -200,11 +220,15 @@ class StitchJob:
         if crop_to_masks and given is not None and all(isinstance(m, np.ndarray) for m in given):
             self._mask_cols = [mask_box(m) for m in given]
         self._crop_cache = None
-        self.reuse_geometry = bool(reuse_geometry) and masks_belong_to_job(feed_masks, seam_masks)
+        self.reuse_geometry = bool(reuse_geometry) and masks_belong_to_job(feed_masks, seam_masks, source_masks)
         self._geometry = None
         self.last_reused = self.last_weights_adopted = False  # of the last run: kept geometry used / weight pyramids adopted by its blender
         self.feed_masks = None if feed_masks is None else [as_device(m, self.ctx) for m in feed_masks]
         self.seam_masks = None if seam_masks is None else [as_device(m, self.ctx) for m in seam_masks]
+
+    def _with_source_masks(self, frames):
+        """the job's validity masks on (new) frames: new handles, the frames' own are not changed"""
+        return [f if m is None else with_validity(f, m) for f, m in zip(frames, self.source_masks)]
 
     @property
     def source_pixels(self):
@@ -239,6 +263,8 @@ class StitchJob:
         if got != [tuple(z) for z in self.sizes]:
             raise StitchingError(f"the job was made for frames of sizes {self.sizes}, got {got}: same rig, same sizes")
         self.frames = [as_device(f, self.ctx) for f in frames]
+        if self.source_masks is not None:
+            self.frames = self._with_source_masks(self.frames)
 
     def release_geometry(self):
         """Drop what the job keeps between runs (masks, weight pyramids: see the class docstring); the next run is a first run."""
@@ -400,7 +426,7 @@ def _seam_mask_input(m):
 
 
 def compose(frames, cameras, warper_type="spherical", blender_type="multiband", blend_strength=Blender.DEFAULT_BLEND_STRENGTH,
-            compensator=None, seam_masks=None, ctx=None, cropper=None, crop_aspect=1, camera_aspect=1):
+            compensator=None, seam_masks=None, ctx=None, cropper=None, crop_aspect=1, camera_aspect=1, source_masks=None):
     """The final-resolution half of Stitcher.stitch (stitching/stitcher.py:117-128) with every intermediate in HBM:
 
         warp_final_resolution_imgs / masks   (:119-121, Warper)            -> one batched warp
@@ -413,6 +439,7 @@ def compose(frames, cameras, warper_type="spherical", blender_type="multiband", 
     `cropper`: a prepared Cropper with `crop_aspect` its lir_aspect (or the pair of both): crop_final_resolution (:119-121) — only the
     cropper's rectangles are warped (StitchJob); compensator gains and seam masks then belong to the cropped images.
     `camera_aspect`: the size of the frames relative to the images the cameras were estimated on.
+    `source_masks`: one validity mask per frame (or None entries), see StitchJob.
     Returns device-resident (panorama u8x3, mask u8)."""
     ctx = ctx or get_context()
     cropper, crop_aspect = _split_cropper(cropper, crop_aspect)
@@ -421,19 +448,20 @@ def compose(frames, cameras, warper_type="spherical", blender_type="multiband", 
             seam_masks = [_seam_mask_input(m) for m in seam_masks]
         return StitchJob(frames, cameras, warper_type=warper_type, blender_type=blender_type, blend_strength=blend_strength, ctx=ctx,
                          seam_masks=seam_masks, compensator=compensator, cropper=cropper, crop_aspect=crop_aspect,
-                         camera_aspect=camera_aspect).run()
+                         camera_aspect=camera_aspect, source_masks=source_masks).run()
     if seam_masks is not None and blender_type == "multiband":
         # nothing between the warp and the blender needs whole images (the gain of a pixel depends on its position alone): warp,
         # compensate and feed only what the seam cells can reach
         return StitchJob(frames, cameras, warper_type=warper_type, blender_type=blender_type, blend_strength=blend_strength, ctx=ctx,
                          seam_masks=[_seam_mask_input(m) for m in seam_masks], compensator=compensator,
-                         camera_aspect=camera_aspect).run()
+                         camera_aspect=camera_aspect, source_masks=source_masks).run()
     prev = config.device_resident()
     config.set_device_resident(True)
     try:
         warper = Warper(warper_type, ctx=ctx)
         warper.set_scale(cameras)
-        imgs, masks, rois = warper.warp_images_and_masks([as_device(f, ctx) for f in frames], cameras, camera_aspect, compensator=compensator)
+        imgs, masks, rois = warper.warp_images_and_masks([as_device(f, ctx) for f in frames], cameras, camera_aspect, compensator=compensator,
+                                                         source_masks=source_masks)
         corners, sizes = [r[0:2] for r in rois], [r[2:4] for r in rois]
         if seam_masks is not None:
             masks = SeamFinder.resize_all(seam_masks, masks)
@@ -452,8 +480,10 @@ class ComposePlan:
     cameras): Composer.run(plan, images=new_frames).  The plan also carries the StitchJob of its final-resolution half, which keeps the
     rig's masks and weight pyramids between runs (StitchJob's memory note; `plan.job.release_geometry()` gives them back)."""
 
-    def __init__(self, images, frames, cameras, warper_scale, cropper, compensator, seam_masks, seam_masks_host, low_corners, low_sizes):
+    def __init__(self, images, frames, cameras, warper_scale, cropper, compensator, seam_masks, seam_masks_host, low_corners, low_sizes,
+                 source_masks=None):
         self.images, self.frames, self.cameras, self.warper_scale = images, frames, list(cameras), warper_scale
+        self.source_masks = source_masks  # the frames' validity masks at the frames' size (device; OwnedMasks where they are the plan's own), or None
         self.cropper, self.compensator, self.seam_masks, self.seam_masks_host = cropper, compensator, seam_masks, seam_masks_host
         self.low_corners, self.low_sizes = low_corners, low_sizes
         self.frame_sizes = images.sizes
@@ -530,20 +560,58 @@ class Composer:
     def _ctx(self):
         return self.ctx or get_context()
 
-    def prepare(self, images, cameras, lenses=None):
+    @staticmethod
+    def _source_masks(source_masks, n, ctx, lens_masks=None):
+        """source_masks= of prepare / stitch -> None, or the device masks (None entries: no mask): OwnedMasks where they are the
+        library's own copies (host arrays uploaded here, a lens's masks), a plain list where a caller's device array is among them"""
+        if source_masks is None:
+            return None
+        if isinstance(source_masks, str):
+            if source_masks != "lens":
+                raise StitchingError(f"source_masks={source_masks!r}: a list of masks, or \"lens\"")
+            if lens_masks is None:
+                raise StitchingError("source_masks=\"lens\" needs lenses: the masks are those of the rectification")
+            return OwnedMasks(lens_masks)
+        source_masks = list(source_masks)
+        if len(source_masks) != n:
+            raise StitchingError(f"{len(source_masks)} source masks for {n} images")
+        own = masks_belong_to_job(None, None, source_masks)
+        dev = [None if m is None else as_device(m, ctx) for m in source_masks]
+        return OwnedMasks(dev) if own else dev
+
+    @staticmethod
+    def _shrunk(source_masks, sizes):
+        """the masks at `sizes` (w, h): conservatively shrunk where a size is smaller than its mask, the mask itself where it is equal"""
+        todo = [i for i, (m, z) in enumerate(zip(source_masks, sizes)) if m is not None and (m.width, m.height) != tuple(z)]
+        out = list(source_masks)
+        if todo:
+            for i, m in zip(todo, shrink_masks_all([source_masks[i] for i in todo], [sizes[i] for i in todo])):
+                out[i] = m
+        return OwnedMasks(out) if isinstance(source_masks, OwnedMasks) else out
+
+    def prepare(self, images, cameras, lenses=None, source_masks=None):
         """The low-resolution half -> ComposePlan.  The host waits for the device where a result decides what is launched next: the ROI
         pass of the warp, the cropper's rectangle, the gain solve (and the read-back of the seam masks for the multi-band blender's
         seam-cell crops).  lenses: one LensMap per image, or one for all — the images are then distorted frames and are rectified
-        first (stitching_amd.rectify); the plan is prepared from, and keeps, the rectified frames."""
+        first (stitching_amd.rectify); the plan is prepared from, and keeps, the rectified frames.
+        source_masks: one validity mask per image at the image's size (of the RECTIFIED image with lenses; None entries: none), or
+        "lens" (needs lenses): the masks of the rectification itself, which keep a lens's black wedges out of the panorama.  The
+        masks are shrunk conservatively to the LOW size and ride on the low-resolution frames, so that the cropper, the gain
+        estimation and the seam finder see them through the warped masks; the plan keeps them for the final-resolution half.  A user's
+        masks and a lens's are not combined."""
         frames, cameras = list(images), list(cameras)
         if lenses is not None:
             lenses = lens_list(lenses, len(frames))
         st, ctx = self.settings, self._ctx()
         if len(frames) != len(cameras):
             raise StitchingError("need one camera per image")
-        if lenses is not None:
+        lens_masks = None
+        if isinstance(source_masks, str) and source_masks == "lens" and lenses is not None:
+            frames, lens_masks = rectify_all(frames, lenses, masks=True, ctx=ctx)
+        elif lenses is not None:
             frames = rectify_all(frames, lenses, ctx=ctx)
         frames = [as_device(f, ctx) for f in frames]  # on THIS context: every later stage follows its images' context
+        source_masks = self._source_masks(source_masks, len(frames), ctx, lens_masks)
         imgs_obj = Images.of(frames, st["medium_megapix"], st["low_megapix"], st["final_megapix"])
         R = Images.Resolution
         prev = config.device_resident()
@@ -554,7 +622,8 @@ class Composer:
             warper = Warper(st["warper_type"], ctx=ctx)
             warper.set_scale(cameras)
             aspect = imgs_obj.get_ratio(R.MEDIUM, R.LOW)
-            imgs, masks, rois = warper.warp_images_and_masks(low, cameras, aspect)
+            low_masks = None if source_masks is None else self._shrunk(source_masks, [(f.width, f.height) for f in low])
+            imgs, masks, rois = warper.warp_images_and_masks(low, cameras, aspect, source_masks=low_masks)
             corners, sizes = [r[0:2] for r in rois], [r[2:4] for r in rois]
             cropper = Cropper(st["crop"])
             cropper.prepare(imgs, masks, corners, sizes)
@@ -575,7 +644,8 @@ class Composer:
                 host = [m.numpy() for m in seam_masks]
         finally:
             config.set_device_resident(prev)
-        return ComposePlan(imgs_obj, frames, cameras, warper.scale, cropper, compensator, seam_masks, host, corners, sizes)
+        return ComposePlan(imgs_obj, frames, cameras, warper.scale, cropper, compensator, seam_masks, host, corners, sizes,
+                           source_masks=source_masks)
 
     def run(self, plan, images=None, lenses=None):
         """The final-resolution half on a plan: `images` None -> the frames the plan was prepared from, else new frames of the same rig
@@ -605,22 +675,25 @@ class Composer:
                                  blend_strength=st["blend_strength"], ctx=ctx,
                                  seam_masks=plan.seam_masks_host if plan.seam_masks_host is not None else plan.seam_masks,
                                  compensator=plan.compensator, cropper=plan.cropper, crop_aspect=plan.lir_aspect,
-                                 camera_aspect=plan.camera_aspect)
+                                 camera_aspect=plan.camera_aspect,
+                                 source_masks=None if plan.source_masks is None else
+                                 self._shrunk(plan.source_masks, [(f.width, f.height) for f in final]))
             plan.job_key = job_key
             return plan.job.run()
         return plan.job.run(frames=final)
 
-    def compose(self, images, cameras, lenses=None):
-        """prepare + run -> the panorama (device-resident u8x3), as Stitcher.stitch returns it; lenses: see `prepare`"""
-        pano, _ = self.run(self.prepare(images, cameras, lenses=lenses))
+    def compose(self, images, cameras, lenses=None, source_masks=None):
+        """prepare + run -> the panorama (device-resident u8x3), as Stitcher.stitch returns it; lenses, source_masks: see `prepare`"""
+        pano, _ = self.run(self.prepare(images, cameras, lenses=lenses, source_masks=source_masks))
         return pano
 
-    def stitch(self, images, feature_estimator=None, match_estimator=None, camera_solver=None, lenses=None):
+    def stitch(self, images, feature_estimator=None, match_estimator=None, camera_solver=None, lenses=None, source_masks=None):
         """Frames in, panorama out (device-resident u8x3), with no cv2 and no cameras supplied: the registration half of Stitcher.stitch
         (stitching/stitcher.py:99-105) by the project's own estimators — resize to MEDIUM on the device, FeatureEstimator.detect,
         MatchEstimator.match, CameraSolver.register — then `compose` on the images registration kept.  The three objects default to
         their classes' defaults.  `self.registration` keeps the indices of the images kept, their cameras and the solver's info.
-        lenses: one LensMap per image, or one for all: registration and composition then see the rectified frames."""
+        lenses: one LensMap per image, or one for all: registration and composition then see the rectified frames.
+        source_masks: as in `prepare`; shrunk to the MEDIUM size they also keep the feature detector off what is not picture."""
         from .camera_estimation import CameraSolver
         from .feature_estimation import FeatureEstimator
         from .match_estimation import MatchEstimator
@@ -629,9 +702,13 @@ class Composer:
             images = list(images)
             lenses = lens_list(lenses, len(images))
         st, ctx = self.settings, self._ctx()
-        if lenses is not None:
+        lens_masks = None
+        if isinstance(source_masks, str) and source_masks == "lens" and lenses is not None:
+            images, lens_masks = rectify_all(images, lenses, masks=True, ctx=ctx)
+        elif lenses is not None:
             images = rectify_all(images, lenses, ctx=ctx)
         frames = [as_device(f, ctx) for f in images]
+        source_masks = self._source_masks(source_masks, len(frames), ctx, lens_masks)
         if len(frames) < 2:
             raise StitchingError("stitching needs at least two images")
         feature_estimator = feature_estimator or FeatureEstimator()
@@ -644,11 +721,15 @@ class Composer:
             medium = list(imgs_obj.resize(Images.Resolution.MEDIUM))
         finally:
             config.set_device_resident(prev)
-        features = feature_estimator.detect(medium)
+        if source_masks is None:
+            features = feature_estimator.detect(medium)
+        else:
+            features = feature_estimator.detect(medium, self._shrunk(source_masks, [(f.width, f.height) for f in medium]))
         matches = match_estimator.match(features, ctx=ctx)
         indices, cameras = camera_solver.register(features, matches, ctx=ctx)
         self.registration = {"indices": list(indices), "cameras": cameras, "info": camera_solver.info}
-        return self.compose([frames[i] for i in indices], cameras)
+        kept = None if source_masks is None else type(source_masks)(source_masks[i] for i in indices)
+        return self.compose([frames[i] for i in indices], cameras, source_masks=kept)
 
 
 class AffineComposer(Composer):

@@ -12,7 +12,7 @@ from statistics import median
 import numpy as np
 
 from . import _lib, config
-from .device import DeviceImage, as_device, get_context
+from .device import DeviceImage, as_device, get_context, with_validity
 from .stitching_error import StitchingError
 
 _TYPE_IDS = _lib.WARP_TYPE_IDS
@@ -172,7 +172,8 @@ class Warper:
     # ------------------------------------------------------------------ back-end extras
     def warp_image_and_mask(self, img, camera, aspect=1):
         """Fused form of warp_image + create_and_warp_mask for one camera: the backward map is
-        evaluated once.  Returns (warped_image, warped_mask, (x, y, w, h))."""
+        evaluated once.  Returns (warped_image, warped_mask, (x, y, w, h)).  A frame that carries a validity mask (with_validity) gets
+        the nearest-neighbour warp of that mask instead of a warped rectangle."""
         ctx = self._ctx()
         src = self._source(img, ctx)
         K, R = self._K_R(camera, aspect)
@@ -182,7 +183,7 @@ class Warper:
         return (self._result(DeviceImage(ctx, oi)), self._result(DeviceImage(ctx, om)), tuple(int(v) for v in roi))
 
     def warp_images_and_masks(self, imgs, cameras, aspect=1, rects=None, compensator=None, with_rois=False, camera_arrays=None, masks=True,
-                              tables=None):
+                              tables=None, source_masks=None, images=True):
         """Batched form of warp_images + create_and_warp_masks (stitching/warper.py:39-41, 54-56) for a list of
         images: one ROI pass, one table launch and one remap launch for all of them (stx_warp_batch).
         Returns (warped_images, warped_masks, rois).
@@ -197,9 +198,18 @@ class Warper:
         masks=False (with rects): the images alone — no mask is written, None comes back in their place (a caller that kept the masks
         of an earlier call with the same cameras and rectangles: StitchJob).
         tables (with rects or with_rois): a WarpTables — the typed projectors' column / row tables are kept in it from call to call; the library
-        compares what they depend on and makes them again where anything differs (`tables` of stx_warp_batch)."""
+        compares what they depend on and makes them again where anything differs (`tables` of stx_warp_batch).
+        source_masks: validity masks of the frames (HxW uint8, non-zero = picture; None entries allowed): the warped mask of such a frame is
+        the nearest-neighbour warp of its mask (0 outside the frame) instead of a warped rectangle — lens wedges, fisheye corners, a mount
+        in view.  Attached with with_validity; frames that already carry a mask need nothing.  Images, ROIs and rectangles do not change.
+        images=False: the masks alone — no image is written, None comes back in their place (the mask-only launch of stx_warp_batch)."""
         ctx = self._ctx()
         srcs = [self._source(img, ctx) for img in imgs]
+        if source_masks is not None:
+            source_masks = list(source_masks)
+            if len(source_masks) != len(srcs):
+                raise StitchingError(f"{len(source_masks)} source masks for {len(srcs)} images")
+            srcs = [s if m is None else with_validity(s, m) for s, m in zip(srcs, source_masks)]
         cameras = list(cameras)
         n = min(len(srcs), len(cameras))
         if n == 0:
@@ -211,6 +221,10 @@ class Warper:
             if rects is None:
                 raise StitchingError("masks=False needs rects: the rectangles of the call that made the masks")
             h_mask = None
+        if not images:
+            if not masks or compensator is not None:
+                raise StitchingError("images=False needs masks and no compensator: nothing else is left to write")
+            h_img = None
         if tables is not None and rects is None and not with_rois:
             raise StitchingError("tables= needs rects or with_rois: kept tables belong to given rectangles")
         blocks = compensator is not None and compensator.compensator_type in ("gain_blocks", "channel_blocks")
@@ -230,6 +244,8 @@ class Warper:
         _lib.check(ctx._lib.stx_warp_batch(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src, rects_p, gain_maps,
                                            gain_flags, flags, h_img, h_mask, rois.ctypes.data_as(ip),
                                            None if tables is None else tables._ref(ctx)))
+        if h_img is None:
+            return None, [self._result(DeviceImage(ctx, C.c_void_p(h_mask[i]))) for i in range(n)], [tuple(int(v) for v in r) for r in rois]
         d_imgs = [DeviceImage(ctx, C.c_void_p(h_img[i])) for i in range(n)]
         if compensator is not None:  # "gain" / "channel" (one launch per image) or "no": after the warp
             prev = config.device_resident()

@@ -82,7 +82,8 @@ STX_DEV pk16 pk_splat(unsigned short v) { pk16 r = {v, v}; return r; }
 // v_perm that builds the pair anyway (UpSel: two registers made once per image and lane) — no select, no second candidate:
 // 3 VALU per window (round 2: 7).  The two shorts in front of a plane's first row are read and never used: every plane this
 // is called on has >= 4 readable bytes in front.
-struct UpRow { uint32_t A0, B0, A1, B1, A2; };  // (c0,c1) (c1,c2) (c2,c3) (c3,c4) (c4,c5)
+// The pair registers of one window row: A0 = (c0,c1), A1 = (c2,c3), A2 = (c4,c5); B0 = (c1,c2) and B1 = (c3,c4) are the halves in between,
+// alignbit(A1, A0, 16) and alignbit(A2, A1, 16) — also at an edge: A0 = (c2,c1) keeps c1 in its high half, A2 = (c4,c4) keeps c4 in its low.
 struct UpSel { uint32_t a0, a2; };
 // window dwords (x,c0) (c1,c2) (c3,c4) (c5,x); v_perm(hi, lo, sel): selector bytes 0-3 pick from `lo`, 4-7 from `hi`
 STX_DEV UpSel up_sel(bool left_edge, bool right_edge)
@@ -91,19 +92,6 @@ STX_DEV UpSel up_sel(bool left_edge, bool right_edge)
     s.a0 = left_edge ? 0x05040706u : 0x05040302u;   // perm(w.y, w.x): (c2,c1) at the left edge, else (c0,c1)
     s.a2 = right_edge ? 0x03020302u : 0x05040302u;  // perm(w.w, w.z): (c4,c4) at the right edge, else (c4,c5)
     return s;
-}
-// row: first sample of the plane's row (wave-uniform); boff: byte offset of sample cx in the row (2 cx)
-STX_DEV UpRow up_row_window(const STX_GAS short* __restrict__ row, uint32_t boff, UpSel sel)
-{
-    const STX_GAS char* q = reinterpret_cast<const STX_GAS char*>(row) + (size_t)boff;
-    const v4u w = *reinterpret_cast<const STX_GAS v4u_a4*>(q - 4);  // (x,c0) (c1,c2) (c3,c4) (c5,x)
-    UpRow r;
-    r.B0 = w.y;
-    r.B1 = w.z;
-    r.A1 = __builtin_amdgcn_alignbit(w.z, w.y, 16);
-    r.A0 = __builtin_amdgcn_perm(w.y, w.x, sel.a0);
-    r.A2 = __builtin_amdgcn_perm(w.w, w.z, sel.a2);
-    return r;
 }
 
 // pyrUp_'s row rule (up_idx: -1 -> 1, or 0 when there is one row; n -> n - 1) for i >= -1, as scalar-unit arithmetic
@@ -135,18 +123,6 @@ STX_DEV UpSel up_sel_u8(bool left_edge, bool right_edge)
     s.a2 = right_edge ? 0x0c030c03u : 0x0c040c03u;  // perm(d2, d1): (c4, c4) at the right edge, else (c4, c5)
     return s;
 }
-STX_DEV UpRow up_row_window_u8(const STX_GAS uint8_t* __restrict__ row, uint32_t boff, UpSel sel)
-{
-    const STX_GAS uint8_t* q = row + (size_t)boff;
-    const v3u w = *reinterpret_cast<const STX_GAS v3u_a4*>(q - 4);
-    UpRow r;
-    r.A0 = __builtin_amdgcn_perm(w.y, w.x, sel.a0);
-    r.B0 = __builtin_amdgcn_perm(w.y, w.y, 0x0c010c00u);
-    r.A1 = __builtin_amdgcn_perm(w.y, w.y, 0x0c020c01u);
-    r.B1 = __builtin_amdgcn_perm(w.y, w.y, 0x0c030c02u);
-    r.A2 = __builtin_amdgcn_perm(w.z, w.y, sel.a2);
-    return r;
-}
 STX_DEV const STX_GAS uint8_t* row_ptr_s(const STX_GAS uint8_t* plane, int r, uint32_t stride)
 {
     const unsigned long long a = (unsigned long long)(plane + (size_t)((uint32_t)r * stride));
@@ -167,34 +143,49 @@ STX_DEV void up_patch_pk_load(const STX_GAS uint8_t* __restrict__ plane, uint32_
 #pragma unroll
     for (int r = 0; r < 3; r++) w[r] = *reinterpret_cast<const STX_GAS v3u_a4*>(row_ptr_s(plane, rr[r], stride) + (size_t)boff - 4);
 }
-STX_DEV UpRow up_row_of_u8(v3u w, UpSel sel)
+// Rows before columns: the filter is separable and everything in front of the final shift is an integer sum, so the three window rows
+// are combined first — VE = r0 + 6 r1 + r2 (output row 2 cy) and VO = r1 + r2 (row 2 cy + 1; the factor 4 is in the shift) on the three
+// pair registers of each row — and the horizontal 1-6-1 / 1-1 taps then run on the two combined rows instead of on three window rows.
+// Building a pair register is a selection of 16-bit halves, the edge selectors of UpSel included, and commutes with lane-wise sums: the
+// B pairs are taken from the combined A registers.  The rounding constants ride along: VE + 4 is + 32 under 1-6-1 and + 8 under 1-1,
+// VO + 1 is + 8 and + 2 — the constants of pyrUp_ in front of >> 6, >> 4, >> 4, >> 2.  9 v_perm + 15 + 4 + 12 + 8 VALU (columns first: 61).
+// Bounds (the total sums are those of the other order): VE <= 8 * 255 + 4 = 2044 and HE(VE) <= 64 * 255 + 32 = 16 352: an unsigned half.
+template <class V>  // pk16 or pk16s: two 16-bit lanes
+struct UpComb { V e[3], o[3]; };  // VE, VO of the pair registers A0, A1, A2
+template <class V>
+STX_DEV V up_between(V hi, V lo)  // (lo.high half, hi.low half)
 {
-    UpRow r;
-    r.A0 = __builtin_amdgcn_perm(w.y, w.x, sel.a0);
-    r.B0 = __builtin_amdgcn_perm(w.y, w.y, 0x0c010c00u);
-    r.A1 = __builtin_amdgcn_perm(w.y, w.y, 0x0c020c01u);
-    r.B1 = __builtin_amdgcn_perm(w.y, w.y, 0x0c030c02u);
-    r.A2 = __builtin_amdgcn_perm(w.z, w.y, sel.a2);
-    return r;
+    return __builtin_bit_cast(V, __builtin_amdgcn_alignbit(__builtin_bit_cast(uint32_t, hi), __builtin_bit_cast(uint32_t, lo), 16));
+}
+template <class V>
+STX_DEV void up_patch_columns(const UpComb<V>& C, V up[2][4])
+{
+    const V k6 = {6, 6};
+    const V eB[2] = {up_between(C.e[1], C.e[0]), up_between(C.e[2], C.e[1])}, oB[2] = {up_between(C.o[1], C.o[0]), up_between(C.o[2], C.o[1])};
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        up[0][k] = (C.e[k] + eB[k] * k6 + C.e[k + 1]) >> V{6, 6};  // c[j] + 6 c[j+1] + c[j+2], j = 2k, 2k + 1
+        up[0][2 + k] = (eB[k] + C.e[k + 1]) >> V{4, 4};            // c[j+1] + c[j+2]
+        up[1][k] = (C.o[k] + oB[k] * k6 + C.o[k + 1]) >> V{4, 4};
+        up[1][2 + k] = (oB[k] + C.o[k + 1]) >> V{2, 2};
+    }
 }
 STX_DEV void up_patch_pk_math(const v3u (&w)[3], UpSel sel, pk16 up[2][4])
 {
-    pk16 HE[3][2], HO[3][2];
+    pk16 A[3][3];
 #pragma unroll
     for (int r = 0; r < 3; r++) {
-        const UpRow t = up_row_of_u8(w[r], sel);
-        HE[r][0] = pk(t.A0) + pk(t.B0) * pk_splat(6) + pk(t.A1);            // c[j] + 6 c[j+1] + c[j+2], j = 0,1
-        HE[r][1] = pk(t.A1) + pk(t.B1) * pk_splat(6) + pk(t.A2);            // j = 2,3
-        HO[r][0] = pk(t.B0) + pk(t.A1);                                     // c[j+1] + c[j+2] (the factor 4 is folded below)
-        HO[r][1] = pk(t.B1) + pk(t.A2);
+        A[r][0] = pk(__builtin_amdgcn_perm(w[r].y, w[r].x, sel.a0));
+        A[r][1] = pk(__builtin_amdgcn_perm(w[r].y, w[r].y, 0x0c020c01u));
+        A[r][2] = pk(__builtin_amdgcn_perm(w[r].z, w[r].y, sel.a2));
     }
+    UpComb<pk16> C;
 #pragma unroll
-    for (int k = 0; k < 2; k++) {
-        up[0][k] = (HE[0][k] + HE[1][k] * pk_splat(6) + HE[2][k] + pk_splat(32)) >> pk_splat(6);
-        up[0][2 + k] = (HO[0][k] + HO[1][k] * pk_splat(6) + HO[2][k] + pk_splat(8)) >> pk_splat(4);
-        up[1][k] = (HE[1][k] + HE[2][k] + pk_splat(8)) >> pk_splat(4);
-        up[1][2 + k] = (HO[1][k] + HO[2][k] + pk_splat(2)) >> pk_splat(2);
+    for (int j = 0; j < 3; j++) {
+        C.e[j] = A[1][j] * pk_splat(6) + A[0][j] + A[2][j] + pk_splat(4);
+        C.o[j] = A[1][j] + A[2][j] + pk_splat(1);
     }
+    up_patch_columns(C, up);
 }
 STX_DEV void up_patch_pk(const STX_GAS uint8_t* __restrict__ plane, uint32_t stride, int ch, uint32_t boff, int cy, UpSel sel, pk16 up[2][4])
 {
@@ -1585,34 +1576,29 @@ STX_DEV void up_patch_pks_load(const STX_GAS short* __restrict__ plane, uint32_t
     for (int r = 0; r < 3; r++)
         w[r] = *reinterpret_cast<const STX_GAS v4u_a4*>(reinterpret_cast<const STX_GAS char*>(row_ptr_s(plane, rr[r], stride)) + (size_t)boff - 4);
 }
+// Rows before columns as up_patch_pk_math; the range test stays on the selected taps of every row.  Bounds: taps in [-500, 500] give
+// |VE| <= 8 * 500 + 4 and |HE(VE)| <= 64 * 500 + 32 = 32 032: a signed half.  The limit must not be widened.
 STX_DEV bool up_patch_pks_math(const v4u (&w)[3], UpSel sel, pk16s up[2][4])
 {
-    pk16s HE[3][2], HO[3][2];
+    pk16s A[3][3];
     pk16 worst = pk_splat(0);
 #pragma unroll
-    for (int r = 0; r < 3; r++) {
-        UpRow t;  // up_row_window's five registers from the window (x,c0) (c1,c2) (c3,c4) (c5,x)
-        t.B0 = w[r].y;
-        t.B1 = w[r].z;
-        t.A1 = __builtin_amdgcn_alignbit(w[r].z, w[r].y, 16);
-        t.A0 = __builtin_amdgcn_perm(w[r].y, w[r].x, sel.a0);
-        t.A2 = __builtin_amdgcn_perm(w[r].w, w[r].z, sel.a2);
-        worst = __builtin_elementwise_max(worst, pk(t.A0) + pk_splat(500));
-        worst = __builtin_elementwise_max(worst, pk(t.A1) + pk_splat(500));
-        worst = __builtin_elementwise_max(worst, pk(t.A2) + pk_splat(500));
-        HE[r][0] = pks(t.A0) + pks(t.B0) * pks_splat(6) + pks(t.A1);
-        HE[r][1] = pks(t.A1) + pks(t.B1) * pks_splat(6) + pks(t.A2);
-        HO[r][0] = pks(t.B0) + pks(t.A1);
-        HO[r][1] = pks(t.B1) + pks(t.A2);
+    for (int r = 0; r < 3; r++) {  // from the window (x,c0) (c1,c2) (c3,c4) (c5,x)
+        const uint32_t a0 = __builtin_amdgcn_perm(w[r].y, w[r].x, sel.a0), a1 = __builtin_amdgcn_alignbit(w[r].z, w[r].y, 16),
+                       a2 = __builtin_amdgcn_perm(w[r].w, w[r].z, sel.a2);
+        worst = __builtin_elementwise_max(worst, pk(a0) + pk_splat(500));
+        worst = __builtin_elementwise_max(worst, pk(a1) + pk_splat(500));
+        worst = __builtin_elementwise_max(worst, pk(a2) + pk_splat(500));
+        A[r][0] = pks(a0); A[r][1] = pks(a1); A[r][2] = pks(a2);
     }
     if (unpk(__builtin_elementwise_min(worst, pk_splat(1000))) != unpk(worst)) return false;
+    UpComb<pk16s> C;
 #pragma unroll
-    for (int k = 0; k < 2; k++) {
-        up[0][k] = (HE[0][k] + HE[1][k] * pks_splat(6) + HE[2][k] + pks_splat(32)) >> pks_splat(6);
-        up[0][2 + k] = (HO[0][k] + HO[1][k] * pks_splat(6) + HO[2][k] + pks_splat(8)) >> pks_splat(4);
-        up[1][k] = (HE[1][k] + HE[2][k] + pks_splat(8)) >> pks_splat(4);
-        up[1][2 + k] = (HO[1][k] + HO[2][k] + pks_splat(2)) >> pks_splat(2);
+    for (int j = 0; j < 3; j++) {
+        C.e[j] = A[1][j] * pks_splat(6) + A[0][j] + A[2][j] + pks_splat(4);
+        C.o[j] = A[1][j] + A[2][j] + pks_splat(1);
     }
+    up_patch_columns(C, up);
     return true;
 }
 STX_DEV bool up_patch_pks(const STX_GAS short* __restrict__ plane, uint32_t stride, int ch, uint32_t boff, int cy, UpSel sel, pk16s up[2][4])
@@ -1799,6 +1785,30 @@ STX_DEV void level0_epilogue_pk(const MbLevelK& P, int X0, int Y0, uint32_t (&ac
     }
 }
 
+// What level0_epilogue_pk<false, true> stores for a lane no image covers — zero panorama bytes, a zero mask where one is asked for, zero
+// int16 rows — without its normalisation, its nine window loads and the collapse (the REPLAY instantiations, where the rig's cover word
+// says so before anything is loaded).  Level 0 only: a level >= 1 adds pyrUp of the coarser level to uncovered samples.
+STX_DEV void level0_store_uncovered(const MbLevelK& P, int X0, int Y0)
+{
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        const int y = Y0 + r;
+        if (y >= P.y1) break;
+        const int oy = y - P.pano_y0, ox = X0 - P.pano_x0;
+        uint32_t* po = reinterpret_cast<uint32_t*>(P.pano + (long long)oy * P.pano_stride + (long long)ox * 3);
+        *reinterpret_cast<uint2*>(po) = make_uint2(0u, 0u);
+        *reinterpret_cast<uint2*>(po + 2) = make_uint2(0u, 0u);
+        *reinterpret_cast<uint2*>(po + 4) = make_uint2(0u, 0u);
+        if (P.pmask) *reinterpret_cast<uint2*>(P.pmask + (long long)oy * P.pmask_stride + ox) = make_uint2(0u, 0u);
+        if (P.pano16) {
+            uint32_t* p16 = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(P.pano16) + (long long)oy * P.pano16_stride + (long long)ox * 6);
+            *reinterpret_cast<uint4*>(p16) = make_uint4(0u, 0u, 0u, 0u);
+            *reinterpret_cast<uint4*>(p16 + 4) = make_uint4(0u, 0u, 0u, 0u);
+            *reinterpret_cast<uint4*>(p16 + 8) = make_uint4(0u, 0u, 0u, 0u);
+        }
+    }
+}
+
 // DEFER (masks that may be grey, MbLevelK::defer_list): the packed arithmetic is exact for a lane as long as every mask byte under its
 // 8 x 2 patch is 0 or 255, whatever the other lanes of the wavefront see — so the kernel runs as it is, a lane notes "grey byte seen" (a
 // byte is 0 / 255 iff it equals its sign bit replicated), and at the end such a lane queues its patch for the fp32-weight pass instead of
@@ -1825,11 +1835,12 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(L0_W
         cntb[r][0] = cntb[r][1] = 0;
     }
     uint32_t grey_seen = 0u;  // DEFER: non-zero once a mask byte under this lane was neither 0 nor 255
+    bool uncovered = false;   // REPLAY: the rig's cover word names no image under this wavefront (wave-uniform)
 
     // every wavefront finds the images under ITS two rows with one ballot (no LDS list, no barrier)
     for (int base = 0; base < (REPLAY ? 1 : P.n_images); base += 64) {
         unsigned long long todo;
-        if (REPLAY) todo = mb_cover_word(P, tile_tx, Y0);
+        if (REPLAY) uncovered = (todo = mb_cover_word(P, tile_tx, Y0)) == 0ull;
         else todo = __ballot(mb_tile_hit<true, CONTRIB>(P.images, P.n_images, 0, tile_x, Y0, base + (tid & 63)));
         while (todo) {
             const int k = base + (int)__builtin_ctzll(todo);
@@ -1940,6 +1951,10 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(L0_W
         }
     }
     if (!active) return;
+    if (REPLAY && uncovered) {  // every count is 0 and the epilogue's `keep` would clear every value: nothing to load, nothing to sum
+        level0_store_uncovered(P, X0, Y0);
+        return;
+    }
     if (DEFER) {
         // one atomic per wavefront that holds deferred lanes, on the counter of this workgroup's segment of the queue
         const bool mine = grey_seen != 0u;

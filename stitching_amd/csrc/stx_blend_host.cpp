@@ -201,7 +201,7 @@ static int mb_feed(stx_blender* b, const stx_buf* img, const stx_buf* mask, int 
         const long long gs = (long long)align_up((size_t)lw, im.g_u8 ? 64 : 32), ws = (long long)align_up((size_t)lw, 16);
         void* g = nullptr;
         // MB_FRONT_PAD in front, 64 bytes behind: the pyrUp tap windows of the gather kernels start up to 4 bytes in front of a row
-        // and end up to 8 bytes behind its last sample (up_row_window / up_row_window_u8)
+        // and end up to 8 bytes behind its last sample (up_patch_pks_load / up_patch_pk_load)
         STX_TRY(stx_dev_alloc(ctx, MB_FRONT_PAD + (size_t)gs * lh * 3 * (im.g_u8 ? 1 : sizeof(short)) + 64, &g));
         b->pyr_allocs.push_back(g);
         im.g[i] = (short*)((uint8_t*)g + MB_FRONT_PAD); im.g_stride[i] = gs; im.g_plane[i] = gs * lh;

@@ -665,6 +665,32 @@ int stx_lens_map_free(stx_lens_map* map);
 int stx_rectify(stx_ctx* ctx, int n, const stx_buf* const* srcs, const stx_lens_map* const* maps, int border, int want_masks,
                 stx_buf** out_imgs, stx_buf** out_masks);
 
+/* ---- the warp through the lens: distorted frames -> warped images in ONE resampling ---------------------------
+ * stx_rectify followed by stx_warp_batch resamples every frame twice.  stx_warp_lens_batch keeps the warp's own fp32 backward map — for
+ * all 16 warper types, bit for bit what stx_warp_batch computes — and puts another sampler behind it: the map's 1/32-px position in the
+ * RECTIFIED (pinhole) frame goes through the camera's lens map and four taps of the DISTORTED frame are blended.  tests/numpy_lens_warp.py
+ * is the contract, byte for byte.  Per destination pixel with map value (x, y), integer only after the first step:
+ *   sx = cvRound(32 x), sy = cvRound(32 y) (as remap; NaN and anything outside int32: INT_MIN);
+ *   qx = clip(sx, 0, 32 (W - 1)), qy = clip(sy, 0, 32 (H - 1)), W x H the map's dst_w x dst_h: a replicate border in the pinhole frame;
+ *   cell (qx >> 9, qy >> 9), nodes N00 N10 / N01 N11, ax = qx & 511, ay = qy & 511, per coordinate in int32:
+ *     L0 = ((512 - ax) N00 + ax N10 + 256) >> 9, L1 likewise from N01, N11 (Q6);  q = ((512 - ay) L0 + ay L1 + 512) >> 10 (Q5, floor);
+ *   i = q >> 5, f = q & 31; the taps (ix, iy) .. (ix + 1, iy + 1) at indices CLAMPED into the source, always;
+ *   out = (w00 p00 + w10 p10 + w01 p01 + w11 p11 + 512) >> 10 per channel, the weights of stx_rectify.
+ * |q / 32 - B| <= 1/32 px, B the exact bilinear interpolation of the unrounded node coordinates at (qx / 32, qy / 32).  With an identity
+ * lens map the result is stx_warp_batch's image wherever that one's taps are not reflected ones.
+ *
+ * K, R and the rectangles belong to the rectified frame (the map's dst_w x dst_h); srcs[i] is the map's src_w x src_h distorted frame
+ * (u8x3, crop views included).  Images only: warped masks do not depend on pixel values, stx_warp_batch (out_imgs null) over the
+ * rectified sizes makes them.  rects_xywh null: the ROIs of stx_warp_rois over the rectified sizes; out_xywh (or null) receives the
+ * rectangles used.  tables (or null) as in stx_warp_batch: a kept handle means no table kernel on later calls of the same rig; the
+ * per-pixel projector families leave it empty.  More images than one launch takes go in groups.  The trig mode is honoured (it acts on
+ * the map only).  Refused with STX_ERR_INVALID before anything is allocated or launched, the context stays usable: null handles, a
+ * source that is not u8x3 or whose size is not the map's source size, a map, buffer or tables handle of another context, a source that
+ * spans 2^31 bytes or has a pitch of 2^24, a rectangle with a non-positive side, a remap mode other than STX_REMAP_Q15 (the sampler has
+ * one arithmetic). */
+int stx_warp_lens_batch(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s, const stx_buf* const* srcs,
+                        const stx_lens_map* const* maps, const int* rects_xywh, stx_buf** out_imgs, int* out_xywh, stx_warp_tables** tables);
+
 /* ---- sharded multi-band blending: one process per GPU, one stx_blender per rank ------------------
  * No counterpart in the reference (it is single process, stitching/stitcher.py:247-254).  Every rank
  * prepares the same roi; rank g produces the columns [x0, x1) of the panorama (stx_blend_set_band).

@@ -184,6 +184,7 @@ PROTOTYPES = {
     "stx_lens_map_create": [_vp, _i, _i, _i, _i, _i, _i, _ip, _vpp],
     "stx_lens_map_free": [_vp],
     "stx_rectify": [_vp, _i, _vpp, _vpp, _i, _i, _vpp, _vpp],
+    "stx_warp_lens_batch": [_vp, _i, _f, _i, _fp, _fp, _vpp, _vpp, _ip, _vpp, _ip, _vpp],
     # include/stitching_amd_debug.h: test hooks, never called by the package's classes
     "stx_debug_warp_maps": [_vp, _i, _f, _fp, _fp, _i, _i, _i, _ip, _vpp, _vpp, _ip],
     "stx_debug_feather_dist_cap": [],

@@ -289,6 +289,15 @@ struct stx_warp_tables {
 };
 int stx_launch_warp(stx_ctx* ctx, const StxWarpLaunch& L);
 int stx_launch_warp_batch(stx_ctx* ctx, const StxWarpLaunch* Ls, int n, stx_warp_tables* kept = nullptr);
+// The warp through the lens (stx_warp_lens_batch): what its sampler reads, a kernel argument of its own next to the projector's —
+// the nodes of the camera's lens grid (stx_lens_map: nx per row, Q6) over the rectified w x h, and the distorted u8x3 source.
+struct StxLensK {
+    const int2* nodes; int nx;
+    int w, h;  // the rectified frame: what the projector's K, R and the clip of the map's positions belong to
+    const uint8_t* src; int spitch; int sw, sh;
+};
+// Ls[i]: the projector and the destination rectangle with sw x sh the RECTIFIED size, an image and no mask, no source (lens[i] has it)
+int stx_launch_warp_lens_batch(stx_ctx* ctx, const StxWarpLaunch* Ls, const StxLensK* lens, int n, stx_warp_tables* kept);
 int stx_launch_roi_minmax(stx_ctx* ctx, int n, const StxProjector* projs, const int* sizes_wh, float* out_minmax4);
 
 // multi-band -------------------------------------------------------------------------------------

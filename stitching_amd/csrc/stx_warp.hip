@@ -1098,6 +1098,169 @@ __global__ __launch_bounds__(256) void warp_general_kernel(WarpK P)
 }
 
 // ---------------------------------------------------------------------------------------------
+// The warp through the lens (stx_warp_lens_batch; tests/numpy_lens_warp.py is the contract, byte for byte): the
+// one-pixel-per-lane kernels above with another sampler behind the same fp32 map.  The map's 1/32-px position in the RECTIFIED frame is
+// clipped into it, taken through the camera's lens grid (the nodes of a stx_lens_map: one every 16 rectified pixels, Q6) in two rounded
+// stages, and the four taps of the DISTORTED frame are read at clamped indices and blended as the rectify kernel blends them.  Images
+// only: the warped masks do not depend on pixel values and come from the kernels above.
+// ---------------------------------------------------------------------------------------------
+// the taps (x, x + 1) of one row of a u8x3 image at byte offset a from the 4-aligned base, each in the low 24 bits of its word: the
+// aligned words around them, shifted into place (load6; stx_rectify.hip states how far the words reach and why that is inside the image's
+// allocation)
+STX_DEV void lens_taps(const STX_GAS uint8_t* base, uint32_t a, uint32_t& t0, uint32_t& t1)
+{
+    const STX_GAS uint32_t* q = reinterpret_cast<const STX_GAS uint32_t*>(base + (a & ~3u));
+    const uint32_t d0 = q[0], d1 = q[1], d2 = q[2];
+    const uint32_t l = __builtin_amdgcn_alignbyte(d1, d0, a), h = __builtin_amdgcn_alignbyte(d2, d1, a);  // bytes 0 .. 3 and 4 .. 7 from a
+    t0 = l & 0xffffffu;
+    t1 = __builtin_amdgcn_alignbyte(h, l, 3u) & 0xffffffu;
+}
+
+// one axis of the lens grid: position a (0 .. 511) between two Q6 values, rounded to Q6.  (512 - a) n0 + a n1 = 512 n0 + a (n1 - n0):
+// |n| <= 2^21 (stx_lens_map_create), so |n1 - n0| <= 2^22 fits the signed 24-bit multiply where (512 - a) n0 does not, and the sum is
+// the same integer, at most 2^30 in magnitude
+STX_DEV int lens_lerp9(int n0, int n1, int a) { return ((n0 << 9) + __mul24(a, n1 - n0) + 256) >> 9; }
+
+STX_DEV uint32_t sample_lens(const StxLensK& L, float x, float yy)
+{
+    const int qx = min(max(cv_round(fmul(x, 32.f)), 0), 32 * (L.w - 1)), qy = min(max(cv_round(fmul(yy, 32.f)), 0), 32 * (L.h - 1));
+    const int ax = qx & 511, ay = qy & 511;
+    // cell (qx >> 9, qy >> 9) <= ((w - 1) / 16, (h - 1) / 16): its four nodes exist (nx = (w + 15) / 16 + 1).  Neighbouring lanes share cells.
+    const int2* nd = L.nodes + (__mul24(qy >> 9, L.nx) + (qx >> 9));
+    const int2 n00 = nd[0], n10 = nd[1], n01 = nd[L.nx], n11 = nd[L.nx + 1];
+    const int l0x = lens_lerp9(n00.x, n10.x, ax), l1x = lens_lerp9(n01.x, n11.x, ax);
+    const int l0y = lens_lerp9(n00.y, n10.y, ax), l1y = lens_lerp9(n01.y, n11.y, ax);
+    // ((512 - ay) L0 + ay L1 + 512) >> 10: Q5 (|L| <= 2^21 as the nodes)
+    const int sx = ((l0x << 9) + __mul24(ay, l1x - l0x) + 512) >> 10, sy = ((l0y << 9) + __mul24(ay, l1y - l0y) + 512) >> 10;
+    const int ix = sx >> 5, iy = sy >> 5;
+    const uint32_t fx = (uint32_t)sx & 31u, fy = (uint32_t)sy & 31u;
+    const int cx0 = min(max(ix, 0), L.sw - 1), cx1 = min(max(ix + 1, 0), L.sw - 1);
+    const int cy0 = min(max(iy, 0), L.sh - 1), cy1 = min(max(iy + 1, 0), L.sh - 1);
+    // 32-bit offsets, rows by a 24-bit multiply: the host admits sources below 2^31 bytes with a pitch below 2^24
+    const uintptr_t src = (uintptr_t)L.src;
+    const STX_GAS uint8_t* base = (const STX_GAS uint8_t*)(src & ~(uintptr_t)3);
+    const uint32_t a0 = (uint32_t)(src & 3u) + __umul24((uint32_t)cy0, (uint32_t)L.spitch) + (uint32_t)cx0 * 3u;
+    const uint32_t a1 = a0 + (cy1 != cy0 ? (uint32_t)L.spitch : 0u);
+    uint32_t t00, t10, t01, t11;  // t<x><y>
+    lens_taps(base, a0, t00, t10);
+    lens_taps(base, a1, t01, t11);
+    if (cx1 == cx0) { t10 = t00; t11 = t01; }  // both clamped to one column
+    // (w00 p00 + w10 p10 + w01 p01 + w11 p11 + 512) >> 10 as ((32 - fy) p.0 + fy p.1) . (32 - fx, fx): the same products, packed
+    const uint32_t wy1 = fy * 0x10001u, wy0 = 0x200020u - wy1, wx = (32u - fx) | (fx << 16);
+    uint32_t px = 0u;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const uint32_t sel = k == 0 ? 0x0c040c00u : (k == 1 ? 0x0c050c01u : 0x0c060c02u);  // byte k of the left and of the right tap
+        const v2h top = as_v2h(__builtin_amdgcn_perm(t10, t00, sel)), bottom = as_v2h(__builtin_amdgcn_perm(t11, t01, sel));
+        const v2h v = top * as_v2h(wy0) + bottom * as_v2h(wy1);  // <= 255 * 32
+        px |= (__builtin_amdgcn_udot2(v, as_v2h(wx), 512u, false) >> 10) << (8 * k);
+    }
+    return px;
+}
+
+// the 12 bytes of a lane's 4 pixels as whole dwords: the destination is an image of the library's own, whose rows hold whole 8-pixel
+// groups (stx_buf_new), so the last lane of a row stores into the row's padding as the kernels above do
+STX_DEV void store_px4(const WarpK& P, int x0, int y, const uint32_t (&out)[3])
+{
+    uint32_t* d = reinterpret_cast<uint32_t*>(P.dimg + (long long)y * P.dimg_stride + (long long)x0 * 3);
+    d[0] = out[0];
+    d[1] = out[1];
+    d[2] = out[2];
+}
+
+// warp_kernel's coordinates (the same operations on the same tables, in the same order), sample_lens behind them
+template <int TYPE>
+__global__ __launch_bounds__(256) void warp_lens_kernel(WarpK P, const float2* __restrict__ colT, const float4* __restrict__ rowT, StxLensK L)
+{
+    const int lane = threadIdx.x & 63;
+    const int x0 = blockIdx.x * WARP_TW + lane * 4;
+    const int y = blockIdx.y * WARP_TH + (threadIdx.x >> 6);
+    if (x0 >= P.dw || y >= P.dh) return;
+    float ca[4], cb[4];
+    {
+        const float4 c01 = *reinterpret_cast<const float4*>(colT + x0);
+        const float4 c23 = *reinterpret_cast<const float4*>(colT + x0 + 2);
+        ca[0] = c01.x; cb[0] = c01.y; ca[1] = c01.z; cb[1] = c01.w;
+        ca[2] = c23.x; cb[2] = c23.y; ca[3] = c23.z; cb[3] = c23.w;
+    }
+    const float* rowF = reinterpret_cast<const float*>(rowT);
+    const float ra = rowF[16 * (y >> 2) + (y & 3)], rb = rowF[4 * round_up4(P.dh) + y];
+    const float omt = fsub(1.f, P.t[2]);
+    uint32_t out[3] = {0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        float x, yy;
+        if (TYPE == STX_WARP_PLANE || TYPE == STX_WARP_AFFINE) {
+            float z;
+            x = fadd(fadd(fmul(P.kr[0], ca[j]), fmul(P.kr[1], ra)), fmul(P.kr[2], omt));
+            yy = fadd(fadd(fmul(P.kr[3], ca[j]), fmul(P.kr[4], ra)), fmul(P.kr[5], omt));
+            z = fadd(fadd(fmul(P.kr[6], ca[j]), fmul(P.kr[7], ra)), fmul(P.kr[8], omt));
+            x = fdiv(x, z);
+            yy = fdiv(yy, z);
+        } else {
+            float x_, y_, z_;
+            if (TYPE == STX_WARP_SPHERICAL) {
+                x_ = fmul(ra, ca[j]);
+                y_ = rb;
+                z_ = fmul(ra, cb[j]);
+            } else {
+                x_ = ca[j];
+                y_ = ra;
+                z_ = cb[j];
+            }
+            x = dot3(P.kr[0], x_, P.kr[1], y_, P.kr[2], z_);
+            yy = dot3(P.kr[3], x_, P.kr[4], y_, P.kr[5], z_);
+            float z = dot3(P.kr[6], x_, P.kr[7], y_, P.kr[8], z_);
+            if (z > 0) {
+                x = fdiv(x, z);
+                yy = fdiv(yy, z);
+            } else {
+                x = yy = -1.f;
+            }
+        }
+        put_px(out, j, sample_lens(L, x, yy));
+    }
+    store_px4(P, x0, y, out);
+}
+
+// warp_general_kernel's coordinates, sample_lens behind them
+template <int G>
+__global__ __launch_bounds__(256) void warp_lens_general_kernel(WarpK P, StxLensK L)
+{
+    __shared__ float4 s_col[WARP_TW];
+    __shared__ float2 s_row[GEN_TH];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tx0 = blockIdx.x * WARP_TW, ty0 = blockIdx.y * GEN_TH;
+    s_col[tid] = gen_col<G>(P, (float)(P.tlx + min(tx0 + tid, P.dw - 1)));
+    if (tid < GEN_TH) s_row[tid] = gen_row<G>(P, (float)(P.tly + min(ty0 + tid, P.dh - 1)));
+    __syncthreads();
+    const int x0 = tx0 + lane * 4;
+    if (x0 >= P.dw) return;
+    for (int it = 0; it < GEN_TH / 4; it++) {
+        const int yl = it * 4 + wv, y = ty0 + yl;
+        if (y >= P.dh) break;
+        const float2 rw = s_row[yl];
+        uint32_t out[3] = {0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            float d0, d1, d2;
+            gen_dir<G>(P, s_col[lane * 4 + j], rw, d0, d1, d2);
+            float x = dot3(P.kr[0], d0, P.kr[1], d1, P.kr[2], d2);
+            float yy = dot3(P.kr[3], d0, P.kr[4], d1, P.kr[5], d2);
+            const float z = dot3(P.kr[6], d0, P.kr[7], d1, P.kr[8], d2);
+            if (z > 0) {
+                x = fdiv(x, z);
+                yy = fdiv(yy, z);
+            } else {
+                x = yy = -1.f;
+            }
+            put_px(out, j, sample_lens(L, x, yy));
+        }
+        store_px4(P, x0, y, out);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // ROI: forward-project the source border, NaN-ignoring float min/max
 // ---------------------------------------------------------------------------------------------
 struct RoiK {
@@ -1247,7 +1410,7 @@ bool fast_ok(const WarpK& K, bool nearest)
 
 template <int TYPE>
 int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, bool nearest, const char* prof_name, const double* algo_bytes,
-                 int dbg, stx_warp_tables* kept)
+                 int dbg, stx_warp_tables* kept, const StxLensK* lens = nullptr)
 {
     hipStream_t s = ctx->stream;
     // per-column / per-row trig tables (a few KB per image, L2 resident), one allocation for the batch, freed in stream order
@@ -1313,7 +1476,7 @@ int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, bool
             max_tab = std::max(max_tab, K.dw + ((K.dh + 3) & ~3));
             gx = std::max(gx, (K.dw + WARP_TW - 1) / WARP_TW);
             gy = std::max(gy, (K.dh + WARP_TH - 1) / WARP_TH);
-            fast = fast && fast_ok(K, nearest) && dbg != 2;
+            fast = fast && fast_ok(K, nearest) && dbg != 2 && !lens;  // through the lens: the one-pixel-per-lane kernel
             valid = valid || (mask && !nearest && K.msrc != nullptr);
             if (gain && (!fast_ok(K, nearest) || dbg || valid))
                 return stx_fail(STX_ERR_UNSUPPORTED, "a fused gain needs the tuned warp kernel (image %d does not qualify)", base + i);
@@ -1397,7 +1560,8 @@ int launch_typed(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, bool
                 StxProfScope prof(ctx, prof_name, algo_bytes[base + i]);
                 const WarpK& K = B.k[i];
                 const dim3 grid((K.dw + WARP_TW - 1) / WARP_TW, (K.dh + WARP_TH - 1) / WARP_TH);
-                if (dbg) hipLaunchKernelGGL((warp_kernel<TYPE, false, false, true>), grid, dim3(256), 0, s, K, B.colT[i], B.rowT[i]);
+                if (lens) hipLaunchKernelGGL((warp_lens_kernel<TYPE>), grid, dim3(256), 0, s, K, B.colT[i], B.rowT[i], lens[base + i]);
+                else if (dbg) hipLaunchKernelGGL((warp_kernel<TYPE, false, false, true>), grid, dim3(256), 0, s, K, B.colT[i], B.rowT[i]);
                 else if (img && mask) hipLaunchKernelGGL((warp_kernel<TYPE, true, true>), grid, dim3(256), 0, s, K, B.colT[i], B.rowT[i]);
                 else if (img) hipLaunchKernelGGL((warp_kernel<TYPE, true, false>), grid, dim3(256), 0, s, K, B.colT[i], B.rowT[i]);
                 else hipLaunchKernelGGL((warp_kernel<TYPE, false, true>), grid, dim3(256), 0, s, K, B.colT[i], B.rowT[i]);
@@ -1421,13 +1585,34 @@ void launch_general_group(stx_ctx* ctx, const WarpK& K, bool img, bool mask, int
     else hipLaunchKernelGGL((warp_general_kernel<G, false, true>), grid, dim3(256), 0, ctx->stream, K);
 }
 
-int launch_general(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, const char* prof_name, const double* algo_bytes, int dbg)
+template <int G>
+void launch_lens_general_group(stx_ctx* ctx, const WarpK& K, const StxLensK& L)
+{
+    const dim3 grid((K.dw + WARP_TW - 1) / WARP_TW, (K.dh + GEN_TH - 1) / GEN_TH);
+    hipLaunchKernelGGL((warp_lens_general_kernel<G>), grid, dim3(256), 0, ctx->stream, K, L);
+}
+
+int launch_general(stx_ctx* ctx, const WarpK* Ks, int n, bool img, bool mask, const char* prof_name, const double* algo_bytes, int dbg,
+                   const StxLensK* lens = nullptr)
 {
     for (int i = 0; i < n; i++)
         if (Ks[i].g_H) return stx_fail(STX_ERR_UNSUPPORTED, "a fused gain needs the tuned warp kernel (per-pixel projector families have none)");
     for (int i = 0; i < n; i++) {
         StxProfScope prof(ctx, prof_name, algo_bytes[i]);
         const WarpK& K = Ks[i];
+        if (lens) {
+            switch (K.family) {
+            case STX_F_FISHEYE:
+            case STX_F_STEREOGRAPHIC: launch_lens_general_group<GEN_FISH>(ctx, K, lens[i]); break;
+            case STX_F_CRECT:
+            case STX_F_CRECT_PORTRAIT: launch_lens_general_group<GEN_CRECT>(ctx, K, lens[i]); break;
+            case STX_F_PANINI:
+            case STX_F_PANINI_PORTRAIT: launch_lens_general_group<GEN_PANINI>(ctx, K, lens[i]); break;
+            case STX_F_TRANSVERSE_MERCATOR: launch_lens_general_group<GEN_TMERC>(ctx, K, lens[i]); break;
+            default: return stx_fail(STX_ERR_INVALID, "no per-pixel kernel for projector family %d", K.family);
+            }
+            continue;
+        }
         switch (K.family) {
         case STX_F_FISHEYE:
         case STX_F_STEREOGRAPHIC: launch_general_group<GEN_FISH>(ctx, K, img, mask, dbg); break;
@@ -1532,6 +1717,28 @@ int stx_launch_warp_batch(stx_ctx* ctx, const StxWarpLaunch* Ls, int n, stx_warp
 }
 
 int stx_launch_warp(stx_ctx* ctx, const StxWarpLaunch& L) { return stx_launch_warp_batch(ctx, &L, 1); }
+
+// The projector's arguments are made as for any warp (the rectified size stands where the source's does); the sampler's travel beside them.
+int stx_launch_warp_lens_batch(stx_ctx* ctx, const StxWarpLaunch* Ls, const StxLensK* lens, int n, stx_warp_tables* kept)
+{
+    ctx->warp_table_launches = 0;
+    if (n <= 0) return STX_OK;
+    std::vector<WarpK> Ks(n);
+    std::vector<double> bytes(n);
+    for (int i = 0; i < n; i++) {
+        fill_warpk(Ls[i], &Ks[i], &bytes[i]);
+        // algorithmic bytes: the distorted source and the lens grid once, the warped image once
+        bytes[i] = 3.0 * lens[i].sw * lens[i].sh + 8.0 * lens[i].nx * ((lens[i].h + STX_LENS_CELL - 1) / STX_LENS_CELL + 1) + 3.0 * Ls[i].dw * Ls[i].dh;
+    }
+    const char* name = "warp_lens_img";
+    switch (Ls[0].proj.family) {
+    case STX_F_PLANE: return launch_typed<STX_WARP_PLANE>(ctx, Ks.data(), n, true, false, false, name, bytes.data(), 0, kept, lens);
+    case STX_F_CYLINDRICAL: return launch_typed<STX_WARP_CYLINDRICAL>(ctx, Ks.data(), n, true, false, false, name, bytes.data(), 0, kept, lens);
+    case STX_F_SPHERICAL:
+    case STX_F_MERCATOR: return launch_typed<STX_WARP_SPHERICAL>(ctx, Ks.data(), n, true, false, false, name, bytes.data(), 0, kept, lens);
+    default: return launch_general(ctx, Ks.data(), n, true, false, name, bytes.data(), 0, lens);
+    }
+}
 
 bool stx_warp_fast_eligible(const StxWarpLaunch& L)
 {

@@ -484,6 +484,62 @@ STX_EXPORT int stx_warp_batch(stx_ctx* ctx, int type, float scale, int n, const 
     return kept.keep();
 }
 
+// The warp through the lens (include/stitching_amd.h): K, R and the rectangles are the rectified frame's, whose
+// size is the map's destination size; the source is the map's distorted frame.  Images only.
+STX_EXPORT int stx_warp_lens_batch(stx_ctx* ctx, int type, float scale, int n, const float* K9s, const float* R9s, const stx_buf* const* srcs,
+                                   const stx_lens_map* const* maps, const int* rects_xywh, stx_buf** out_imgs, int* out_xywh,
+                                   stx_warp_tables** tables)
+{
+    if (!ctx || !K9s || !R9s || !srcs || !maps || !out_imgs || n < 0) return stx_fail(STX_ERR_INVALID, "bad argument");
+    if (tables && *tables && (*tables)->ctx != ctx)
+        return stx_fail(STX_ERR_INVALID, "warp tables: the handle belongs to another context (no cross-stream use)");
+    if (remap_mode_now() != STX_REMAP_Q15)
+        return stx_fail(STX_ERR_INVALID, "warp through the lens: the sampler has one arithmetic, the remap mode must be q15");
+    std::vector<StxProjector> ps((size_t)n);
+    std::vector<int> sizes(2 * (size_t)n);
+    std::vector<StxLensK> lens((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const stx_buf* S = srcs[i];
+        const stx_lens_map* M = maps[i];
+        if (!S) return stx_fail(STX_ERR_INVALID, "warp through the lens: image %d is a null handle", i);
+        if (!M) return stx_fail(STX_ERR_INVALID, "warp through the lens: lens map %d is a null handle", i);
+        if (S->ctx != ctx || M->ctx != ctx) return stx_fail(STX_ERR_INVALID, "warp through the lens: image or lens map %d belongs to another context", i);
+        if (S->elem != STX_U8 || S->c != 3) return stx_fail(STX_ERR_INVALID, "warp through the lens: source %d must be u8x3", i);
+        if (S->w != M->src_w || S->h != M->src_h)
+            return stx_fail(STX_ERR_INVALID, "warp through the lens: image %d is %dx%d, its lens map was made for %dx%d", i, S->w, S->h, M->src_w, M->src_h);
+        // the sampler's 32-bit offsets and 24-bit row multiply (stx_rectify's limits)
+        if (S->stride >= (size_t)1 << 24 || (unsigned long long)(S->h - 1) * S->stride + (unsigned long long)S->w * 3 + 32 > 0x7fffffffull)
+            return stx_fail(STX_ERR_INVALID, "warp through the lens: image %d spans %llu bytes with a pitch of %zu: below 2^31 and 2^24 is taken", i,
+                            (unsigned long long)(S->h - 1) * S->stride + (unsigned long long)S->w * 3, S->stride);
+        if (rects_xywh) STX_TRY(check_warp_rect(rects_xywh + 4 * i));
+        STX_TRY(stx_make_projector(type, scale, K9s + 9 * i, R9s + 9 * i, &ps[i]));
+        sizes[2 * i] = M->dst_w;
+        sizes[2 * i + 1] = M->dst_h;
+        StxLensK& L = lens[i];
+        L.nodes = (const int2*)M->d_nodes.get(); L.nx = M->nx; L.w = M->dst_w; L.h = M->dst_h;
+        L.src = S->ptr; L.spitch = (int)S->stride; L.sw = S->w; L.sh = S->h;
+    }
+    // nothing was allocated or queued up to here
+    WarpTablesSlot kept(ctx, tables);
+    if (n == 0) return kept.keep();
+    STX_TRY(stx_set_device(ctx));
+    std::vector<int> rois(4 * (size_t)n);
+    if (rects_xywh) rois.assign(rects_xywh, rects_xywh + 4 * (size_t)n);
+    else STX_TRY(rois_cached(ctx, type, scale, n, K9s, R9s, ps.data(), sizes.data(), true, rois.data()));
+    std::vector<StxBufRef> bi((size_t)n);
+    std::vector<StxWarpLaunch> Ls((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const int* roi = &rois[4 * i];
+        STX_TRY(check_warp_rect(roi));
+        STX_TRY(stx_buf_new(ctx, roi[2], roi[3], 3, STX_U8, &bi[i]));
+        Ls[i] = warp_launch(ps[i], roi, nullptr, sizes[2 * i], sizes[2 * i + 1], bi[i].get(), nullptr);
+    }
+    STX_TRY(stx_launch_warp_lens_batch(ctx, Ls.data(), lens.data(), n, kept.get()));
+    for (int i = 0; i < n; i++) out_imgs[i] = bi[i].release();
+    if (out_xywh) memcpy(out_xywh, rois.data(), sizeof(int) * 4 * (size_t)n);
+    return kept.keep();
+}
+
 STX_EXPORT int stx_warp_tables_free(stx_warp_tables* t)
 {
     if (!t) return STX_OK;

@@ -15,9 +15,9 @@ import numpy as np
 from . import _lib, config
 from .blender import Blender
 from .cropper import Cropper
-from .device import as_device, get_context, is_foreign_device_array, shrink_masks_all, with_validity
+from .device import DeviceImage, as_device, get_context, is_foreign_device_array, shrink_masks_all, with_validity
 from .exposure_error_compensator import ExposureErrorCompensator
-from .images import Images
+from .images import Images, MegapixDownscaler
 from .rectify import lens_list, rectify_all
 from .seam_estimation import SeamEstimator
 from .seam_finder import DEVICE_SEAM_FINDERS, SeamFinder
@@ -147,6 +147,68 @@ def masks_belong_to_job(feed_masks, seam_masks, source_masks=None):
     return given is None or all(isinstance(m, np.ndarray) for m in given)
 
 
+class _LensWarper:
+    """StitchJob's warper when the job has lenses: a Warper whose warp_images_and_masks takes DISTORTED frames through their lenses
+    (Warper.warp_images_through_lenses).  The job's own code is the same with and without lenses — the rectangles,
+    the masks and the ROIs it sees are those of the rectified frames:
+      * warped masks do not depend on pixel values: the existing mask-only launch over frames of the rectified sizes makes them (once per
+        rig; the frames are placeholders that are never read, they carry the rectified-size source masks where the job has any);
+      * images come from stx_warp_lens_batch into the same rectangles;
+      * gains are a second pass over the warped images (the plain `apply`, or stx_block_gain_apply_batch with the rectangle's place in
+        the whole warped image): byte for byte the gain applied to the ungained warp."""
+
+    def __init__(self, warper, lenses, source_masks):
+        self._warper, self._lenses, self._source_masks = warper, lenses, source_masks
+        self._rois = None  # (key, ROIs of the rectified frames): what a block gain's map lies over
+
+    def __getattr__(self, name):
+        return getattr(self._warper, name)
+
+    def set_scale(self, cameras):
+        self._warper.set_scale(cameras)
+
+    def _placeholders(self, ctx):
+        out = []
+        for i, lens in enumerate(self._lenses):
+            h = C.c_void_p()
+            _lib.check(ctx._lib.stx_buf_alloc(ctx.handle, lens.dst_size[0], lens.dst_size[1], 3, _lib.U8, C.byref(h)))
+            d = DeviceImage(ctx, h)
+            m = None if self._source_masks is None else self._source_masks[i]
+            out.append(d if m is None else with_validity(d, m))
+        return out
+
+    def _full_rois(self, cameras, aspect, camera_arrays):
+        sizes = [lens.dst_size for lens in self._lenses]
+        Ks, Rs = camera_arrays if camera_arrays is not None else self._warper.camera_arrays(cameras, aspect)
+        key = (Ks.tobytes(), Rs.tobytes(), float(aspect), self._warper.scale, self._warper.warper_type, config.trig_mode())
+        if self._rois is None or self._rois[0] != key:
+            corners, wh = self._warper.warp_rois(sizes, cameras, aspect, camera_arrays=(Ks, Rs))
+            self._rois = (key, [tuple(c) + tuple(z) for c, z in zip(corners, wh)])
+        return self._rois[1]
+
+    def warp_images_and_masks(self, imgs, cameras, aspect=1, rects=None, compensator=None, with_rois=False, camera_arrays=None, masks=True,
+                              tables=None):
+        ctx = self._warper._ctx()
+        cameras = list(cameras)
+        masks_out = None
+        if masks:
+            _, masks_out, rois = self._warper.warp_images_and_masks(self._placeholders(ctx), cameras, aspect, rects=rects, with_rois=with_rois,
+                                                                    camera_arrays=camera_arrays, images=False)
+            if rects is None:
+                rects = rois
+        elif rects is None:
+            raise StitchingError("masks=False needs rects: the rectangles of the call that made the masks")
+        out, rois = self._warper.warp_images_through_lenses(imgs, self._lenses, cameras, aspect, rects=rects, camera_arrays=camera_arrays,
+                                                            tables=tables)
+        if compensator is not None and compensator.compensator_type != "no":
+            corners, sub = [r[0:2] for r in rois], None
+            if compensator.compensator_type in ("gain_blocks", "channel_blocks"):
+                full = self._full_rois(cameras, aspect, camera_arrays)
+                sub = [(f[2], f[3], r[0] - f[0], r[1] - f[1]) for r, f in zip(rois, full)]
+            out = compensator.apply_all(corners, out, None, sub=sub, ctx=ctx)
+        return out, masks_out, rois
+
+
 class StitchJob:
     """Pre-staged inputs of one panorama — or of the panoramas of one rig: device-resident source frames + cameras.
 
@@ -157,7 +219,8 @@ class StitchJob:
 
     def __init__(self, frames, cameras, warper_type="spherical", blender_type="multiband", num_bands=None,
                  blend_strength=Blender.DEFAULT_BLEND_STRENGTH, ctx=None, async_upload=False, feed_masks=None, seam_masks=None,
-                 crop_to_masks=True, compensator=None, cropper=None, crop_aspect=1, camera_aspect=1, reuse_geometry=True, source_masks=None):
+                 crop_to_masks=True, compensator=None, cropper=None, crop_aspect=1, camera_aspect=1, reuse_geometry=True, source_masks=None,
+                 lenses=None):
         """async_upload: numpy frames in page-locked memory (pinned_empty) are only queued for upload; they must stay
         untouched until ctx.sync() (a streaming caller alternates two contexts).
         feed_masks: final-resolution u8 masks fed to the blender instead of the warped masks (seam masks already at the
@@ -187,21 +250,37 @@ class StitchJob:
         the nearest-neighbour warps of these instead of warped rectangles (with_validity) — whatever the job then
         does with warped masks (feeding, SeamFinder.resize) sees them.  Attached once, and again to the frames of set_frames /
         run(frames=).  ROIs, the blender's rectangle and view_rects do not change: a source mask changes what is inside a warped mask,
-        never its rectangle.  Host arrays belong to the job; device arrays of the caller turn reuse_geometry off."""
+        never its rectangle.  Host arrays belong to the job; device arrays of the caller turn reuse_geometry off.
+        lenses: one LensMap per frame, or one for all: the frames (also those of set_frames / run(frames=)) are DISTORTED frames of the
+        lenses' source sizes, and every run takes them to the panorama in one resampling (Warper.warp_images_through_lenses; DESIGN.md
+        section 24) instead of rectifying first.  Cameras, source_masks, rectangles and ROIs belong to the rectified frames (the lenses'
+        dst_size); the warped masks are those of a job over rectified frames, byte for byte; gains are applied as a second pass;
+        source_masks="lens" takes the masks that rectification returns (rectify_all(masks=True), once, at construction).  The
+        panorama's pixels differ from rectify-then-warp (one bilinear blend instead of two)."""
         cropper, crop_aspect = _split_cropper(cropper, crop_aspect)
         if len(frames) != len(cameras) or not frames:
             raise StitchingError("need one camera per frame and at least one frame")
+        self.lenses = None if lenses is None else lens_list(lenses, len(frames))
         self.ctx = ctx or get_context()
         self.frames = [as_device(f, self.ctx, wait=not async_upload) for f in frames]
         self.source_masks = None
+        if isinstance(source_masks, str):  # "lens" (with lenses): the masks rectification returns, made here, once
+            if source_masks != "lens" or self.lenses is None:
+                raise StitchingError(f"source_masks={source_masks!r}: a list of masks, or \"lens\" with lenses")
+            source_masks = OwnedMasks(rectify_all(self.frames, self.lenses, masks=True, ctx=self.ctx)[1])
         if source_masks is not None:
             if len(source_masks) != len(self.frames):
                 raise StitchingError(f"{len(source_masks)} source masks for {len(self.frames)} frames")
             self.source_masks = [None if m is None else as_device(m, self.ctx) for m in source_masks]
             self.frames = self._with_source_masks(self.frames)
         self.cameras = list(cameras)
-        self.sizes = [(f.width, f.height) for f in self.frames]
+        self.frame_sizes = self.sizes = [(f.width, f.height) for f in self.frames]  # sizes: what cameras and ROIs belong to
         self.warper = Warper(warper_type, ctx=self.ctx)
+        if self.lenses is not None:
+            if self.frame_sizes != [lens.src_size for lens in self.lenses]:
+                raise StitchingError(f"the lenses were made for frames of sizes {[lens.src_size for lens in self.lenses]}, got {self.frame_sizes}")
+            self.sizes = [lens.dst_size for lens in self.lenses]
+            self.warper = _LensWarper(self.warper, self.lenses, self.source_masks)
         self.warper.set_scale(self.cameras)
         self.blender_type = blender_type
         self.compensator = compensator
@@ -228,6 +307,8 @@ class StitchJob:
 
     def _with_source_masks(self, frames):
         """the job's validity masks on (new) frames: new handles, the frames' own are not changed"""
+        if self.lenses is not None:  # the masks belong to the rectified frames: _LensWarper has them
+            return frames
         return [f if m is None else with_validity(f, m) for f, m in zip(frames, self.source_masks)]
 
     @property
@@ -260,8 +341,8 @@ class StitchJob:
         """New frames of the same rig: the same number, the same sizes (ComposePlan.check_frames's rule)."""
         frames = list(frames)
         got = [Images.get_image_size(f) for f in frames]
-        if got != [tuple(z) for z in self.sizes]:
-            raise StitchingError(f"the job was made for frames of sizes {self.sizes}, got {got}: same rig, same sizes")
+        if got != [tuple(z) for z in self.frame_sizes]:
+            raise StitchingError(f"the job was made for frames of sizes {self.frame_sizes}, got {got}: same rig, same sizes")
         self.frames = [as_device(f, self.ctx) for f in frames]
         if self.source_masks is not None:
             self.frames = self._with_source_masks(self.frames)
@@ -277,8 +358,10 @@ class StitchJob:
     def geometry_key(self):
         """rig_key of the job as it stands now"""
         modes = (config.trig_mode(), config.remap_mode()) + tuple(config.pyrdown_mode())
-        return rig_key(self._cam_bytes, self.camera_aspect, self.warper.warper_type, self.warper.scale, self.sizes, self.blender_type,
-                       self.num_bands, self.blend_strength, modes, self.cropper, self.crop_aspect)
+        key = rig_key(self._cam_bytes, self.camera_aspect, self.warper.warper_type, self.warper.scale, self.sizes, self.blender_type,
+                      self.num_bands, self.blend_strength, modes, self.cropper, self.crop_aspect)
+        # the lenses' identity: another lens is another rig (a LensMap's nodes cannot be written)
+        return key if self.lenses is None else key + (tuple(id(lens) for lens in self.lenses),)
 
     def run(self, frames=None):
         """warp every frame, feed it, blend.  Returns device-resident (panorama u8x3, mask u8).
@@ -425,8 +508,32 @@ def _seam_mask_input(m):
     return m if is_foreign_device_array(m) else np.asarray(m.get() if hasattr(m, "get") else m)
 
 
+LENS_MODES = ("rectify", "fused")
+
+
+def check_lens_mode(lens_mode, lenses):
+    """lens_mode= of compose and Composer -> True for "fused"; any other string than LENS_MODES, and "fused" without lenses, is refused"""
+    if lens_mode not in LENS_MODES:
+        raise StitchingError(f"lens_mode {lens_mode!r}: one of {list(LENS_MODES)}")
+    if lens_mode == "fused" and lenses is None:
+        raise StitchingError("lens_mode=\"fused\" needs lenses: it warps distorted frames through them")
+    return lens_mode == "fused"
+
+
+def check_final_size(final_megapix, sizes):
+    """lens_mode="fused": a final_megapix that resizes the (rectified) frames of `sizes` is refused — the lens belongs to the frame's
+    own size.  The scale is the first frame's, as Images sets it."""
+    scaler = MegapixDownscaler(final_megapix)
+    scaler.set_scale_by_img_size(sizes[0])
+    scaled = [scaler.get_scaled_img_size(z) for z in sizes]
+    if scaled != [tuple(z) for z in sizes]:
+        raise StitchingError(f"lens_mode=\"fused\" with final_megapix={final_megapix}: the frames would be resized to {scaled}, and a "
+                             "lens belongs to the frame's own size")
+
+
 def compose(frames, cameras, warper_type="spherical", blender_type="multiband", blend_strength=Blender.DEFAULT_BLEND_STRENGTH,
-            compensator=None, seam_masks=None, ctx=None, cropper=None, crop_aspect=1, camera_aspect=1, source_masks=None):
+            compensator=None, seam_masks=None, ctx=None, cropper=None, crop_aspect=1, camera_aspect=1, source_masks=None, lenses=None,
+            lens_mode="rectify"):
     """The final-resolution half of Stitcher.stitch (stitching/stitcher.py:117-128) with every intermediate in HBM:
 
         warp_final_resolution_imgs / masks   (:119-121, Warper)            -> one batched warp
@@ -440,9 +547,21 @@ def compose(frames, cameras, warper_type="spherical", blender_type="multiband", 
     cropper's rectangles are warped (StitchJob); compensator gains and seam masks then belong to the cropped images.
     `camera_aspect`: the size of the frames relative to the images the cameras were estimated on.
     `source_masks`: one validity mask per frame (or None entries), see StitchJob.
+    `lenses`: one LensMap per frame, or one for all: the frames are distorted.  `lens_mode` "rectify" (the default) rectifies them first
+    (rectify_all); "fused" takes them to the panorama in one resampling (StitchJob(lenses=)) — other pixels than
+    "rectify", the same masks.  Cameras and source_masks belong to the rectified frames either way.
     Returns device-resident (panorama u8x3, mask u8)."""
+    fused = check_lens_mode(lens_mode, lenses)
     ctx = ctx or get_context()
     cropper, crop_aspect = _split_cropper(cropper, crop_aspect)
+    if fused:
+        if seam_masks is not None and blender_type == "multiband":
+            seam_masks = [_seam_mask_input(m) for m in seam_masks]
+        return StitchJob(frames, cameras, warper_type=warper_type, blender_type=blender_type, blend_strength=blend_strength, ctx=ctx,
+                         seam_masks=seam_masks, compensator=compensator, cropper=cropper, crop_aspect=crop_aspect,
+                         camera_aspect=camera_aspect, source_masks=source_masks, lenses=lenses).run()
+    if lenses is not None:
+        frames = rectify_all(frames, lenses, ctx=ctx)
     if cropper is not None:
         if seam_masks is not None and blender_type == "multiband":
             seam_masks = [_seam_mask_input(m) for m in seam_masks]
@@ -481,8 +600,11 @@ class ComposePlan:
     rig's masks and weight pyramids between runs (StitchJob's memory note; `plan.job.release_geometry()` gives them back)."""
 
     def __init__(self, images, frames, cameras, warper_scale, cropper, compensator, seam_masks, seam_masks_host, low_corners, low_sizes,
-                 source_masks=None):
+                 source_masks=None, distorted=None, lenses=None):
         self.images, self.frames, self.cameras, self.warper_scale = images, frames, list(cameras), warper_scale
+        # lens_mode="fused": the distorted frames the plan was prepared from and their lenses (`frames` are their rectified forms, which
+        # the low-resolution pass read); None, None otherwise
+        self.distorted, self.lenses = distorted, lenses
         self.source_masks = source_masks  # the frames' validity masks at the frames' size (device; OwnedMasks where they are the plan's own), or None
         self.cropper, self.compensator, self.seam_masks, self.seam_masks_host = cropper, compensator, seam_masks, seam_masks_host
         self.low_corners, self.low_sizes = low_corners, low_sizes
@@ -589,7 +711,7 @@ class Composer:
                 out[i] = m
         return OwnedMasks(out) if isinstance(source_masks, OwnedMasks) else out
 
-    def prepare(self, images, cameras, lenses=None, source_masks=None):
+    def prepare(self, images, cameras, lenses=None, source_masks=None, lens_mode="rectify"):
         """The low-resolution half -> ComposePlan.  The host waits for the device where a result decides what is launched next: the ROI
         pass of the warp, the cropper's rectangle, the gain solve (and the read-back of the seam masks for the multi-band blender's
         seam-cell crops).  lenses: one LensMap per image, or one for all — the images are then distorted frames and are rectified
@@ -598,10 +720,17 @@ class Composer:
         "lens" (needs lenses): the masks of the rectification itself, which keep a lens's black wedges out of the panorama.  The
         masks are shrunk conservatively to the LOW size and ride on the low-resolution frames, so that the cropper, the gain
         estimation and the seam finder see them through the warped masks; the plan keeps them for the final-resolution half.  A user's
-        masks and a lens's are not combined."""
+        masks and a lens's are not combined.
+        lens_mode: "rectify" (the default): as above.  "fused" (needs lenses): the low-resolution pass still reads rectified frames —
+        it runs once per rig — but the plan keeps the DISTORTED frames and the lenses, and `run` warps through the lens (StitchJob with
+        lenses).  Refused with a final_megapix that resizes the frames: a lens belongs to the frame's own size."""
         frames, cameras = list(images), list(cameras)
+        fused = check_lens_mode(lens_mode, lenses)
+        distorted = frames if fused else None
         if lenses is not None:
             lenses = lens_list(lenses, len(frames))
+        if fused:
+            check_final_size(self.settings["final_megapix"], [lens.dst_size for lens in lenses])
         st, ctx = self.settings, self._ctx()
         if len(frames) != len(cameras):
             raise StitchingError("need one camera per image")
@@ -645,12 +774,15 @@ class Composer:
         finally:
             config.set_device_resident(prev)
         return ComposePlan(imgs_obj, frames, cameras, warper.scale, cropper, compensator, seam_masks, host, corners, sizes,
-                           source_masks=source_masks)
+                           source_masks=source_masks, distorted=distorted, lenses=lenses if fused else None)
 
     def run(self, plan, images=None, lenses=None):
         """The final-resolution half on a plan: `images` None -> the frames the plan was prepared from, else new frames of the same rig
         (no low-resolution pass).  lenses: the LensMaps of new, distorted `images`, which are rectified first (the plan's own frames
-        are rectified already).  Returns device-resident (panorama u8x3, mask u8)."""
+        are rectified already).  A plan of lens_mode="fused" warps through the lens: its own distorted frames, or new distorted `images`
+        with their `lenses`.  Returns device-resident (panorama u8x3, mask u8)."""
+        if getattr(plan, "lenses", None) is not None:
+            return self._run_fused(plan, images, lenses)
         if lenses is not None:
             if images is None:
                 raise StitchingError("lenses go with new images: the frames the plan was prepared from are rectified already")
@@ -682,22 +814,51 @@ class Composer:
             return plan.job.run()
         return plan.job.run(frames=final)
 
-    def compose(self, images, cameras, lenses=None, source_masks=None):
-        """prepare + run -> the panorama (device-resident u8x3), as Stitcher.stitch returns it; lenses, source_masks: see `prepare`"""
-        pano, _ = self.run(self.prepare(images, cameras, lenses=lenses, source_masks=source_masks))
+    def _run_fused(self, plan, images, lenses):
+        """`run` on a plan of lens_mode="fused": one StitchJob with lenses per plan and set of lenses"""
+        if images is None:
+            if lenses is not None:
+                raise StitchingError("lenses go with new images: the plan has the lenses of its own frames")
+            frames, lenses = plan.distorted, plan.lenses
+        else:
+            if lenses is None:
+                raise StitchingError("a plan of lens_mode=\"fused\" takes distorted images with their lenses")
+            frames = list(images)
+            lenses = lens_list(lenses, len(frames))
+            plan.check_frames(frames, lenses)
+        st, ctx = self.settings, self._ctx()
+        job_key = (id(ctx), st["warper_type"], st["blender_type"], st["blend_strength"], "fused", tuple(id(lens) for lens in lenses))
+        if plan.job is None or plan.job_key != job_key:
+            plan.job = StitchJob(frames, plan.cameras, warper_type=st["warper_type"], blender_type=st["blender_type"],
+                                 blend_strength=st["blend_strength"], ctx=ctx,
+                                 seam_masks=plan.seam_masks_host if plan.seam_masks_host is not None else plan.seam_masks,
+                                 compensator=plan.compensator, cropper=plan.cropper, crop_aspect=plan.lir_aspect,
+                                 camera_aspect=plan.camera_aspect, source_masks=plan.source_masks, lenses=lenses)
+            plan.job_key = job_key
+            return plan.job.run()
+        return plan.job.run(frames=frames)
+
+    def compose(self, images, cameras, lenses=None, source_masks=None, lens_mode="rectify"):
+        """prepare + run -> the panorama (device-resident u8x3), as Stitcher.stitch returns it; lenses, source_masks, lens_mode: see
+        `prepare`"""
+        pano, _ = self.run(self.prepare(images, cameras, lenses=lenses, source_masks=source_masks, lens_mode=lens_mode))
         return pano
 
-    def stitch(self, images, feature_estimator=None, match_estimator=None, camera_solver=None, lenses=None, source_masks=None):
+    def stitch(self, images, feature_estimator=None, match_estimator=None, camera_solver=None, lenses=None, source_masks=None,
+               lens_mode="rectify"):
         """Frames in, panorama out (device-resident u8x3), with no cv2 and no cameras supplied: the registration half of Stitcher.stitch
         (stitching/stitcher.py:99-105) by the project's own estimators — resize to MEDIUM on the device, FeatureEstimator.detect,
         MatchEstimator.match, CameraSolver.register — then `compose` on the images registration kept.  The three objects default to
         their classes' defaults.  `self.registration` keeps the indices of the images kept, their cameras and the solver's info.
         lenses: one LensMap per image, or one for all: registration and composition then see the rectified frames.
-        source_masks: as in `prepare`; shrunk to the MEDIUM size they also keep the feature detector off what is not picture."""
+        source_masks: as in `prepare`; shrunk to the MEDIUM size they also keep the feature detector off what is not picture.
+        lens_mode: as in `prepare`; registration reads the rectified frames either way."""
         from .camera_estimation import CameraSolver
         from .feature_estimation import FeatureEstimator
         from .match_estimation import MatchEstimator
 
+        fused = check_lens_mode(lens_mode, lenses)
+        distorted = list(images) if fused else None
         if lenses is not None:
             images = list(images)
             lenses = lens_list(lenses, len(images))
@@ -729,6 +890,9 @@ class Composer:
         indices, cameras = camera_solver.register(features, matches, ctx=ctx)
         self.registration = {"indices": list(indices), "cameras": cameras, "info": camera_solver.info}
         kept = None if source_masks is None else type(source_masks)(source_masks[i] for i in indices)
+        if fused:  # the distorted frames registration kept, with their lenses (prepare rectifies them for its low-resolution pass)
+            return self.compose([distorted[i] for i in indices], cameras, lenses=[lenses[i] for i in indices], source_masks=kept,
+                                lens_mode="fused")
         return self.compose([frames[i] for i in indices], cameras, source_masks=kept)
 
 

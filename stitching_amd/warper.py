@@ -258,6 +258,43 @@ class Warper:
         masks_out = None if h_mask is None else [self._result(DeviceImage(ctx, C.c_void_p(h_mask[i]))) for i in range(n)]
         return imgs_out, masks_out, [tuple(int(v) for v in r) for r in rois]
 
+    def warp_images_through_lenses(self, frames, lenses, cameras, aspect=1, rects=None, camera_arrays=None, tables=None):
+        """DISTORTED frames to warped images in one resampling (stx_warp_lens_batch; tests/numpy_lens_warp.py is the contract): the warp's
+        own backward map, then the frame's LensMap, then four taps of the distorted frame — instead of rectify_all followed by
+        warp_images_and_masks, which resamples twice.  Returns (warped_images, rois).
+        frames: numpy arrays, DeviceImages (crop views included) or foreign device arrays, HxWx3 uint8, each of its lens's src_size.
+        lenses: one LensMap per frame, or one for all.  cameras, aspect, rects, camera_arrays, tables: as warp_images_and_masks, for the
+        RECTIFIED frames (each lens's dst_size): the ROIs are those of the rectified sizes.
+        Images only: warped masks do not depend on pixel values — warp_images_and_masks(..., images=False) over rectified sizes makes them."""
+        from .rectify import lens_list
+
+        frames, cameras = list(frames), list(cameras)
+        lenses = lens_list(lenses, len(frames))
+        if len(cameras) != len(frames):
+            raise StitchingError(f"{len(cameras)} cameras for {len(frames)} frames")
+        ctx = self._ctx()
+        n = len(frames)
+        if n == 0:
+            return [], []
+        srcs = [self._source(f, ctx) for f in frames]
+        for i, (s, lens) in enumerate(zip(srcs, lenses)):
+            if (s.width, s.height) != lens.src_size:
+                raise StitchingError(f"warp through the lens: frame {i} is {s.width}x{s.height}, its lens was made for "
+                                     f"{lens.src_size[0]}x{lens.src_size[1]}")
+        Ks, Rs = camera_arrays if camera_arrays is not None else self.camera_arrays(cameras, aspect)
+        ip = C.POINTER(C.c_int)
+        rects_p = None
+        if rects is not None:
+            rects = np.ascontiguousarray(np.asarray(rects, np.int32).reshape(n, 4))
+            rects_p = rects.ctypes.data_as(ip)
+        h_src = (C.c_void_p * n)(*[s._h.value for s in srcs])
+        h_map = (C.c_void_p * n)(*[lens.handle(ctx).value for lens in lenses])
+        h_img = (C.c_void_p * n)()
+        rois = np.zeros((n, 4), np.int32)
+        _lib.check(ctx._lib.stx_warp_lens_batch(ctx.handle, self._type_id(), self._scale(aspect), n, _fp(Ks), _fp(Rs), h_src, h_map, rects_p,
+                                                h_img, rois.ctypes.data_as(ip), None if tables is None else tables._ref(ctx)))
+        return ([self._result(DeviceImage(ctx, C.c_void_p(h_img[i]))) for i in range(n)], [tuple(int(v) for v in r) for r in rois])
+
     # ------------------------------------------------------------------ helpers
     @staticmethod
     def _source(img, ctx):

@@ -394,6 +394,48 @@ int stx_exposure_solve_device(stx_ctx* ctx, int m, int npairs, const int* pairs_
 /* The elimination alone, for tests and tools: A (n x n, row-major, host) x = b by the device LU for every n >= 1 -> x_out[n], the bits
  * of tests/numpy_exposure.py::lu_solve(A, b, skip_zeros=False).  out_info as stx_exposure_solve_device. */
 int stx_lu_solve_device(stx_ctx* ctx, int n, const double* A_dense_host, const double* b_host, double* x_out, double out_info[4]);
+/* ---- exposure-gain tracking on a known rig (tests/numpy_exposure_track.py is the contract) -----------------
+ * The gains of ExposureCompensator::feed are estimated once, on the low-resolution pass.  A tracker measures, on the warped and
+ * compensated images every panorama of a known rig makes anyway, how far the cameras have drifted since: integer sums over a lattice.
+ * The lattice of stride s holds the panorama pixels (X, Y) with X mod s == 0 and Y mod s == 0 (floor-mod: corners are often
+ * negative).  Image i is warped into rects_xywh[i]; V_i is 1 at the lattice points inside it where its warped mask is 255 (grey values
+ * do not count); c_ii = sum(V_i).  A pair job is (a, b), a < b, whose rectangles intersect (also where the intersection holds no
+ * lattice point), in lexicographic order.  Its statistics are eight 64-bit integers c, aB, aG, aR, bB, bG, bR, rej over the lattice
+ * points of both rectangles with V_a & V_b: a sample whose six bytes all lie in 1 .. 254 adds 1 to c and its channels to the sums,
+ * any other adds 1 to rej (a saturated product cannot be de-compensated).  Integer sums: the same bits whatever the order.
+ * stx_exposure_track_create: one launch over the masks (u8x1, the rectangles' sizes; views with their own pitch are taken) makes the V
+ *   grids, one byte per lattice point, kept by the handle; the masks are not kept.  One host wait (c_ii comes back).
+ * stx_exposure_track_pairs: out_ab NULL and out_self_counts NULL: writes the number of pair jobs to *inout_count.  Else *inout_count is
+ *   the capacity of out_ab in pairs; out_ab gets (a, b) per pair, out_self_counts c_ii per image (n values).
+ * stx_exposure_track_measure: in the context's stream order — clears the accumulators of slot k mod 2 (k: measures so far), one
+ *   launch (a 256-lane workgroup per tile of 32 x 32 lattice points of a pair; one 64-bit integer atomic add per value and workgroup),
+ *   an asynchronous copy to page-locked host memory, an event.  No host wait.  imgs_u8x3[i]: the warped, compensated image of
+ *   rectangle i (its size; views are taken); it must stay unwritten until the launch has run (stream order does that for the
+ *   library's own calls).  At most two measures may be pending.
+ * stx_exposure_track_collect: waits for the event of the OLDEST pending measure and copies its pairs x 8 values to out_stats (may
+ *   be NULL without pairs).  STX_ERR_INVALID if none is pending.
+ * stx_exposure_track_info: {pair jobs, tile jobs, bytes of the V grids, the statistics launch of the last collected measure in ms (HIP
+ *   events), the wait of the last collect in ms (host clock), measures so far}.
+ * Refused with STX_ERR_INVALID before anything is launched, the context stays usable: null handles or handles of another context,
+ * images or masks whose size is not their rectangle's, wrong element types, a stride outside 1 .. STX_TRACK_STRIDE_MAX, n outside
+ * 1 .. STX_TRACK_IMAGES_MAX, more than STX_TRACK_TILES_MAX tile jobs (take a larger stride). */
+#define STX_TRACK_STRIDE_MAX 64
+#define STX_TRACK_IMAGES_MAX 1024
+#define STX_TRACK_TILES_MAX 65536
+typedef struct stx_exposure_track stx_exposure_track;
+int stx_exposure_track_create(stx_ctx* ctx, int n, const int* rects_xywh, const stx_buf* const* masks_u8, int stride,
+                              stx_exposure_track** out);
+int stx_exposure_track_pairs(stx_exposure_track* t, int* inout_count, int* out_ab, long long* out_self_counts);
+int stx_exposure_track_measure(stx_exposure_track* t, const stx_buf* const* imgs_u8x3);
+int stx_exposure_track_collect(stx_exposure_track* t, long long* out_stats);
+int stx_exposure_track_info(stx_exposure_track* t, double out_info[6]);
+int stx_exposure_track_free(stx_exposure_track* t);
+/* outs[i] = a new f32 image, maps_f32[i] * factors in fp32 (one rounded product per value), for all n maps in one launch per 32: an
+ * f32x1 map with planes == 1 gives f32x1 (factors[i]), with planes == 3 f32x3 (factors[3 i + c] per channel); an f32x3 map gives f32x3
+ * (planes == 1: the one factor for all channels).  The factors travel in the kernel's arguments: no upload, no host wait.  Refused with
+ * STX_ERR_INVALID before anything is launched: null handles, maps of another context, maps that are not f32x1 / f32x3, planes other
+ * than 1 or 3, n outside 1 .. STX_TRACK_IMAGES_MAX.  A failing call hands nothing out. */
+int stx_gain_maps_scale(stx_ctx* ctx, int n, const stx_buf* const* maps_f32, const float* factors, int planes, stx_buf** outs);
 /* ---- seam finding: SeamFinder::find of the "voronoi" and "no" finders (stitching/seam_finder.py:33-35) -------------------------
  * kind: STX_SEAM_VORONOI (VoronoiSeamFinder: PairwiseSeamFinder::run over the overlapping pairs (i, j), i < j, in order; a gap of
  * 10 pixels around each overlap; dist1 < dist2 of the L1 distances (saturated at 8192) zeroes mask j there, anything else mask i) or

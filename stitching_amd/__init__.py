@@ -16,6 +16,7 @@ from .device import (Context, DeviceImage, as_device, device_count, get_context,
                      with_validity)
 from .exposure_error_compensator import ExposureErrorCompensator
 from .exposure_estimation import ExposureEstimator
+from .exposure_tracking import ExposureTracker
 from .feature_detector import FeatureDetector
 from .feature_estimation import FeatureEstimator, ImageFeatures
 from .feature_matcher import FeatureMatcher
@@ -33,7 +34,7 @@ from .timelapser import Timelapser
 from .warper import Warper
 
 __all__ = [
-    "AffineComposer", "Blender", "CameraAdjuster", "CameraEstimator", "CameraParams", "CameraSolver", "ColorSeamEstimator", "ComposePlan", "Composer", "Context", "Cropper", "Rectangle", "DeviceImage", "ExposureErrorCompensator", "ExposureEstimator", "FeatureDetector", "FeatureEstimator", "FeatureMatcher", "ImageFeatures", "Images", "MatchEstimator", "MatchesInfo", "MegapixDownscaler", "MegapixScaler", "StitchingError", "StitchingWarning",
+    "AffineComposer", "Blender", "CameraAdjuster", "CameraEstimator", "CameraParams", "CameraSolver", "ColorSeamEstimator", "ComposePlan", "Composer", "Context", "Cropper", "Rectangle", "DeviceImage", "ExposureErrorCompensator", "ExposureEstimator", "ExposureTracker", "FeatureDetector", "FeatureEstimator", "FeatureMatcher", "ImageFeatures", "Images", "MatchEstimator", "MatchesInfo", "MegapixDownscaler", "MegapixScaler", "StitchingError", "StitchingWarning",
     "SeamEstimator", "SeamFinder", "Subsetter", "Timelapser", "Warper", "WaveCorrector", "resize_linear_exact", "resize_linear_exact_all",
     "LensMap", "rectify", "rectify_all", "with_validity", "shrink_masks_all",
     "as_device", "emit", "emit_all", "ingest", "ingest_all", "parse_cuda_array_interface", "device_count", "pinned_empty", "device_resident", "get_context", "set_default_device", "set_device_resident", "set_trig_mode", "trig_mode", "set_remap_mode", "remap_mode", "set_pyrdown_mode", "pyrdown_mode",

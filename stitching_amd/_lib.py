@@ -35,6 +35,8 @@ EXPOSURE_KINDS = {"gain": 1, "gain_blocks": 2, "channel": 3, "channel_blocks": 4
 EXPOSURE_SOLVERS = {"host": 0, "device": 1}
 # the device LU of csrc/stx_solve.hip: pivots per blocked step, and the largest system it takes (8 n^2 bytes of device memory: 2 GiB)
 LU_NB, LU_MAX_N = 32, 16384
+# STX_TRACK_*: the limits of ExposureTracker (lattice stride, images, tile jobs of 32 x 32 lattice points)
+TRACK_STRIDE_MAX, TRACK_IMAGES_MAX, TRACK_TILES_MAX = 64, 1024, 65536
 SEAM_KINDS = {"no": 0, "voronoi": 1}
 # STX_COLOR_SEAM_MAX_*: the limits of ColorSeamEstimator (seam length: u32 accumulators; cross extent: accumulator rows in LDS)
 COLOR_SEAM_MAX_LENGTH, COLOR_SEAM_MAX_CROSS = 16384, 4096
@@ -167,6 +169,13 @@ PROTOTYPES = {
     "stx_exposure_feed_ex": [_vp, _i, _i, _vpp, _vpp, _ip, _i, _i, _i, _dp, _llp, _dp],
     "stx_exposure_solve_device": [_vp, _i, _i, _ip, _dp, _ubp, _dp, _dp],
     "stx_lu_solve_device": [_vp, _i, _dp, _dp, _dp, _dp],
+    "stx_exposure_track_create": [_vp, _i, _ip, _vpp, _i, _vpp],
+    "stx_exposure_track_pairs": [_vp, _ip, _ip, _llp],
+    "stx_exposure_track_measure": [_vp, _vpp],
+    "stx_exposure_track_collect": [_vp, _llp],
+    "stx_exposure_track_info": [_vp, _dp],
+    "stx_exposure_track_free": [_vp],
+    "stx_gain_maps_scale": [_vp, _i, _vpp, _fp, _i, _vpp],
     "stx_seam_find": [_vp, _i, _i, _ip, _ip, _vpp, _vpp, _dp],
     "stx_seam_schedule": [_i, _ip, _ip, _ip, _ip, _ip],
     "stx_color_seam_find": [_vp, _i, _ip, _ip, _vpp, _vpp, _vpp, _dp],

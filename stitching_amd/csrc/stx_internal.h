@@ -371,6 +371,30 @@ int stx_launch_exposure_block_mul(stx_ctx* ctx, const StxExpBlockMul* d_tab, int
 struct StxLuEntry { int row, col; double v; };
 constexpr int STX_LU_MAX_N = 16384;
 int stx_lu_device(stx_ctx* ctx, int n, const StxLuEntry* entries, size_t count, double* x, double out[3]);
+// exposure-gain tracking on a known rig (stx_exposure_track.hip, stx_exposure_track_host.cpp) -----------------
+// The lattice of stride s: panorama pixels (l s, m s).  Per image, made once per rig: the rectangle's corner, the first lattice
+// indices inside it (lx0, ly0), the lattice points per row (nx) and rows (ny), and where its V bytes start in the handle's grid block.
+struct StxTrackGeo { int x, y, lx0, ly0, nx, ny; long long voff; };
+// per image and measure: the warped, compensated u8x3 image of the rectangle
+struct StxTrackPix { const uint8_t* img; long long istride; };
+// a tile of one pair's lattice points: images a < b, the pair's index, the tile's first lattice indices and its extent
+// (1 .. STX_TRACK_TILE each way)
+struct StxTrackTile { int a, b, pair, lx, ly, nx, ny, pad_; };
+constexpr int STX_TRACK_WG = 256, STX_TRACK_TILE = 32, STX_TRACK_MAX_TILES = STX_TRACK_TILES_MAX, STX_TRACK_MAX_IMAGES = STX_TRACK_IMAGES_MAX,
+              STX_TRACK_MAX_STRIDE = STX_TRACK_STRIDE_MAX;  // the limits of include/stitching_amd.h
+// a lane's u32 partial holds at most (tile points / lanes) samples of at most 255 each, a wavefront's 64 times that
+static_assert((long long)STX_TRACK_TILE * STX_TRACK_TILE / STX_TRACK_WG * 255 * 64 < (1ll << 32), "tracking: a partial sum must fit 32 bits");
+// masks (u8x1 of the rectangles' sizes: pointer and pitch per image) -> V bytes (1: the mask is 255 at the lattice point) and c_ii
+// added into d_self[n] (cleared by the caller); max_points: the most lattice points of one image
+int stx_launch_exposure_track_grid(stx_ctx* ctx, int n, const StxTrackGeo* d_geo, const StxTrackPix* d_masks, int stride, long long max_points,
+                                   uint8_t* d_grid, unsigned long long* d_self);
+// one workgroup per tile; eight 64-bit integer sums per pair added into d_acc[8 pairs] (cleared by the caller)
+int stx_launch_exposure_track_stats(stx_ctx* ctx, const StxTrackGeo* d_geo, const StxTrackPix* d_pix, const StxTrackTile* d_tiles, int ntiles,
+                                    int stride, const uint8_t* d_grid, unsigned long long* d_acc, double algo_bytes);
+// out = map * factor in fp32, up to STX_SCALE_MAPS_PER_LAUNCH maps a launch; the factors travel in the kernel's arguments
+constexpr int STX_SCALE_MAPS_PER_LAUNCH = 32;
+struct StxScaleMap { const float* src; float* dst; long long sstride, dstride; int w, h, sc, dc; float f[3]; int pad_; };  // strides in floats
+int stx_launch_gain_maps_scale(stx_ctx* ctx, const StxScaleMap* maps, int n);
 // seam finding (stx_seams.hip, stx_seams_host.cpp) ----------------------------------------------------------------------------------
 // a pair of one level: masks i (m1) and j (m2) with their strides and sizes, the window's top-left in each image (roi - gap - corner),
 // window ww x wh, roi rw x rh (at (gap, gap) of the window), off: the pair's u16 distances in the level's arena (mask i's wh x rw plane,

@@ -464,7 +464,8 @@ class ShardedStitchJob:
 
     def __init__(self, frames, cameras, all_cameras, rank, world, all_sizes=None, warper_type="spherical",
                  blender_type="multiband", num_bands=5, blend_strength=None, ctx=None, group=None, transport=None,
-                 split_boundary=True, exchange="strips", mask_bits=True, balance=None, dist=None, compensator=None, seam_masks=None):
+                 split_boundary=True, exchange="strips", mask_bits=True, balance=None, dist=None, compensator=None, seam_masks=None,
+                 exposure_tracker=None):
         """blender_type / blend_strength: as stitching.blender.Blender (stitching/blender.py:5-38); for "multiband" `num_bands` sets the
         band count when blend_strength is None (the benchmark's way of naming a configuration).
         split_boundary (multiband): warp / feed the images that owe strips to other ranks first and the rest while the strips
@@ -481,7 +482,11 @@ class ShardedStitchJob:
         a rank sends are strips of compensated images, so the assembled panorama equals the single-GPU one.
         seam_masks: LOW-resolution seam masks by global image order (every rank holds all of them: a few KB each), resized on the device to
         each warped mask and ANDed with it (SeamFinder.resize, stitching/stitcher.py:124) before the image is fed or its strips are cut —
-        the masks are then grey along the seams and travel as bytes."""
+        the masks are then grey along the seams and travel as bytes.
+        exposure_tracker: refused — a tracker's statistics are those of one device's images; trackers across ranks do not exist."""
+        if exposure_tracker is not None:
+            raise StitchingError("ShardedStitchJob takes no exposure tracker: its statistics would cover this rank's images alone and "
+                                 "the ranks would drift apart; use StitchJob")
         if blender_type not in Blender.BLENDER_CHOICES:
             raise StitchingError(f"unknown blender type {blender_type!r}")
         if blender_type != "multiband" and exchange != "strips":

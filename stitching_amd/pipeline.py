@@ -215,12 +215,14 @@ class StitchJob:
     Between runs the job keeps what does not depend on the pixels (reuse_geometry=True): the ROIs, the rectangles it warps, the masks it
     feeds (the warped masks after SeamFinder.resize_all, slicing or cropping) and the weight pyramids of the multi-band blender — device
     memory of about P_w + 0.8 P_f bytes (P_w: pixels of the warped masks, P_f: pixels of the feed rectangles; roughly 150 MB for eight
-    4000 x 3000 frames at 5 bands) until release_geometry() or the end of the job.  Warped images are never kept."""
+    4000 x 3000 frames at 5 bands) until release_geometry() or the end of the job.  Warped images are never kept.  With an
+    exposure_tracker the job also keeps the tracker's lattice grids (P_w / stride^2 bytes) and every run measures its warped images for
+    the next one (stitching_amd.exposure_tracking)."""
 
     def __init__(self, frames, cameras, warper_type="spherical", blender_type="multiband", num_bands=None,
                  blend_strength=Blender.DEFAULT_BLEND_STRENGTH, ctx=None, async_upload=False, feed_masks=None, seam_masks=None,
                  crop_to_masks=True, compensator=None, cropper=None, crop_aspect=1, camera_aspect=1, reuse_geometry=True, source_masks=None,
-                 lenses=None):
+                 lenses=None, exposure_tracker=None):
         """async_upload: numpy frames in page-locked memory (pinned_empty) are only queued for upload; they must stay
         untouched until ctx.sync() (a streaming caller alternates two contexts).
         feed_masks: final-resolution u8 masks fed to the blender instead of the warped masks (seam masks already at the
@@ -256,7 +258,12 @@ class StitchJob:
         section 24) instead of rectifying first.  Cameras, source_masks, rectangles and ROIs belong to the rectified frames (the lenses'
         dst_size); the warped masks are those of a job over rectified frames, byte for byte; gains are applied as a second pass;
         source_masks="lens" takes the masks that rectification returns (rectify_all(masks=True), once, at construction).  The
-        panorama's pixels differ from rectify-then-warp (one bilinear blend instead of two)."""
+        panorama's pixels differ from rectify-then-warp (one bilinear blend instead of two).
+        exposure_tracker: an ExposureTracker (stitching_amd.exposure_tracking) — every run measures its warped,
+        compensated images on a lattice of the overlaps and the NEXT run applies compensator gains x the tracker's residual gains
+        (run 0: the compensator's own).  The compensator is read, never written.  One tracker per job; it needs reuse_geometry to
+        hold (the lattice grids are part of what the job keeps: about P_w / stride^2 bytes), so reuse_geometry=False and device-array
+        masks of the caller are refused with it.  The one host wait it adds is for the previous run's statistics, at the start of a run."""
         cropper, crop_aspect = _split_cropper(cropper, crop_aspect)
         if len(frames) != len(cameras) or not frames:
             raise StitchingError("need one camera per frame and at least one frame")
@@ -304,6 +311,25 @@ class StitchJob:
         self.last_reused = self.last_weights_adopted = False  # of the last run: kept geometry used / weight pyramids adopted by its blender
         self.feed_masks = None if feed_masks is None else [as_device(m, self.ctx) for m in feed_masks]
         self.seam_masks = None if seam_masks is None else [as_device(m, self.ctx) for m in seam_masks]
+        self.exposure_tracker, self._tracked = exposure_tracker, None
+        if exposure_tracker is not None:
+            from .exposure_tracking import ExposureTracker, _TrackedCompensator
+
+            if not isinstance(exposure_tracker, ExposureTracker):
+                raise StitchingError(f"exposure_tracker= takes an ExposureTracker, got {type(exposure_tracker).__name__}")
+            if not self.reuse_geometry:
+                raise StitchingError("an exposure tracker measures on what the job keeps between runs: it needs reuse_geometry=True and masks "
+                                     "that belong to the job (host arrays, not device arrays of the caller)")
+            exposure_tracker._bind(self, len(self.frames))
+            self._tracked = _TrackedCompensator(compensator, exposure_tracker)
+
+    def _run_compensator(self):
+        """the compensator of this run: the job's own, or with a tracker the one that applies its gains x the tracker's residuals —
+        after collect + update for the previous run"""
+        if self._tracked is None:
+            return self.compensator
+        self._tracked.refresh(self.exposure_tracker._begin_run())
+        return self._tracked
 
     def _with_source_masks(self, frames):
         """the job's validity masks on (new) frames: new handles, the frames' own are not changed"""
@@ -354,6 +380,8 @@ class StitchJob:
             g.weights.free()
         if g is not None:
             g.tables.free()
+        if self.exposure_tracker is not None:
+            self.exposure_tracker._release()  # the lattice grids go with the geometry; the residual gains survive
 
     def geometry_key(self):
         """rig_key of the job as it stands now"""
@@ -377,16 +405,19 @@ class StitchJob:
                 self.release_geometry()
                 g = None
             self.last_reused, self.last_weights_adopted = g is not None, False
+            compensator = self._run_compensator()
             if g is None:
-                g, imgs = self._geometry_pass()
+                g, imgs = self._geometry_pass(compensator)
                 g.key = key
             else:
                 # a panorama of a known rig: the images alone, into the kept rectangles (no ROI pass, no wait, no mask, no seam_resize)
                 imgs, _, _ = self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect, rects=g.rects,
-                                                               compensator=self.compensator if g.gain_in_warp else None,
+                                                               compensator=compensator if g.gain_in_warp else None,
                                                                camera_arrays=self._cam_arrays, masks=False, tables=g.tables)
-                if self.compensator is not None and not g.gain_in_warp:
-                    imgs = self.compensator.apply_all(g.gain_corners, imgs, None, sub=g.gain_sub, ctx=self.ctx)
+                if compensator is not None and not g.gain_in_warp:
+                    imgs = compensator.apply_all(g.gain_corners, imgs, None, sub=g.gain_sub, ctx=self.ctx)
+            if self.exposure_tracker is not None:  # the images are final: their statistics ride along, for the next run
+                self.exposure_tracker._measure(imgs)
             self.last_crop = g.crop
             blender, g.blender = g.blender, None
             if blender is None:
@@ -408,20 +439,20 @@ class StitchJob:
             config.set_device_resident(prev)
         return pano, pmask
 
-    def _geometry_pass(self):
+    def _geometry_pass(self, compensator):
         """The first run of a rig (every run of a job that keeps nothing): ROI pass, warps WITH masks, the masks' way to the blender.
         -> (_RigGeometry, warped images).  The one piece of code that decides rectangles, feed corners and feed masks, for the plain path,
-        the seam-cell crops and a cropper alike."""
+        the seam-cell crops and a cropper alike.  compensator: the run's (_run_compensator)."""
         # one ROI pass (the reference's eager Warper.warp_rois, stitching/stitcher.py:188), batched: one device pass, one wait.  It is the
         # ONE point where the host waits for the device and the device then waits for the host: without seam-cell crops (which need the
         # ROIs before the warps) pass and warps are one native call, and everything Python does with the ROIs happens behind the warp
         # launch (profiles/r05_latency.md)
         g = _RigGeometry()
         if self.cropper is not None:
-            return self._geometry_pass_cropped(g)
+            return self._geometry_pass_cropped(g, compensator)
         warped = None
         if self._mask_cols is None:
-            warped = self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect, compensator=self.compensator,
+            warped = self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect, compensator=compensator,
                                                        with_rois=True, camera_arrays=self._cam_arrays,
                                                        tables=g.tables if self.reuse_geometry else None)
             self._adopt([r[0:2] for r in warped[2]], [r[2:4] for r in warped[2]])
@@ -436,8 +467,9 @@ class StitchJob:
             box = [c if c is not None else (0, w, 0, h) for c, (w, h) in zip(crop, self.warped_sizes)]
             rects = [(cx + x0, cy + y0, x1 - x0, y1 - y0) for (x0, x1, y0, y1), (cx, cy) in zip(box, self.corners)]
             imgs, masks, rois = self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect, rects=rects,
-                                                                  compensator=self.compensator, camera_arrays=self._cam_arrays,
+                                                                  compensator=compensator, camera_arrays=self._cam_arrays,
                                                                   tables=g.tables if self.reuse_geometry else None)
+            self._track_rig(rects, masks)
             if self.feed_masks is not None:
                 masks = [m[y0:y1, x0:x1] for m, (x0, x1, y0, y1) in zip(self.feed_masks, box)]
             else:
@@ -446,7 +478,8 @@ class StitchJob:
             corners = [(r[0], r[1]) for r in rects]
         else:
             imgs, masks, rois = warped or self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect,
-                                                                            compensator=self.compensator, camera_arrays=self._cam_arrays)
+                                                                            compensator=compensator, camera_arrays=self._cam_arrays)
+            self._track_rig(rois, masks)
             if self.feed_masks is not None:
                 masks = self.feed_masks
             elif self.seam_masks is not None:
@@ -461,7 +494,12 @@ class StitchJob:
         g.feed_corners, g.feed_masks = list(corners), list(masks)
         return g, imgs
 
-    def _geometry_pass_cropped(self, g):
+    def _track_rig(self, rects, masks):
+        """right behind the warp that returned masks: a tracker's lattice grids of these rectangles and warped masks"""
+        if self.exposure_tracker is not None:
+            self.exposure_tracker._create(self.ctx, [tuple(int(v) for v in r) for r in rects], masks)
+
+    def _geometry_pass_cropped(self, g, compensator):
         """_geometry_pass with a cropper (device residency is on): the ROI pass first, then only the cropper's rectangle of every image —
         and inside it, with host seam masks and the multi-band blender, only what the seam cell can reach (view_rects)."""
         self.plan()
@@ -488,9 +526,10 @@ class StitchJob:
         rects = [(cx + c[0] + x0, cy + c[2] + y0, x1 - x0, y1 - y0) for (x0, x1, y0, y1), c, (cx, cy) in zip(box, cuts, self.corners)]
         imgs, masks, _ = self.warper.warp_images_and_masks(self.frames, self.cameras, self.camera_aspect, rects=rects,
                                                            camera_arrays=self._cam_arrays)
+        self._track_rig(rects, masks)
         sub = None if crop is None else [(w, h, x0, y0) for (x0, x1, y0, y1), (w, h) in zip(box, cut_sizes)]
-        if self.compensator is not None:  # over the CROPPED image (apply on a crop); a seam-cell rectangle carries its offset in it
-            imgs = self.compensator.apply_all(corners, imgs, None, sub=sub, ctx=self.ctx)
+        if compensator is not None:  # over the CROPPED image (apply on a crop); a seam-cell rectangle carries its offset in it
+            imgs = compensator.apply_all(corners, imgs, None, sub=sub, ctx=self.ctx)
         if self.feed_masks is not None:
             masks = [m if b == (0, m.width, 0, m.height) else m[b[2]:b[3], b[0]:b[1]] for m, b in zip(self.feed_masks, box)]
         elif self.seam_masks is not None:
@@ -600,7 +639,8 @@ class ComposePlan:
     rig's masks and weight pyramids between runs (StitchJob's memory note; `plan.job.release_geometry()` gives them back)."""
 
     def __init__(self, images, frames, cameras, warper_scale, cropper, compensator, seam_masks, seam_masks_host, low_corners, low_sizes,
-                 source_masks=None, distorted=None, lenses=None):
+                 source_masks=None, distorted=None, lenses=None, exposure_tracker=None):
+        self.exposure_tracker = exposure_tracker  # Composer.prepare(exposure_tracker=): handed to the plan's StitchJob
         self.images, self.frames, self.cameras, self.warper_scale = images, frames, list(cameras), warper_scale
         # lens_mode="fused": the distorted frames the plan was prepared from and their lenses (`frames` are their rectified forms, which
         # the low-resolution pass read); None, None otherwise
@@ -711,7 +751,7 @@ class Composer:
                 out[i] = m
         return OwnedMasks(out) if isinstance(source_masks, OwnedMasks) else out
 
-    def prepare(self, images, cameras, lenses=None, source_masks=None, lens_mode="rectify"):
+    def prepare(self, images, cameras, lenses=None, source_masks=None, lens_mode="rectify", exposure_tracker=None):
         """The low-resolution half -> ComposePlan.  The host waits for the device where a result decides what is launched next: the ROI
         pass of the warp, the cropper's rectangle, the gain solve (and the read-back of the seam masks for the multi-band blender's
         seam-cell crops).  lenses: one LensMap per image, or one for all — the images are then distorted frames and are rectified
@@ -723,7 +763,15 @@ class Composer:
         masks and a lens's are not combined.
         lens_mode: "rectify" (the default): as above.  "fused" (needs lenses): the low-resolution pass still reads rectified frames —
         it runs once per rig — but the plan keeps the DISTORTED frames and the lenses, and `run` warps through the lens (StitchJob with
-        lenses).  Refused with a final_megapix that resizes the frames: a lens belongs to the frame's own size."""
+        lenses).  Refused with a final_megapix that resizes the frames: a lens belongs to the frame's own size.
+        exposure_tracker: an ExposureTracker kept on the plan: `run` gives it to the plan's StitchJob, whose runs then follow the
+        cameras' exposure from frame to frame on top of the gains estimated here.  `compose` and `stitch` make
+        one panorama and take none."""
+        if exposure_tracker is not None:
+            from .exposure_tracking import ExposureTracker
+
+            if not isinstance(exposure_tracker, ExposureTracker):
+                raise StitchingError(f"exposure_tracker= takes an ExposureTracker, got {type(exposure_tracker).__name__}")
         frames, cameras = list(images), list(cameras)
         fused = check_lens_mode(lens_mode, lenses)
         distorted = frames if fused else None
@@ -774,7 +822,7 @@ class Composer:
         finally:
             config.set_device_resident(prev)
         return ComposePlan(imgs_obj, frames, cameras, warper.scale, cropper, compensator, seam_masks, host, corners, sizes,
-                           source_masks=source_masks, distorted=distorted, lenses=lenses if fused else None)
+                           source_masks=source_masks, distorted=distorted, lenses=lenses if fused else None, exposure_tracker=exposure_tracker)
 
     def run(self, plan, images=None, lenses=None):
         """The final-resolution half on a plan: `images` None -> the frames the plan was prepared from, else new frames of the same rig
@@ -803,13 +851,16 @@ class Composer:
         # one job per plan: its second run warps pixels only (same rig, new frames)
         job_key = (id(ctx), st["warper_type"], st["blender_type"], st["blend_strength"])
         if plan.job is None or plan.job_key != job_key:
+            if getattr(plan, "exposure_tracker", None) is not None:
+                plan.job = None  # a tracker follows one job at a time: the old one goes first
             plan.job = StitchJob(final, plan.cameras, warper_type=st["warper_type"], blender_type=st["blender_type"],
                                  blend_strength=st["blend_strength"], ctx=ctx,
                                  seam_masks=plan.seam_masks_host if plan.seam_masks_host is not None else plan.seam_masks,
                                  compensator=plan.compensator, cropper=plan.cropper, crop_aspect=plan.lir_aspect,
                                  camera_aspect=plan.camera_aspect,
                                  source_masks=None if plan.source_masks is None else
-                                 self._shrunk(plan.source_masks, [(f.width, f.height) for f in final]))
+                                 self._shrunk(plan.source_masks, [(f.width, f.height) for f in final]),
+                                 exposure_tracker=getattr(plan, "exposure_tracker", None))
             plan.job_key = job_key
             return plan.job.run()
         return plan.job.run(frames=final)
@@ -829,11 +880,14 @@ class Composer:
         st, ctx = self.settings, self._ctx()
         job_key = (id(ctx), st["warper_type"], st["blender_type"], st["blend_strength"], "fused", tuple(id(lens) for lens in lenses))
         if plan.job is None or plan.job_key != job_key:
+            if getattr(plan, "exposure_tracker", None) is not None:
+                plan.job = None  # a tracker follows one job at a time: the old one goes first
             plan.job = StitchJob(frames, plan.cameras, warper_type=st["warper_type"], blender_type=st["blender_type"],
                                  blend_strength=st["blend_strength"], ctx=ctx,
                                  seam_masks=plan.seam_masks_host if plan.seam_masks_host is not None else plan.seam_masks,
                                  compensator=plan.compensator, cropper=plan.cropper, crop_aspect=plan.lir_aspect,
-                                 camera_aspect=plan.camera_aspect, source_masks=plan.source_masks, lenses=lenses)
+                                 camera_aspect=plan.camera_aspect, source_masks=plan.source_masks, lenses=lenses,
+                                 exposure_tracker=getattr(plan, "exposure_tracker", None))
             plan.job_key = job_key
             return plan.job.run()
         return plan.job.run(frames=frames)
